@@ -1,9 +1,17 @@
 #!/usr/bin/env python
 """bench.py -- CG iterations/s + achieved SpMV HBM GB/s on the 3D 7-point Laplacian (fp64).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one cg! iteration (iterate(::CGIterable), src/cg.jl:43-66) on synthetic input already resident in HBM.
+
+N = 1, plain run: set-up, W warm-up steps, EXACTLY K timed steps between two synchronisations, the line -- `metric`, `value`
+       (iterations/s of the contract loop), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (K steps' wall time / K) and little else.
+       Everything below that is not the headline (parity, the default-layout loop, roofline, per-kernel figures, the sub-benchmarks,
+       the CPU baselines) runs only with --full, which keeps the same headline measurement in front of it.
+--dump-outputs DIR: after the timed steps, what they computed -- DIR/x.npy and DIR/r.npy (the solution and residual vectors after
+       the last step; a fixed, seeded sample of DUMP_SAMPLE entries when n is larger) and DIR/resnorm.npy (the residual norm each
+       timed step returned), float64.  The inputs depend only on the arguments, so two builds can be compared output for output.
 
 N = 1: BASELINE.json configs[1] -- cg! on the 256^3 Laplacian through the fused single-GPU iterable.
 N > 1: BASELINE.json configs[3] -- the same iteration row-partitioned into z-slabs, one process per GPU, halo exchange
@@ -11,14 +19,14 @@ N > 1: BASELINE.json configs[3] -- the same iteration row-partitioned into z-sla
        512^3 grid (64 planes and two 512^2-double halos per rank); N = 2, 4 are its weak-scaled pieces 512 x 512 x 64N
        (16.7 M rows per GPU throughout, like the single-GPU 256^3).  If the process was not started by
        torch.distributed.run (WORLD_SIZE unset) bench.py launches the N ranks itself.
-Rank 0 prints ONE JSON line.  At every N:
+Rank 0 prints ONE JSON line.  At every N (at N = 1 with --full):
   `value` / `ms_per_step`  the CONTRACT loop: the operator (every rank's slab) on its plain Int32 CSR arrays (k_spmv_rowgather), one
                            host-visible residual per step like the reference's loop; iterations/s of the one (global) system;
                            `value_bytes_per_step[_per_gpu]` = SURVEY.md 8d's B_cg, so bytes / ms <= 8 TB/s is checkable from the top level
   `roofline`               SURVEY.md 8d bytes of the CSR SpMV over the in-loop HIP-event time of that kernel, + the loop it was timed in
   `default_layout_*`       the same iteration in the layout mik_csr_create picks by itself (one mask byte per row for this
                            constant-coefficient operator; bit-identical results) -- reported, NOT the contract figure
-N = 1 adds: parity_full_history (the 613-step solve against the committed CPU histories), gmres_hbm_bound (gmres!(30) at 256^3),
+N = 1 with --full adds: parity_full_history (the 613-step solve against the committed CPU histories), gmres_hbm_bound (gmres!(30) at 256^3),
 f_solvers (PCG / Chebyshev / MINRES / BiCGStab(2)), gmres_config3 (configs[2]), config5 (configs[4] stand-ins), cpu_baseline (+ OpenMP).
 N > 1 adds: parity_vs_oracle (every transport on a small global system against the partition-aware oracle), transports_measured.
 """
@@ -40,7 +48,9 @@ import __graft_entry__ as graft  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (MI355X_MICROARCH.md); measured copy ceiling 6290 GB/s
 COPY_CEILING_GBS = 6290.0
-MIN_TIMED_SECONDS = float(os.environ.get("MIK_BENCH_MIN_SECONDS", "0.25"))   # the K-step timed region is repeated until this much has been measured
+MIN_TIMED_SECONDS = float(os.environ.get("MIK_BENCH_MIN_SECONDS", "0.25"))   # --full: the K-step regions of its loops are repeated until this much has been measured
+DUMP_SAMPLE = 1 << 20            # --dump-outputs: entries of x and r written (all of them up to this n, else a seeded sample)
+DUMP_SEED = 20240917
 
 
 def cpu_model() -> str:
@@ -578,6 +588,41 @@ def stencil27(grid: int, steps: int):
     return out
 
 
+def headline_steps(A, b, K: int, Wm: int, layout: str):
+    """The headline measurement of every N = 1 run: cg! with reltol = 0 (every step does identical work) on A in `layout`, Wm warm-up
+    steps, then EXACTLY K steps between two synchronisations, one host-visible residual per step like the reference's loop.
+    Returns the iterable (its x and r hold the state after step Wm + K), the K residuals and the seconds the K steps took."""
+    import torch
+    pkg = graft.load_package()
+    A.set_layout(layout)
+    it = pkg.cg_iterator_(pkg.zerox(A, b), A, b, reltol=0.0, initially_zero=True, maxiter=10 ** 9)
+    for k in range(Wm):
+        if it.iterate(k) is None:
+            raise RuntimeError(f"cg! stopped during warm-up step {k + 1}")
+    res = np.empty(K, np.float64)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for j in range(K):
+        nxt = it.iterate(Wm + j)
+        if nxt is None:
+            raise RuntimeError(f"cg! stopped at timed step {j + 1}")
+        res[j] = nxt[0]
+    torch.cuda.synchronize()
+    return it, res, time.perf_counter() - t0
+
+
+def dump_outputs(path: str, it, residuals: np.ndarray):
+    """--dump-outputs: what the timed steps computed, as a caller of cg_iterator! receives it -- x and r after the last step (all of
+    them up to DUMP_SAMPLE entries, else the same seeded sample of indices in every run) and the residual of every timed step."""
+    os.makedirs(path, exist_ok=True)
+    x, r = it.x.to_numpy(), it.r.to_numpy()          # mik_memcpy_d2h: ordered after the last step's work on the ctx stream
+    n = x.size
+    idx = slice(None) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    np.save(os.path.join(path, "x.npy"), np.ascontiguousarray(x[idx], np.float64))
+    np.save(os.path.join(path, "r.npy"), np.ascontiguousarray(r[idx], np.float64))
+    np.save(os.path.join(path, "resnorm.npy"), np.asarray(residuals, np.float64))
+
+
 def run_single(args):
     import torch
     pkg = graft.load_package()
@@ -587,11 +632,46 @@ def run_single(args):
     t_up = time.perf_counter()
     A = pkg.HipCSR(n, n, colptr, rowval, nzval, index_base=1)
     upload_seconds = time.perf_counter() - t_up
-    csc = (colptr, rowval, nzval) if (args.extras and not args.no_f_solvers and N >= 128) else None     # --extras: kept for the adjoint operator of the LSQR / LSMR / QMR leg
+    csc = (colptr, rowval, nzval) if (args.full and args.extras and not args.no_f_solvers and N >= 128) else None     # --extras: kept for the adjoint operator of the LSQR / LSMR / QMR leg
     del colptr, rowval, nzval
     nnz = A.nnz
     b = pkg.HipVector.from_numpy(pkg.fixtures.hashed_rhs(n))
     sync = torch.cuda.synchronize
+
+    # ---- (0) the headline, in every run: EXACTLY K timed steps of the contract loop on the plain CSR arrays -------------
+    # (mik_csr_set_layout(A, 0): Int32 CSR, k_spmv_rowgather, moving SURVEY.md 8d's B_cg = B_spmv + 9 n s per step; --no-csr: the default layout)
+    layout = A.layout()
+    value_is_csr = not args.no_csr or layout == "csr-rowblock"
+    alg_bytes = A.spmv_algorithmic_bytes()         # SURVEY.md 8d: nnz*(s+4) + (n+1)*4 + 2*n*s
+    iter_alg = alg_bytes + 9 * n * 8               # B_cg = B_spmv + 9 n s
+    try:
+        hit, hres, hsec = headline_steps(A, b, K, Wm, "csr" if value_is_csr else "auto")
+        h_layout, h_kernel = A.layout(), A.spmv_kernel()
+        v_bytes = iter_alg if value_is_csr else A.spmv_stored_bytes() + (8 if hit.fused_x() else 9) * n * 8
+    finally:
+        A.set_layout("auto")
+    v_ips, v_ms = K / hsec, hsec / K * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, hit, hres)
+    del hit
+    out = {
+        "metric": "cg_iters_per_sec", "value": v_ips, "unit": "iters/s", "n_gpus": 1, "steps": K, "warmup": Wm,
+        "ms_per_step": v_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "value_is_contract": bool(value_is_csr),
+        "value_bytes_per_step": v_bytes,
+        "value_gbs": v_bytes / (v_ms * 1e-3) / 1e9,
+        "config": {"workload": f"cg! on {N}^3 3D 7-point Laplacian (test/laplace_matrix.jl), fp64, hashed rhs, x0 = 0 "
+                               f"(BASELINE.json configs[1])", "n": n, "nnz": nnz, "reltol_in_timed_loop": 0.0, "host_sync_per_step": 1,
+                   "operator_layout_of_the_timed_loop": f"csr (mik_csr_set_layout(A, 0): Int32 rowptr / col / val, {h_kernel})" if value_is_csr else h_layout,
+                   "timed_steps": K, "timed_regions": 1, "timed_seconds": hsec,
+                   "operator_upload_seconds": upload_seconds, "final_residual": float(hres[-1]),
+                   "machine": {k: v for k, v in ctx.info().items() if k in ("arch", "compute_units", "xcds", "lds_bytes_per_cu", "l2_bytes", "hbm_bytes", "xcd_maps",
+                                                                             "resident_workgroup_cap", "gs_single_launch_max_segments", "mgs_resident_max_segments")}},
+    }
+    if not args.full:
+        print(json.dumps(out))
+        return
 
     # ---- (1) the full solve to the default tolerance: parity of the WHOLE residual history -------------------
     parity = None
@@ -627,8 +707,6 @@ def run_single(args):
         tb = timed_regions(batch, max(1, K // 25), sync)
         return it, times, prof, tb, max(1, K // 25) * 25
 
-    alg_bytes = A.spmv_algorithmic_bytes()         # SURVEY.md 8d: nnz*(s+4) + (n+1)*4 + 2*n*s
-    layout = A.layout()
     it, times, (spmv_ms_total, spmv_launches), tb, kb = timed_loop(A)
     dt = float(np.median(times))
     spmv_ms = spmv_ms_total / max(spmv_launches, 1)
@@ -689,8 +767,7 @@ def run_single(args):
                "final_residual": residual}
 
     moved_gbs = stored_bytes / (spmv_ms * 1e-3) / 1e9
-    iter_moved = stored_bytes + (8 if fx else 9) * n * 8          # bytes ONE step of the loop behind `value` moves (its SpMV + the two sweeps)
-    iter_alg = alg_bytes + 9 * n * 8                               # B_cg = B_spmv + 9 n s
+    iter_moved = stored_bytes + (8 if fx else 9) * n * 8          # bytes ONE step of the default-layout loop moves (its SpMV + the two sweeps)
     d_tf = traffic_fields(kern)
     default_spmv = {"kernel": kern + "<double, fused dot>", "operator_layout": layout, "bytes_moved_per_launch": stored_bytes, "avg_launch_ms": spmv_ms,
                     "launches_timed": int(spmv_launches), "back_to_back_ms": b2b_ms, "achieved_moved": moved_gbs, "frac_moved": moved_gbs / HBM_PEAK_GBS,
@@ -727,31 +804,9 @@ def run_single(args):
     # moves SURVEY.md 8d's B_cg = B_spmv + 9 n s per step -- so value_bytes_per_step / ms_per_step <= 8 TB/s can be checked from the top level alone.
     # The same iteration in the layout mik_csr_create picks by itself for this constant-coefficient operator (one mask byte per row,
     # bit-identical results) is reported next to it as `default_layout_iters_per_sec`.
-    value_is_csr = csr is not None
-    v_ips, v_ms = (csr["iters_per_sec"], csr["ms_per_step"]) if value_is_csr else (K / dt, dt / K * 1e3)
-    v_regions = csr["timed_regions"] if value_is_csr else len(times)
-    out = {
-        "metric": "cg_iters_per_sec", "value": v_ips, "unit": "iters/s", "n_gpus": 1, "steps": K, "warmup": Wm,
-        "ms_per_step": v_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "value_is_contract": bool(value_is_csr),
-        "value_bytes_per_step": iter_alg if value_is_csr else iter_moved,
-        "value_gbs": (iter_alg if value_is_csr else iter_moved) / (v_ms * 1e-3) / 1e9,
+    # `value` / `ms_per_step` themselves are the headline's exactly-K-step region (0) above; contract_csr_loop repeats that loop in regions of K steps.
+    out.update({
         "default_layout_iters_per_sec": K / dt, "default_layout_ms_per_step": dt / K * 1e3,
-        "config": {"workload": f"cg! on {N}^3 3D 7-point Laplacian (test/laplace_matrix.jl), fp64, hashed rhs, x0 = 0 "
-                               f"(BASELINE.json configs[1])", "n": n, "nnz": nnz, "reltol_in_timed_loop": 0.0, "host_sync_per_step": 1,
-                   "operator_layout_of_the_timed_loop": "csr (mik_csr_set_layout(A, 0): Int32 rowptr / col / val, k_spmv_rowgather)" if value_is_csr else layout,
-                   "timed_regions": v_regions,
-                   "operator_upload_seconds": upload_seconds, "final_residual": csr["final_residual"] if value_is_csr else residual,
-                   "machine": {k: v for k, v in ctx.info().items() if k in ("arch", "compute_units", "xcds", "lds_bytes_per_cu", "l2_bytes", "hbm_bytes", "xcd_maps",
-                                                                             "resident_workgroup_cap", "gs_single_launch_max_segments", "mgs_resident_max_segments")},
-                   "default_layout": {"operator_layout": layout, "iters_per_sec": K / dt, "ms_per_step": dt / K * 1e3,
-                                      "bytes_per_step": iter_moved, "gbs": iter_moved / (dt / K) / 1e9,
-                                      "frac_of_8000": iter_moved / (dt / K) / 1e9 / HBM_PEAK_GBS, "spmv_avg_launch_ms": spmv_ms,
-                                      "timed_regions": len(times), "timed_seconds_total": float(sum(times)),
-                                      "region_seconds_min_max": [float(min(times)), float(max(times))], "final_residual": residual,
-                                      "note": "what cg! does on this input when the layout is left to mik_csr_create: the SpMV streams one mask byte per row "
-                                              "instead of the CSR arrays (constant-coefficient operator), same residual history bit for bit; NOT the contract figure"}},
         "contract_csr_loop": csr,
         "roofline": roofline,
         "default_layout_spmv": default_spmv,
@@ -766,7 +821,14 @@ def run_single(args):
         "contract_cg_iteration_gbs": (iter_alg / (csr["ms_per_step"] * 1e-3) / 1e9) if csr else None,
         "batched_25_steps_per_sync_iters_per_sec": kb / float(np.median(tb)),
         "parity_full_history": parity,
-    }
+    })
+    out["config"].update({"default_layout": {"operator_layout": layout, "iters_per_sec": K / dt, "ms_per_step": dt / K * 1e3,
+                                      "bytes_per_step": iter_moved, "gbs": iter_moved / (dt / K) / 1e9,
+                                      "frac_of_8000": iter_moved / (dt / K) / 1e9 / HBM_PEAK_GBS, "spmv_avg_launch_ms": spmv_ms,
+                                      "timed_regions": len(times), "timed_seconds_total": float(sum(times)),
+                                      "region_seconds_min_max": [float(min(times)), float(max(times))], "final_residual": residual,
+                                      "note": "what cg! does on this input when the layout is left to mik_csr_create: the SpMV streams one mask byte per row "
+                                              "instead of the CSR arrays (constant-coefficient operator), same residual history bit for bit; NOT the contract figure"}})
     if not args.no_gmres_large and N >= 128:
         A.set_layout("csr")
         try:
@@ -892,8 +954,12 @@ def launch_ranks(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (N = 1: exactly this many, in one region)")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true", help="N = 1: after the headline, everything else the line reports (parity, default-layout loop, "
+                                                        "roofline and per-kernel figures, sub-benchmarks, CPU baselines); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="N = 1: write x, r (sampled beyond 2^20 entries) and the timed steps' residuals "
+                                                                         "as DIR/<name>.npy, float64")
     ap.add_argument("--grid", dest="n", type=int, default=None, help="grid points per dimension (default: 256 at N = 1, 512 x 512 x 64 N at N > 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the full solve compared with tests/golden/")
@@ -908,6 +974,10 @@ def main():
     ap.add_argument("--cpu-iters", type=int, default=100, help="iterations of the CPU baseline's bounded sample (about 12 s of one EPYC core at 256^3)")
     ap.add_argument("--force-dist", action="store_true", help="run the row-partitioned code path even with one rank")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus > 1 or args.force_dist):
+        ap.error("--dump-outputs is implemented for the single-GPU line (--gpus 1) only")
 
     world = int(os.environ.get("WORLD_SIZE", "0"))
     if args.gpus > 1 and world == 0:

@@ -7,7 +7,7 @@ cd $R
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout 1200 python -m pytest tests -m gpu -x -q > $O/pytest_gpu_final.log 2>&1; echo "pytest rc=$?"
 grep -E "passed|failed|error" $O/pytest_gpu_final.log | tail -3
-( time timeout 600 python bench.py > $O/bench_final.json 2> $O/bench_final.err ) 2>&1 | grep real; echo "bench rc=$?"
+( time timeout 600 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err ) 2>&1 | grep real; echo "bench rc=$?"
 tail -2 $O/bench_final.err
 MIK_FORCE_DEVICE=0 MIK_NATIVE_TRANSPORTS=mailbox timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 50 --warmup 5 --cpu-iters 5 > $O/bench_2ranks_1gpu_final.json 2> $O/bench_2ranks_1gpu_final.err; echo "bench2 rc=$?"
 timeout 200 python scripts/adjoint_solver_bench.py > $O/adjoint_solver_bench.json 2> $O/adjoint_solver_bench.err; echo "adjoint bench rc=$?"; cat $O/adjoint_solver_bench.json

@@ -26,3 +26,14 @@ def test_world_size_mismatch_is_rejected():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode != 0 and "WORLD_SIZE=2" in (p.stderr + p.stdout)
+
+
+def test_plain_and_full_options_are_there_and_steps_are_checked():
+    """--full gates everything but the headline; --steps is the number of timed steps, so fewer than one is refused before any work"""
+    h = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert h.returncode == 0 and "--full" in h.stdout and "--dump-outputs" in h.stdout
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--warmup", "0"], capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and "--steps must be at least 1" in p.stderr and '"metric"' not in p.stdout
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--dump-outputs", "d"], capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode != 0 and "single-GPU line" in p.stderr and '"metric"' not in p.stdout
