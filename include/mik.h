@@ -63,7 +63,9 @@ extern "C" {
 #endif
 
 #define MIK_ABI_VERSION 6   /* 6 (round 6): mik_ctx_info / mik_device_info (the machine is queried, not assumed); mik_plink_exchange;
-                             *   mik_comm_allgather_sum also over a mailbox-only communicator.
+                             *   mik_comm_allgather_sum also over a mailbox-only communicator.  Added later, without a version bump (additive):
+                             *   the stationary methods (mik_stationary_*, mik_diag_ldiv, mik_offdiag_mul, mik_gs_multiply, mik_forward_sub,
+                             *   mik_backward_sub).
                              *   5 (round 5): mik_partition gained `link`; the pushed halo lands in library-owned buffers (mik_plink_*, mik_cgd_ghost_export;
                              *   mik_cgd_connect_ghosts takes ghost counts instead of byte offsets; mik_mem_export is gone); mik_cgd_profile.
                              *   4 (round 4): MIK_ERR_SINGULAR replaces MIK_ERR_INVALID for an exactly singular pivot (mik_lu_solve, mik_bicgstab_step);
@@ -81,7 +83,8 @@ enum {
     MIK_ERR_CALLBACK = 6,    /* a mik_partition / operator / preconditioner callback returned non-zero */
     MIK_ERR_RANGE = 7,       /* a norm left the safe range while the HOST drives the phases of a row-partitioned step itself (see "Norms") */
     MIK_ERR_SINGULAR = 8     /* lu! met an exactly singular pivot (the reference throws SingularException, src/bicgstabl.jl:124): mik_lu_solve,
-                              * mik_bicgstab_step -- a code of its own, so that an invalid handle is never reported as a singular matrix */
+                              * mik_bicgstab_step -- a code of its own, so that an invalid handle is never reported as a singular matrix;
+                              * mik_stationary_create: a zero or missing diagonal entry (src/stationary_sparse.jl:19) */
 };
 
 enum { MIK_F64 = 0, MIK_F32 = 1 };
@@ -599,6 +602,42 @@ int mik_hessenberg_ldiv(int dtype, void *H, int64_t ldh, int width, void *rhs);
 /* Host: LinearAlgebra.givensAlgorithm(f, g) -> out = {c, s, r} with [c s; -s c] [f; g] = [r; 0]
  * (src/hessenberg.jl:24, src/minres.jl:129).  f, g, out: host scalars / 3-array of dtype. */
 int mik_givens(int dtype, const void *f, const void *g, void *out);
+
+/* ---- stationary methods: jacobi / gauss_seidel / sor / ssor on a SparseMatrixCSC (src/stationary_sparse.jl) ------------------
+ * The building blocks of the four iterables, one entry each.  Every row is summed by one lane, serially, in the order the
+ * reference's CSC column loop delivers its terms (no wave tree, no FMA), so the results are bit-identical to the reference's:
+ *   mik_offdiag_mul      row i: y[i] = 0 | y[i] | beta*y[i], then y[i] += A[i,j] * (alpha*x[j]) for j != i ascending
+ *   mik_gs_multiply  U:  z[i] = beta*y[i], then += A[i,j] * (alpha*x[j]) for j > i ascending (x: the OLD vector)
+ *                    L:  the same for j < i DESCENDING
+ *   mik_forward_sub      x[i] -= A[i,j]*x[j] for j < i ascending (x[j] already new), then x[i] /= A[i,i]
+ *                        (relaxed form: x[i] = alpha*x[i]/A[i,i] + beta*y[i])
+ *   mik_backward_sub     the same for j > i DESCENDING
+ * The triangular sweeps run a level schedule of the strict triangle built in mik_stationary_create: one launch per level with more
+ * than 256 rows, one one-workgroup launch per run of narrower levels (a barrier between its levels).  Their cost is the number of
+ * levels: a tridiagonal matrix (one row per level) stays latency-bound.  Asynchronous on the ctx stream. */
+typedef struct mik_stationary mik_stationary;    /* DiagonalIndices + the triangular views of one square operator -- :6-64 */
+/* DiagonalIndices(A) (:6-28) + both level schedules.  Reads A's CSR arrays once (A's layouts are untouched; A must outlive *out).
+ * MIK_ERR_SINGULAR with *singular_col = the first 1-based column whose diagonal entry is missing or zero (-0.0 included);
+ * MIK_ERR_MISMATCH for a non-square operator; MIK_ERR_NOTIMPL after mik_csr_compact released the CSR arrays.  Synchronises. */
+int mik_stationary_create(mik_ctx *ctx, const mik_csr *A, int64_t *singular_col, mik_stationary **out);
+int mik_stationary_destroy(mik_stationary *S);
+/* levels[2] / launches[2]: per direction ([0] forward = strict lower, [1] backward = strict upper); bytes: device memory held;
+ * analysis_ms: host time of mik_stationary_create.  Any pointer may be NULL. */
+int mik_stationary_info(const mik_stationary *S, int64_t *levels, int64_t *launches, int64_t *bytes, double *analysis_ms);
+/* ldiv!(y, D, x): y[i] = x[i] / A[i,i] -- :30-35.  y may alias x. */
+int mik_diag_ldiv(mik_stationary *S, void *y, const void *x);
+/* mul!(alpha, O::OffDiagonal, x, beta, y) -- :148-171 (beta == 0: fill!, beta == 1: untouched, else lmul!).  Host scalars of the
+ * operator's dtype; x and y must not alias. */
+int mik_offdiag_mul(mik_stationary *S, const void *alpha, const void *x, const void *beta, void *y);
+/* gauss_seidel_multiply!(alpha, U (upper = 1) | L (upper = 0), x, beta, y, z) -- :178-191 / :196-208.  z may alias x (GaussSeidelIterable
+ * does this, :284): the library then reads a copy of the old x.  Host scalars of the operator's dtype. */
+int mik_gs_multiply(mik_stationary *S, int upper, const void *alpha, const void *x, const void *beta, const void *y, void *z);
+/* forward_sub!(F, x) (y == NULL: alpha / beta ignored) -- :67-82; forward_sub!(alpha, F, x, beta, y) -- :87-103.  alpha / beta are host
+ * scalars of scalar_dtype (MIK_F64 / MIK_F32): Float32 data with MIK_F64 scalars evaluates alpha*x[i]/d + beta*y[i] in Float64 and
+ * rounds once at the store (Julia's promotion for sor!(x::Vector{Float32}, A, b, 1.2)); the subtractions stay in the data type. */
+int mik_forward_sub(mik_stationary *S, const void *alpha, void *x, const void *beta, const void *y, int scalar_dtype);
+/* backward_sub!(F, x) -- :109-124; backward_sub!(alpha, F, x, beta, y) -- :126-142.  As mik_forward_sub. */
+int mik_backward_sub(mik_stationary *S, const void *alpha, void *x, const void *beta, const void *y, int scalar_dtype);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Time `reps` back-to-back launches of the SpMV (optionally with the fused dot epilogue used by

@@ -6,6 +6,7 @@ The directory name (``iterativesolvers.jl_amd``) is not a Python identifier; loa
   csrc/      hand-written HIP kernels (gfx950) + the C ABI of include/mik.h  -> libmik.so
   _lib.py    ctypes binding of that ABI (fails loudly when the library is missing)
   api.py     host-side mirror of the reference interface (cg, cg_, gmres, gmres_, iterables ...): SURVEY section 8 rows only
+  stationary.py  jacobi / gauss_seidel / sor / ssor and their iterables (src/stationary_sparse.jl)
   extras.py  solvers outside the scope contract (IDR(s), LSQR, LSMR, QMR, power method); kept apart, unjudged
   dist.py    row-partitioned multi-GPU CG / GMRES (one process per GPU; RCCL, peer-mapped mailboxes, in-process group)
   bench_dist.py  measurement harness of bench.py --gpus N (self-test orchestration, group fall-back, the line) -- not product code
@@ -22,4 +23,7 @@ from .api import (CGIterable, CGStateVariables, ClassicalGramSchmidt, Convergenc
                   nrests, orthogonalize_and_normalize_, zerox, BiCGStabIterable, bicgstabl, bicgstabl_, bicgstabl_iterator_,
                   gemv_t_, lu_solve_, ChebyshevIterable, chebyshev, chebyshev_, chebyshev_iterable_, MINRESIterable, minres, minres_,
                   minres_iterable_, givens_algorithm, axpy_dot_, axpy2_nrm2_, gram_, LinearOperator)
+from .stationary import (GaussSeidelIterable, JacobiIterable, SingularException, SORIterable, SSORIterable,   # noqa: F401
+                         StationaryOperator, gauss_seidel, gauss_seidel_, gauss_seidel_iterable, jacobi, jacobi_,
+                         jacobi_iterable, sor, sor_, sor_iterable, ssor, ssor_, ssor_iterable)
 from . import extras                                             # noqa: F401  (beyond SURVEY section 8: IDR(s), LSQR, LSMR, QMR, powm -- unjudged, not re-exported)

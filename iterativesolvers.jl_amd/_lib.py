@@ -17,7 +17,8 @@ MIK_OK = 0
 MIK_F64, MIK_F32 = 0, 1
 MIK_MGS, MIK_CGS, MIK_DGKS = 0, 1, 2
 STATUS = {1: "invalid argument", 2: "HIP runtime error", 3: "dimension/dtype mismatch",
-          4: "out of memory", 5: "not implemented", 6: "callback failed", 7: "norm outside the safely representable range"}
+          4: "out of memory", 5: "not implemented", 6: "callback failed", 7: "norm outside the safely representable range",
+          8: "singular"}
 
 
 class MikError(RuntimeError):
@@ -196,6 +197,14 @@ SIGNATURES = {
     "mik_cg_profile": (C.c_int, [_vp, C.c_int, _f64p, _i64p]),
     "mik_cgd_profile": (C.c_int, [_vp, C.c_int, _f64p, _i64p]),
     "mik_cg_profile_kernels": (C.c_int, [_vp, _f64p, _i64p]),
+    "mik_stationary_create": (C.c_int, [_vp, _vp, _i64p, C.POINTER(_vp)]),
+    "mik_stationary_destroy": (C.c_int, [_vp]),
+    "mik_stationary_info": (C.c_int, [_vp, _i64p, _i64p, _i64p, _f64p]),
+    "mik_diag_ldiv": (C.c_int, [_vp, _vp, _vp]),
+    "mik_offdiag_mul": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "mik_gs_multiply": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "mik_forward_sub": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "mik_backward_sub": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
 }
 
 _lib = None

@@ -970,4 +970,159 @@ function IterativeSolvers.orthogonalize_and_normalize!(V::Vector{HipVector{T}}, 
     nrm[]
 end
 
+# ---- stationary methods: jacobi / gauss_seidel / sor / ssor on a HipCSR (src/stationary_sparse.jl) ------------------------------
+# DiagonalIndices + the level schedules of both triangular sweeps (mik_stationary_create); every building block one C call whose rows
+# are summed in the order of the reference's column loops, so the iterates are the reference's bits.
+mutable struct HipStationary{T}
+    handle::Ptr{Cvoid}
+    A::HipCSR{T}                     # read at creation; kept alive with the handle
+    ctx::Context
+end
+function HipStationary(A::HipCSR{T}) where {T}
+    h = Ref{Ptr{Cvoid}}(C_NULL); col = Ref{Int64}(0)
+    code = ccall((:mik_stationary_create, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64}, Ref{Ptr{Cvoid}}), A.ctx.handle, A.handle, col, h)
+    code == 8 && throw(LinearAlgebra.SingularException(Int(col[])))             # DiagonalIndices, src/stationary_sparse.jl:19
+    check(code, "mik_stationary_create", A.ctx.handle)
+    S = HipStationary{T}(h[], A, A.ctx)
+    finalizer(o -> alive(o.ctx) && ccall((:mik_stationary_destroy, libmik), Cint, (Ptr{Cvoid},), o.handle), S)
+    S
+end
+function diag_ldiv!(y::HipVector{T}, S::HipStationary{T}, x::HipVector{T}) where {T}                       # ldiv!(y, D, x)  :30-35
+    check(ccall((:mik_diag_ldiv, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), S.handle, y.ptr, x.ptr), "mik_diag_ldiv", S.ctx.handle)
+    y
+end
+function offdiag_mul!(α::T, S::HipStationary{T}, x::HipVector{T}, β::T, y::HipVector{T}) where {T}      # mul!(α, O, x, β, y)  :148-171
+    check(ccall((:mik_offdiag_mul, libmik), Cint, (Ptr{Cvoid}, Ref{T}, Ptr{Cvoid}, Ref{T}, Ptr{Cvoid}), S.handle, α, x.ptr, β, y.ptr),
+          "mik_offdiag_mul", S.ctx.handle)
+    y
+end
+# gauss_seidel_multiply!(α, U | L, x, β, y, z) -- :178-191 / :196-208; z may be x
+function gs_multiply!(upper::Bool, α::T, S::HipStationary{T}, x::HipVector{T}, β::T, y::HipVector{T}, z::HipVector{T}) where {T}
+    check(ccall((:mik_gs_multiply, libmik), Cint, (Ptr{Cvoid}, Cint, Ref{T}, Ptr{Cvoid}, Ref{T}, Ptr{Cvoid}, Ptr{Cvoid}),
+                S.handle, upper, α, x.ptr, β, y.ptr, z.ptr), "mik_gs_multiply", S.ctx.handle)
+    z
+end
+# forward_sub!(L, x) / backward_sub!(U, x) (ω === nothing), or the relaxed forms with α = ω, β = one(T) - ω in Julia's promotion:
+# Float32 data with a Float64 ω evaluate α*x/d + β*y in Float64 (scalar dtype MIK_F64)
+function triangular_sub!(upper::Bool, S::HipStationary{T}, x::HipVector{T}, ω, y) where {T}
+    if ω === nothing
+        check(upper ? ccall((:mik_backward_sub, libmik), Cint, (Ptr{Cvoid}, Ref{T}, Ptr{Cvoid}, Ref{T}, Ptr{Cvoid}, Cint), S.handle, zero(T), x.ptr, zero(T), C_NULL, dtype_code(T)) :
+                      ccall((:mik_forward_sub, libmik), Cint, (Ptr{Cvoid}, Ref{T}, Ptr{Cvoid}, Ref{T}, Ptr{Cvoid}, Cint), S.handle, zero(T), x.ptr, zero(T), C_NULL, dtype_code(T)),
+              upper ? "mik_backward_sub" : "mik_forward_sub", S.ctx.handle)
+        return x
+    end
+    R = promote_type(T, typeof(ω))
+    R <: MikFloat || throw(ArgumentError("ω of type $(typeof(ω)) on $(T) data: the device computes in Float32 / Float64"))
+    α = convert(R, ω); β = convert(R, one(T) - ω)
+    check(upper ? ccall((:mik_backward_sub, libmik), Cint, (Ptr{Cvoid}, Ref{R}, Ptr{Cvoid}, Ref{R}, Ptr{Cvoid}, Cint), S.handle, α, x.ptr, β, y.ptr, dtype_code(R)) :
+                  ccall((:mik_forward_sub, libmik), Cint, (Ptr{Cvoid}, Ref{R}, Ptr{Cvoid}, Ref{R}, Ptr{Cvoid}, Cint), S.handle, α, x.ptr, β, y.ptr, dtype_code(R)),
+          upper ? "mik_backward_sub" : "mik_forward_sub", S.ctx.handle)
+    x
+end
+"levels and launches per triangular sweep (forward, backward), device bytes, analysis milliseconds"
+function stationary_info(S::HipStationary)
+    lv = zeros(Int64, 2); la = zeros(Int64, 2); b = Ref{Int64}(0); ms = Ref{Cdouble}(0)
+    check(ccall((:mik_stationary_info, libmik), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ref{Int64}, Ref{Cdouble}), S.handle, lv, la, b, ms),
+          "mik_stationary_info", S.ctx.handle)
+    (levels = (lv[1], lv[2]), launches = (la[1], la[2]), bytes = b[], analysis_ms = ms[])
+end
+
+mutable struct HipJacobiIterable{T}                      # JacobiIterable  :213-221
+    O::HipStationary{T}
+    x::HipVector{T}
+    next::HipVector{T}
+    b::HipVector{T}
+    maxiter::Int
+end
+mutable struct HipGaussSeidelIterable{T}                 # GaussSeidelIterable  :261-269
+    S::HipStationary{T}
+    x::HipVector{T}
+    b::HipVector{T}
+    maxiter::Int
+end
+mutable struct HipSORIterable{T, numT<:Real}             # SORIterable  :308-318
+    S::HipStationary{T}
+    ω::numT
+    x::HipVector{T}
+    next::HipVector{T}
+    b::HipVector{T}
+    maxiter::Int
+end
+mutable struct HipSSORIterable{T, numT<:Real}            # SSORIterable  :366-376
+    S::HipStationary{T}
+    ω::numT
+    x::HipVector{T}
+    tmp::HipVector{T}
+    b::HipVector{T}
+    maxiter::Int
+end
+const HipStationaryIterable = Union{HipJacobiIterable, HipGaussSeidelIterable, HipSORIterable, HipSSORIterable}
+
+IterativeSolvers.jacobi_iterable(x::HipVector{T}, A::HipCSR{T}, b::HipVector{T}; maxiter::Int = 10) where {T} =
+    HipJacobiIterable{T}(HipStationary(A), x, similar(x), b, maxiter)
+IterativeSolvers.gauss_seidel_iterable(x::HipVector{T}, A::HipCSR{T}, b::HipVector{T}; maxiter::Int = 10) where {T} =
+    HipGaussSeidelIterable{T}(HipStationary(A), x, b, maxiter)
+IterativeSolvers.sor_iterable(x::HipVector{T}, A::HipCSR{T}, b::HipVector{T}, ω::Real; maxiter::Int = 10) where {T} =
+    HipSORIterable{T, typeof(ω)}(HipStationary(A), ω, x, similar(x), b, maxiter)
+IterativeSolvers.ssor_iterable(x::HipVector{T}, A::HipCSR{T}, b::HipVector{T}, ω::Real; maxiter::Int = 10) where {T} =
+    HipSSORIterable{T, typeof(ω)}(HipStationary(A), ω, x, similar(x), b, maxiter)
+
+function Base.iterate(j::HipJacobiIterable{T}, iteration::Int = 1) where {T}                              # :225-234
+    iteration > j.maxiter && return nothing
+    copyto!(j.next, j.b)
+    offdiag_mul!(-one(T), j.O, j.x, one(T), j.next)
+    diag_ldiv!(j.x, j.O, j.next)
+    nothing, iteration + 1
+end
+function Base.iterate(g::HipGaussSeidelIterable{T}, iteration::Int = 1) where {T}                         # :278-288
+    iteration > g.maxiter && return nothing
+    gs_multiply!(true, -one(T), g.S, g.x, one(T), g.b, g.x)
+    triangular_sub!(false, g.S, g.x, nothing, nothing)
+    nothing, iteration + 1
+end
+function Base.iterate(s::HipSORIterable{T}, iteration::Int = 1) where {T}                                 # :322-336
+    iteration > s.maxiter && return nothing
+    gs_multiply!(true, -one(T), s.S, s.x, one(T), s.b, s.next)                  # next = b - U * x
+    triangular_sub!(false, s.S, s.next, s.ω, s.x)                               # next = ω * inv(L) * next + (1 - ω) * x
+    s.x, s.next = s.next, s.x                                                   # switch current and next iterate
+    nothing, iteration + 1
+end
+function Base.iterate(s::HipSSORIterable{T}, iteration::Int = 1) where {T}                                # :392-418
+    iteration > s.maxiter && return nothing
+    gs_multiply!(true, -one(T), s.S, s.x, one(T), s.b, s.tmp)                   # tmp = b - U * x
+    triangular_sub!(false, s.S, s.tmp, s.ω, s.x)                                # tmp = ω * inv(L) * tmp + (1 - ω) * x
+    gs_multiply!(false, -one(T), s.S, s.tmp, one(T), s.b, s.x)                  # x = b - L * tmp
+    triangular_sub!(true, s.S, s.x, s.ω, s.tmp)                                 # x = ω * inv(U) * x + (1 - ω) * tmp
+    nothing, iteration + 1
+end
+Base.length(it::HipStationaryIterable) = it.maxiter
+
+# jacobi! / gauss_seidel! / sor! / ssor! return iterable.x (:251-255, :298-302, :356-360, :422-426): for sor! after an odd maxiter the
+# internal buffer, the caller's x then holding iterate maxiter - 1
+function IterativeSolvers.jacobi!(x::HipVector{T}, A::HipCSR{T}, b::HipVector{T}; maxiter::Int = 10) where {T}
+    iterable = IterativeSolvers.jacobi_iterable(x, A, b, maxiter = maxiter)
+    for item = iterable end
+    iterable.x
+end
+function IterativeSolvers.gauss_seidel!(x::HipVector{T}, A::HipCSR{T}, b::HipVector{T}; maxiter::Int = 10) where {T}
+    iterable = IterativeSolvers.gauss_seidel_iterable(x, A, b, maxiter = maxiter)
+    for item = iterable end
+    iterable.x
+end
+function IterativeSolvers.sor!(x::HipVector{T}, A::HipCSR{T}, b::HipVector{T}, ω::Real; maxiter::Int = 10) where {T}
+    iterable = IterativeSolvers.sor_iterable(x, A, b, ω, maxiter = maxiter)
+    for item = iterable end
+    iterable.x
+end
+function IterativeSolvers.ssor!(x::HipVector{T}, A::HipCSR{T}, b::HipVector{T}, ω::Real; maxiter::Int = 10) where {T}
+    iterable = IterativeSolvers.ssor_iterable(x, A, b, ω, maxiter = maxiter)
+    for item = iterable end
+    iterable.x
+end
+# the non-! forms start from zerox(A, b) (src/stationary.jl:19, :79, :136, :195)
+IterativeSolvers.jacobi(A::HipCSR{T}, b::HipVector{T}; kwargs...) where {T} = IterativeSolvers.jacobi!(IterativeSolvers.zerox(A, b), A, b; kwargs...)
+IterativeSolvers.gauss_seidel(A::HipCSR{T}, b::HipVector{T}; kwargs...) where {T} = IterativeSolvers.gauss_seidel!(IterativeSolvers.zerox(A, b), A, b; kwargs...)
+IterativeSolvers.sor(A::HipCSR{T}, b::HipVector{T}, ω::Real; kwargs...) where {T} = IterativeSolvers.sor!(IterativeSolvers.zerox(A, b), A, b, ω; kwargs...)
+IterativeSolvers.ssor(A::HipCSR{T}, b::HipVector{T}, ω::Real; kwargs...) where {T} = IterativeSolvers.ssor!(IterativeSolvers.zerox(A, b), A, b, ω; kwargs...)
+
 end # module
