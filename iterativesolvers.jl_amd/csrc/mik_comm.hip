@@ -895,7 +895,7 @@ int plink_fin_sum(mik_plink *pl, const void *partials, int64_t nseg, void *out_d
     return MIK_OK;
 }
 
-// Modified Gram-Schmidt over a link as the LAUNCH-LEAN chain (orthogonalize_enqueue's form for n <= 1024 segments, csrc/mik_krylov.hip): every
+// Modified Gram-Schmidt over a link as the LAUNCH-LEAN chain (gs_orthogonalize's one-GPU form for n <= 1024 segments, csrc/mik_krylov.hip): every
 // pass finalises the previous pass's reduction itself AND exchanges it (k_map_pro<..., MailSum>), k + 2 launches per Arnoldi column instead of
 // 2 k + 3.  Leaves h in hd[0, k), nrm in hd[k], 1 / nrm in hd[k + 1] (NaN / 1 outside the safe range: w unscaled, the caller recomputes).
 // Every workgroup of a pass spins on the mailbox, so ranks that SHARE a GPU must all fit on it: the caller keeps this form to <= 256 segments.

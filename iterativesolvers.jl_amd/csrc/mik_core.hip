@@ -1734,11 +1734,8 @@ template <typename T> int mik_safe_norm_slow(mik_ctx *ctx, int64_t n, const T *x
     MIK_LAUNCH_CHECK(ctx);
     T amax;
     MIK_TRY(mik_read_scalars<T>(ctx, scr, 1, &amax));
-    if (amax == T(0) || amax != amax || amax > std::numeric_limits<T>::max()) { *out = amax; return MIK_OK; }   // 0, NaN, Inf as they are
-    int e;
-    (void)std::frexp((double)amax, &e);                 // amax = f * 2^e, f in [0.5, 1)
-    e = std::max(-NrmRange<T>::EC, std::min(NrmRange<T>::EC, e));   // keep s and 1 / s normal numbers of T
-    const T sc = (T)std::ldexp(1.0, -e), sinv = (T)std::ldexp(1.0, e);
+    T sc, sinv;
+    if (!mik_nrm_scale(amax, sc, sinv)) { *out = amax; return MIK_OK; }   // 0, NaN, Inf as they are
     OpScaledSq<T> op{x, sc};
     MIK_TRY((launch_map<T>(ctx, n, op, mik_aligned16(x), (T *)ctx->partials, nullptr)));
     hipLaunchKernelGGL((k_finalize_store<T>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)ctx->partials, mik_nseg<T>(n),

@@ -3,9 +3,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -138,6 +140,19 @@ template <typename T> struct NrmRange;
 template <> struct NrmRange<double> { static constexpr double LO = 0x1p-900, HI = 0x1p+900; static constexpr int EC = 1022; };
 template <> struct NrmRange<float>  { static constexpr float LO = 0x1p-70f, HI = 0x1p+100f; static constexpr int EC = 126; };
 template <typename T> __host__ __device__ static inline bool mik_nrm_in_range(T t) { return t >= NrmRange<T>::LO && t <= NrmRange<T>::HI; }
+
+// The scale of the recomputation from amax = max |x_i|: s = 2^-e with amax = f 2^e, f in [0.5, 1), and sinv = 1 / s, so that
+// norm = sqrt(sum of (x_i s)^2) * sinv.  false: amax is the norm as it is (0, NaN, Inf).
+template <typename T> static inline bool mik_nrm_scale(T amax, T &s, T &sinv)
+{
+    if (amax == T(0) || amax != amax || amax > std::numeric_limits<T>::max()) return false;
+    int e;
+    (void)std::frexp((double)amax, &e);
+    e = std::max(-NrmRange<T>::EC, std::min(NrmRange<T>::EC, e));   // keep s and 1 / s normal numbers of T
+    s = (T)std::ldexp(1.0, -e);
+    sinv = (T)std::ldexp(1.0, e);
+    return true;
+}
 
 // Over-/underflow-safe norm of a device n-vector (amax pass, exact power-of-two scaling, the same fixed-shape
 // tree over the scaled squares); *out is a host scalar.  Uses ctx->partials and the tail of ctx->coef; synchronises.

@@ -194,30 +194,204 @@ static int multidot(mik_ctx *ctx, int64_t n, int k, const T *V, int64_t ldv, con
 // orthogonalize_and_normalize!(V[:, 1:k], w, h, method) -> nrm   -- src/orthogonalize.jl:13-79
 // Coefficient area layout (elements of T): [0, k) = h, [k] = nrm, [k+1] = 1/nrm, [k+2, 2k+2) = DGKS correction.
 
-// Workspace the chains below need in ctx->partials (allocate BEFORE a graph capture).
+// Workspace the chains below need in ctx->partials.
 template <typename T> static size_t orthogonalize_workspace(int64_t n, int k)
 {
     const int64_t nseg = mik_nseg<T>(n);
     return sizeof(T) * std::max<size_t>((size_t)std::max<int64_t>(nseg, 1) * (size_t)std::max(k, 1), 2 * 1024);
 }
 
-// Kernels only (no host synchronisation; capturable into a hipGraph): ModifiedGramSchmidt / ClassicalGramSchmidt
-// up to and including w .*= inv(nrm); leaves h in coef[0, k), nrm in coef[k].  For DGKS: the first CGS sweep and
-// the norm (the re-orthogonalisation loop needs the host, see orthogonalize_impl).
-template <typename T>
-static int orthogonalize_enqueue(mik_ctx *ctx, int64_t n, int k, const T *V, int64_t ldv, T *w, int method, const T *const *cols = nullptr)
+template <typename T> static T dgks_small_norm(const T *v, int len)
 {
-    const int64_t nseg = mik_nseg<T>(n);
-    T *hd = (T *)ctx->coef;
-    T *part = (T *)ctx->partials;
+    T s = T(0);
+    for (int j = 0; j < len; ++j) { T p = v[j] * v[j]; s = s + p; }
+    return (T)std::sqrt(s);
+}
+
+// Where the sums of the Gram-Schmidt reductions live: the one thing the three transports do differently.
+//   LOCAL     one GPU: the finalisers leave the totals in ctx->coef.
+//   CALLBACK  a row partition coupled by the host's reduce(): every total goes to the host, is summed over the ranks there in rank order and
+//             comes back as a kernel argument; a norm is sqrt of that sum, taken on the host.
+//   LINK      a row partition with a device-driven link (csrc/mik_comm.hip "mik_plink"): the finaliser adds the rank totals itself (plink_fin_sum: the
+//             additions of reduce(), the same bits), so the dependent reductions of an Arnoldi column run back to back on the stream and the host
+//             waits once per column (once per DGKS round).
+// A rank with no local rows takes part in every exchange like the others.
+template <typename T> struct GsSums {
+    enum Mode { LOCAL, CALLBACK, LINK };
+    mik_ctx *ctx;
+    const mik_partition *part;      // NULL: LOCAL
+    Mode mode;
+    int64_t n, nseg;
+    int k;
+    T *h;                           // host, k coefficients (CALLBACK: written as the reductions finish)
+    T *hd, *partials;
+    T nrm_cb = T(0);                // CALLBACK: the last norm (NaN: its sum of squares was outside the safe range)
+
+    GsSums(mik_ctx *c, const mik_partition *p, int64_t n_, int k_, T *h_)
+        : ctx(c), part(p), mode(!p ? LOCAL : p->link ? LINK : CALLBACK), n(n_), nseg(mik_nseg<T>(n_)), k(k_), h(h_), hd((T *)c->coef),
+          partials((T *)c->partials) {}
+
+    int ready()
+    {
+        if ((size_t)(2 * k + 4) * sizeof(T) > mik_ctx::COEF_SAFE_SLOT) return mik_fail(ctx, MIK_ERR_NOTIMPL, "orthogonalize: k = %d too large", k);
+        MIK_TRY(mik_ensure_partials(ctx, orthogonalize_workspace<T>(n, k)));
+        partials = (T *)ctx->partials;
+        return MIK_OK;
+    }
+    // values[0, count): this rank's partial sums -> the sums over the ranks in rank order (CALLBACK)
+    int reduce(T *values, int count) const
+    {
+        if (!part->reduce || count <= 0) return MIK_OK;
+        if (part->reduce(part->user, sizeof(T) == 8 ? MIK_F64 : MIK_F32, count, values) != 0) return mik_fail(ctx, MIK_ERR_CALLBACK, "gmres: reduce callback failed");
+        return MIK_OK;
+    }
+    // The segment sums in ctx->partials -> their total into coefficient slot `slot`.  norm: nrm into `slot` and 1 / nrm into slot + 1 (NaN and 1
+    // outside the safe range: w is then left unscaled).  CALLBACK: the total goes to the host, into h[slot] or, for a norm, into nrm_cb.
+    int finish(int slot, bool norm)
+    {
+        if (mode == LINK) return plink_fin_sum(part->link, partials, nseg, hd + slot, norm ? 1 : 0);
+        if (mode == LOCAL) return norm ? finalize_nrm_inv<T>(ctx, nseg, hd + slot) : finalize_store<T>(ctx, nseg, 1, hd + slot);
+        T v;
+        MIK_TRY(finalize_store<T>(ctx, nseg, 1, hd + slot));
+        MIK_TRY(coef_download<T>(ctx, slot, &v, 1));
+        MIK_TRY(reduce(&v, 1));
+        if (norm) nrm_cb = mik_nrm_in_range(v) ? (T)std::sqrt(v) : std::numeric_limits<T>::quiet_NaN();
+        else h[slot] = v;
+        return MIK_OK;
+    }
+    // coef[slot, slot + k): this rank's k projections -> their sums over the ranks (CALLBACK: through the host, also left in `host`)
+    int sum_vec(int slot, T *host)
+    {
+        if (mode == LINK) return plink_sum_vec(part->link, hd + slot, k);
+        if (mode == LOCAL) return MIK_OK;
+        MIK_TRY(coef_download<T>(ctx, slot, host, k));
+        MIK_TRY(reduce(host, k));
+        return coef_upload<T>(ctx, slot, host, k);
+    }
+    // the coefficient h[i] as a sweep reads it: from the device, or (CALLBACK) the host value it already has -- no upload per pass
+    Coef<T> coef(int i) const { return mode == CALLBACK ? coef_val<T>(h[i]) : coef_ptr<T>(hd + i); }
+    // The host wait: vec[0, k) from coefficient slot `slot`, and the norm (CALLBACK: both are on the host already).  LINK: every wait checks the mailbox.
+    int wait(int slot, T *vec, T *nrm)
+    {
+        if (mode == CALLBACK) { *nrm = nrm_cb; return MIK_OK; }
+        if (slot == 0) {                                                 // h and nrm are adjacent: one read
+            std::vector<T> out((size_t)k + 1);
+            MIK_TRY(coef_download<T>(ctx, 0, out.data(), k + 1));
+            for (int j = 0; j < k; ++j) vec[j] = out[(size_t)j];
+            *nrm = out[(size_t)k];
+        } else {
+            MIK_TRY(coef_download<T>(ctx, slot, vec, k));
+            MIK_TRY(coef_download<T>(ctx, k, nrm, 1));
+        }
+        return mode == LINK ? plink_check(part->link, "gmres (row-partitioned)") : MIK_OK;
+    }
+    // norm(x) when its plain sum of squares left the safe range: the recomputation of include/mik.h "Norms".  Over a partition: amax = the maximum
+    // over the ranks of the local max |x_i| (CALLBACK: through the sum callback, every rank contributing its value in its own slot of a P-vector of
+    // zeros, 0 + ... + a_q + 0 being exact; LINK: gathered through the mailboxes), the same power of two on every rank, then the sum over the ranks
+    // of the local tree sums of the scaled squares.  oracle/orc_impl.inc safe_nrm_ with a partition is this arithmetic.
+    int scaled_norm(const T *x, T *out)
+    {
+        if (mode == LOCAL) return mik_safe_norm_slow<T>(ctx, n, x, out);
+        const bool link = mode == LINK;
+        const int P = link ? plink_nranks(part->link) : part->nranks, rank = link ? plink_rank(part->link) : part->rank;
+        if (!link && (P < 1 || P > 256 || rank < 0 || rank >= P)) return mik_fail(ctx, MIK_ERR_RANGE, "gmres (row-partitioned): scaled norm needs 1 <= nranks <= 256");
+        if (link && (size_t)(P + 2) * sizeof(T) > mik_ctx::COEF_SAFE_SLOT) return mik_fail(ctx, MIK_ERR_NOTIMPL, "gmres (row-partitioned): scaled norm with %d ranks", P);
+        T *scr = (T *)((unsigned char *)ctx->coef + mik_ctx::COEF_SAFE_SLOT);   // LINK: P scalars (P <= 64: the mailbox's limit)
+        const int grid = (int)std::min<int64_t>((std::max<int64_t>(n, 1) + MIK_BLOCK - 1) / MIK_BLOCK, 1024);
+        MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * (size_t)std::max<int64_t>(std::max<int64_t>(nseg, grid), 1)));
+        partials = (T *)ctx->partials;
+        hipLaunchKernelGGL((k_amax<T>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, x, partials);
+        MIK_LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL((k_amax<T>), dim3(1), dim3(MIK_BLOCK), 0, ctx->stream, (int64_t)grid, (const T *)partials, scr + (link ? rank : 0));
+        MIK_LAUNCH_CHECK(ctx);
+        std::vector<T> v((size_t)P, T(0));
+        if (link) MIK_TRY(plink_gather(part->link, scr));
+        MIK_HIP(ctx, hipMemcpyAsync(link ? v.data() : &v[(size_t)rank], scr, sizeof(T) * (link ? (size_t)P : 1), hipMemcpyDeviceToHost, ctx->stream));
+        MIK_HIP(ctx, mik_wait(ctx));
+        MIK_TRY(link ? plink_check(part->link, "gmres (row-partitioned)") : reduce(v.data(), P));
+        T amax = T(0), sc, sinv;
+        for (T a : v) amax = (a > amax || a != a) ? a : amax;
+        if (!mik_nrm_scale(amax, sc, sinv)) { *out = amax; return MIK_OK; }
+        OpScaledSq<T> op{x, sc};
+        MIK_TRY((launch_map<T>(ctx, n, op, mik_aligned16(x), partials, nullptr)));
+        MIK_TRY(link ? plink_fin_sum(part->link, partials, nseg, scr, 0) : finalize_store<T>(ctx, nseg, 1, scr));
+        T t2;
+        MIK_HIP(ctx, hipMemcpyAsync(&t2, scr, sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        MIK_HIP(ctx, mik_wait(ctx));
+        MIK_TRY(link ? plink_check(part->link, "gmres (row-partitioned)") : reduce(&t2, 1));
+        *out = (T)std::sqrt(t2) * sinv;
+        return MIK_OK;
+    }
+    // w .*= inv(nrm) once the host has the closing norm.  `scaled`: the kernels have done it already -- unless the norm came back NaN (its sum of
+    // squares was outside the safe range and they multiplied by 1): then the scaled norm first.
+    int rescale(T *w, T *nrm, bool scaled)
+    {
+        if (*nrm != *nrm) { MIK_TRY(scaled_norm(w, nrm)); scaled = false; }
+        if (scaled) return MIK_OK;
+        OpScal<T> sc{w, coef_val<T>(T(1) / *nrm)};                           // (the same IEEE quotient the device forms)
+        return launch_map<T>(ctx, n, sc, mik_aligned16(w), (T *)nullptr, nullptr);
+    }
+    // after finish(k, true): w .*= inv(nrm) on the device (CALLBACK: on the host's norm), the host wait for h and nrm
+    int close(T *w, T *nrm)
+    {
+        if (mode != CALLBACK) {
+            OpScal<T> sc{w, coef_ptr<T>(hd + k + 1)};
+            MIK_TRY((launch_map<T>(ctx, n, sc, mik_aligned16(w), (T *)nullptr, nullptr)));
+        }
+        MIK_TRY(wait(0, h, nrm));
+        return rescale(w, nrm, mode != CALLBACK);
+    }
+};
+
+// h = V' w summed over the ranks into coefficient slot `slot` (CALLBACK: also into `host`), then w -= V h   -- src/orthogonalize.jl:15-17, :27, :30
+template <typename T> static int gs_project(GsSums<T> &S, const T *V, int64_t ldv, T *w, int slot, T *host)
+{
+    if (S.k == 0) return MIK_OK;
+    MIK_TRY(multidot<T>(S.ctx, S.n, S.k, V, ldv, w, S.hd + slot));
+    MIK_TRY(S.sum_vec(slot, host));
+    return gemv_n_dev<T>(S.ctx, S.n, S.k, V, ldv, S.hd + slot, T(-1), w);
+}
+
+// The DGKS loop of src/orthogonalize.jl:26-36 from a given state {w unscaled, h in S.h, nrm, projection size}, then the normalisation: every round
+// is a batched dot summed over the ranks, the update, the norm and one host wait.  Entered by the chain below and by the single launch's hand-back.
+template <typename T> static int gs_dgks(GsSums<T> &S, const T *V, int64_t ldv, T *w, T *nrm, T projection_size)
+{
+    MIK_TRY(S.ready());
+    const int k = S.k;
+    OpDot<T> dn{w, w};
+    std::vector<T> corr((size_t)std::max(k, 1));
+    const T eta = T(1) / std::sqrt(T(2));                                // :20
+    while (*nrm < eta * projection_size) {                               // :26
+        MIK_TRY(gs_project<T>(S, V, ldv, w, k + 2, corr.data()));        // :27, :30
+        MIK_TRY((launch_map<T>(S.ctx, S.n, dn, mik_aligned16(w), S.partials, nullptr)));
+        MIK_TRY(S.finish(k, true));                                      // :32
+        MIK_TRY(S.wait(k + 2, corr.data(), nrm));
+        if (*nrm != *nrm) MIK_TRY(S.scaled_norm(w, nrm));
+        projection_size = dgks_small_norm<T>(corr.data(), k);            // :28
+        for (int j = 0; j < k; ++j) S.h[j] = S.h[j] + corr[(size_t)j];   // :31
+    }
+    return S.rescale(w, nrm, false);                                     // :36
+}
+
+// orthogonalize_and_normalize! as a chain of launches: h into S.h (host), nrm, w normalised.  `cols` (ModifiedGramSchmidt on one GPU only): V is
+// a vector of k separate device vectors -- the method of src/orthogonalize.jl:53-65.
+template <typename T>
+static int gs_orthogonalize(GsSums<T> S, const T *V, int64_t ldv, T *w, T *nrm, int method, const T *const *cols = nullptr)
+{
+    MIK_TRY(S.ready());
+    mik_ctx *ctx = S.ctx;
+    const int64_t n = S.n, nseg = S.nseg;
+    const int k = S.k;
+    T *hd = S.hd, *part = S.partials;
     const bool vecw = mik_aligned16(w);
     bool vec = vecw && (cols || (mik_aligned16(V) && (ldv % VT<T>::W == 0)));
-    // `cols` (ModifiedGramSchmidt only): V is a vector of k separate device vectors -- the method of src/orthogonalize.jl:53-65
     auto col = [&](int i) -> const T * { return cols ? cols[i] : V + (int64_t)i * ldv; };
     if (cols) for (int i = 0; i < k; ++i) vec = vec && mik_aligned16(cols[i]);
+    const int hints = mik_mgs_pass_hints(ctx, n, sizeof(T));
     OpDot<T> dn{w, w};
 
-    if (method == MIK_MGS && nseg <= 1024 && ctx->tuning[MIK_KNOB_GS] != 1) {
+    const bool lean = method == MIK_MGS && ctx->tuning[MIK_KNOB_GS] != 1;
+    if (lean && S.mode == S.LOCAL && nseg <= 1024) {
         // src/orthogonalize.jl:69-76, launch-lean form for n up to ~1M: every pass finalises the
         // previous pass's reduction itself (k_map_pro), so the chain is k + 2 launches instead of
         // 2k + 3.  Segment sums ping-pong between two buffers (a pass reads one while writing the other).
@@ -236,7 +410,16 @@ static int orthogonalize_enqueue(mik_ctx *ctx, int64_t n, int k, const T *V, int
             MIK_TRY((launch_map<T>(ctx, n, dn, vecw, P[0], nullptr)));
         }
         OpScal<T> sc{w, coef_val<T>(T(0))};                                // w .*= inv(norm(w))  :75-76
-        return launch_map_pro<T, 2>(ctx, n, sc, vecw, (T *)nullptr, P[k & 1], m, hd + k);
+        MIK_TRY((launch_map_pro<T, 2>(ctx, n, sc, vecw, (T *)nullptr, P[k & 1], m, hd + k)));
+        MIK_TRY(S.wait(0, S.h, nrm));
+        return S.rescale(w, nrm, true);
+    }
+    if (lean && S.mode == S.LINK && nseg <= mik_resident_cap(ctx)) {
+        // the same over the link: every pass finalises AND exchanges the previous reduction itself (csrc/mik_comm.hip plink_mgs_lean).
+        // At most one segment per compute unit (256 on an unpartitioned MI355X): every workgroup of a pass spins on the mailbox, and ranks that share a GPU must all be resident on it.
+        MIK_TRY(plink_mgs_lean(S.part->link, n, k, V, ldv, w, hd, part, vec, vecw, hints));
+        MIK_TRY(S.wait(0, S.h, nrm));
+        return S.rescale(w, nrm, true);
     }
     if (method == MIK_MGS) {
         // src/orthogonalize.jl:69-76.  Pass i subtracts h[i] * V[:, i] from w and, in the same sweep,
@@ -244,106 +427,27 @@ static int orthogonalize_enqueue(mik_ctx *ctx, int64_t n, int k, const T *V, int
         if (k > 0) {
             OpDot<T> d0{col(0), w};
             MIK_TRY((launch_map<T>(ctx, n, d0, vec, part, nullptr)));
-            MIK_TRY(finalize_store<T>(ctx, nseg, 1, hd));
+            MIK_TRY(S.finish(0, false));
             for (int i = 0; i + 1 < k; ++i) {
-                OpMgsPass<T, false> op{w, col(i), col(i + 1), coef_ptr<T>(hd + i), mik_mgs_pass_hints(ctx, n, sizeof(T))};
+                OpMgsPass<T, false> op{w, col(i), col(i + 1), S.coef(i), hints};
                 MIK_TRY((launch_map<T>(ctx, n, op, vec, part, nullptr)));
-                MIK_TRY(finalize_store<T>(ctx, nseg, 1, hd + i + 1));
+                MIK_TRY(S.finish(i + 1, false));
             }
-            OpMgsPass<T, true> last{w, col(k - 1), nullptr, coef_ptr<T>(hd + k - 1), mik_mgs_pass_hints(ctx, n, sizeof(T))};
+            OpMgsPass<T, true> last{w, col(k - 1), nullptr, S.coef(k - 1), hints};
             MIK_TRY((launch_map<T>(ctx, n, last, vec, part, nullptr)));
         } else {
             MIK_TRY((launch_map<T>(ctx, n, dn, vecw, part, nullptr)));
         }
-        MIK_TRY(finalize_nrm_inv<T>(ctx, nseg, hd + k));
     } else {
         // src/orthogonalize.jl:15-17 / :43-45: h = V' w (batched dot), w -= V h (axpy sweep), norm
-        MIK_TRY(multidot<T>(ctx, n, k, V, ldv, w, hd));
-        MIK_TRY(gemv_n_dev<T>(ctx, n, k, V, ldv, hd, T(-1), w));
+        MIK_TRY(gs_project<T>(S, V, ldv, w, 0, S.h));
         MIK_TRY((launch_map<T>(ctx, n, dn, vecw, part, nullptr)));
-        MIK_TRY(finalize_nrm_inv<T>(ctx, nseg, hd + k));
-        if (method == MIK_DGKS) return MIK_OK;                           // normalisation after the host loop
     }
-    OpScal<T> sc{w, coef_ptr<T>(hd + k + 1)};                           // w .*= inv(nrm)  :76 / :48
-    return launch_map<T>(ctx, n, sc, vecw, (T *)nullptr, nullptr);
-}
-
-// The closing norm of a Gram-Schmidt chain came back as NaN: its sum of squares was outside the safe range and the
-// kernels left w unscaled (k_finalize_nrm_inv / k_map_pro<2> multiply by 1).  Scaled norm, then w .*= inv(nrm).
-template <typename T> static int orth_rescale(mik_ctx *ctx, int64_t n, T *w, T *nrm_host)
-{
-    T nrm;
-    MIK_TRY(mik_safe_norm_slow<T>(ctx, n, w, &nrm));
-    OpScal<T> sc{w, coef_val<T>(T(1) / nrm)};
-    MIK_TRY((launch_map<T>(ctx, n, sc, mik_aligned16(w), (T *)nullptr, nullptr)));
-    *nrm_host = nrm;
-    return MIK_OK;
-}
-
-// The DGKS loop of src/orthogonalize.jl:26-36 from a given state {w (unscaled), hh, nrm, projection size}, then the
-// normalisation; multi-launch chain + host control.  Shared by orthogonalize_impl and the single-launch kernel's hand-back.
-template <typename T> static T dgks_small_norm(const T *v, int len)
-{
-    T s = T(0);
-    for (int j = 0; j < len; ++j) { T p = v[j] * v[j]; s = s + p; }
-    return (T)std::sqrt(s);
-}
-
-template <typename T>
-static int dgks_host_loop(mik_ctx *ctx, int64_t n, int k, const T *V, int64_t ldv, T *w, T *hh, T *nrm_io, T projection_size)
-{
-    const int64_t nseg = mik_nseg<T>(n);
-    MIK_TRY(mik_ensure_partials(ctx, orthogonalize_workspace<T>(n, k)));
-    T *hd = (T *)ctx->coef;
-    const bool vecw = mik_aligned16(w);
-    OpDot<T> dn{w, w};
-    std::vector<T> corr(std::max(k, 1));
-    T nrm = *nrm_io;
-    const T eta = T(1) / std::sqrt(T(2));                               // :20
-    while (nrm < eta * projection_size) {                                // :26
-        T *cd = hd + k + 2;
-        MIK_TRY(multidot<T>(ctx, n, k, V, ldv, w, cd));                  // :27
-        MIK_TRY(gemv_n_dev<T>(ctx, n, k, V, ldv, cd, T(-1), w));         // :30
-        MIK_TRY((launch_map<T>(ctx, n, dn, vecw, (T *)ctx->partials, nullptr)));
-        MIK_TRY(finalize_nrm_inv<T>(ctx, nseg, hd + k));                // :32
-        MIK_TRY(coef_download<T>(ctx, k + 2, corr.data(), k));
-        T nn[2];
-        MIK_TRY(coef_download<T>(ctx, k, nn, 2));
-        projection_size = dgks_small_norm<T>(corr.data(), k);           // :28
-        for (int j = 0; j < k; ++j) hh[j] = hh[j] + corr[j];            // :31
-        nrm = nn[0];
-        if (nrm != nrm) MIK_TRY(mik_safe_norm_slow<T>(ctx, n, w, &nrm));
-    }
-    OpScal<T> sc{w, coef_val<T>(T(1) / nrm)};                           // :36 (same IEEE quotient the device forms)
-    MIK_TRY((launch_map<T>(ctx, n, sc, vecw, (T *)nullptr, nullptr)));
-    *nrm_io = nrm;
-    return MIK_OK;
-}
-
-template <typename T>
-static int orthogonalize_impl(mik_ctx *ctx, int64_t n, int k, const T *V, int64_t ldv, T *w, T *h_host, T *nrm_host, int method,
-                              const T *const *cols = nullptr)
-{
-    if ((size_t)(2 * k + 4) * sizeof(T) > mik_ctx::COEF_SAFE_SLOT) return mik_fail(ctx, MIK_ERR_NOTIMPL, "orthogonalize: k = %d too large", k);
-    MIK_TRY(mik_ensure_partials(ctx, orthogonalize_workspace<T>(n, k)));
-    MIK_TRY(orthogonalize_enqueue<T>(ctx, n, k, V, ldv, w, method, cols));
-    if (method == MIK_DGKS) {                                            // src/orthogonalize.jl:20-36
-        std::vector<T> hh(k + 2);
-        MIK_TRY(coef_download<T>(ctx, 0, hh.data(), k + 2));
-        T nrm = hh[k];
-        if (nrm != nrm) MIK_TRY(mik_safe_norm_slow<T>(ctx, n, w, &nrm));   // sum of squares outside the safe range (k_finalize_nrm_inv)
-        T projection_size = dgks_small_norm<T>(hh.data(), k);          // :22
-        MIK_TRY(dgks_host_loop<T>(ctx, n, k, V, ldv, w, hh.data(), &nrm, projection_size));
-        for (int j = 0; j < k; ++j) h_host[j] = hh[j];
-        *nrm_host = nrm;
-        return MIK_OK;
-    }
-    std::vector<T> out(k + 1);
-    MIK_TRY(coef_download<T>(ctx, 0, out.data(), k + 1));
-    for (int j = 0; j < k; ++j) h_host[j] = out[j];
-    *nrm_host = out[k];
-    if (out[k] != out[k]) MIK_TRY(orth_rescale<T>(ctx, n, w, nrm_host));
-    return MIK_OK;
+    MIK_TRY(S.finish(k, true));
+    if (method != MIK_DGKS) return S.close(w, nrm);                     // w .*= inv(nrm)  :76 / :48
+    MIK_TRY(S.wait(0, S.h, nrm));                                        // DGKS, src/orthogonalize.jl:19-36: the loop condition lives on the host
+    if (*nrm != *nrm) MIK_TRY(S.scaled_norm(w, nrm));
+    return gs_dgks<T>(S, V, ldv, w, nrm, dgks_small_norm<T>(S.h, k));   // :22
 }
 
 extern "C" int mik_orthogonalize(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv, void *w, void *h,
@@ -351,8 +455,8 @@ extern "C" int mik_orthogonalize(mik_ctx *ctx, int dtype, int64_t n, int k, cons
 {
     if (!ctx || n < 0 || k < 0 || !nrm || (k && (!h || !V)) || (n && !w) || (k && ldv < n)) return MIK_ERR_INVALID;
     if (method != MIK_MGS && method != MIK_CGS && method != MIK_DGKS) return MIK_ERR_INVALID;
-    if (dtype == MIK_F64) return orthogonalize_impl<double>(ctx, n, k, (const double *)V, ldv, (double *)w, (double *)h, (double *)nrm, method);
-    if (dtype == MIK_F32) return orthogonalize_impl<float>(ctx, n, k, (const float *)V, ldv, (float *)w, (float *)h, (float *)nrm, method);
+    if (dtype == MIK_F64) return gs_orthogonalize<double>(GsSums<double>(ctx, nullptr, n, k, (double *)h), (const double *)V, ldv, (double *)w, (double *)nrm, method);
+    if (dtype == MIK_F32) return gs_orthogonalize<float>(GsSums<float>(ctx, nullptr, n, k, (float *)h), (const float *)V, ldv, (float *)w, (float *)nrm, method);
     return MIK_ERR_INVALID;
 }
 
@@ -360,8 +464,8 @@ extern "C" int mik_orthogonalize_vectors(mik_ctx *ctx, int dtype, int64_t n, int
 {
     if (!ctx || n < 0 || k < 0 || !nrm || (k && (!h || !V)) || (n && !w)) return MIK_ERR_INVALID;
     for (int i = 0; i < k; ++i) if (!V[i] && n) return MIK_ERR_INVALID;
-    if (dtype == MIK_F64) return orthogonalize_impl<double>(ctx, n, k, nullptr, 0, (double *)w, (double *)h, (double *)nrm, MIK_MGS, (const double *const *)V);
-    if (dtype == MIK_F32) return orthogonalize_impl<float>(ctx, n, k, nullptr, 0, (float *)w, (float *)h, (float *)nrm, MIK_MGS, (const float *const *)V);
+    if (dtype == MIK_F64) return gs_orthogonalize<double>(GsSums<double>(ctx, nullptr, n, k, (double *)h), nullptr, 0, (double *)w, (double *)nrm, MIK_MGS, (const double *const *)V);
+    if (dtype == MIK_F32) return gs_orthogonalize<float>(GsSums<float>(ctx, nullptr, n, k, (float *)h), nullptr, 0, (float *)w, (float *)nrm, MIK_MGS, (const float *const *)V);
     return MIK_ERR_INVALID;
 }
 
@@ -1147,317 +1251,8 @@ template <typename T> static int gm_spmv(mik_gmres *g, const T *src, T *dst)
     return mik_spmv_launch<T>(ctx, g->A, ext, dst, false, nullptr, nullptr);
 }
 
-// values[0..count): this rank's partial sums -> sums over ranks in rank order (identity without a partition)
-template <typename T> static int gm_reduce(mik_gmres *g, T *values, int count)
-{
-    if (!g->dist || !g->part.reduce || count <= 0) return MIK_OK;
-    if (g->part.reduce(g->part.user, g->dtype, count, values) != 0) return mik_fail(g->ctx, MIK_ERR_CALLBACK, "gmres: reduce callback failed");
-    return MIK_OK;
-}
-
-// Row-partitioned norm(x) from ss = the rank-ordered sum of the local sums of squares (identical on every rank, so every rank
-// takes the same branch): sqrt(ss) inside the safe range; outside (0 included: every square may have underflowed), the over-/underflow-safe
-// recomputation of include/mik.h "Norms" across the ranks -- amax = max over the ranks of the local max |x_i|, obtained through
-// the SUM callback by letting every rank contribute its value in its own slot of a P-vector of zeros (0 + ... + a_q + 0 is
-// exact); s = 2^-exponent(amax), the same power of two everywhere; t' = the rank-ordered sum of the local tree sums of
-// (x_i s)^2; norm = sqrt(t') / s.  oracle/orc_impl.inc safe_nrm_ with a partition is this arithmetic.
-template <typename T> static int gm_part_norm(mik_gmres *g, const T *x, T ss, T *nrm)
-{
-    if (mik_nrm_in_range(ss)) { *nrm = std::sqrt(ss); return MIK_OK; }       // (an exact 0 may be an underflow: it takes the scaled pass too)
-    mik_ctx *ctx = g->ctx;
-    const int64_t n = g->n, nseg = mik_nseg<T>(n);
-    const int P = g->part.nranks, rank = g->part.rank;
-    if (P < 1 || P > 256 || rank < 0 || rank >= P) return mik_fail(ctx, MIK_ERR_RANGE, "gmres (row-partitioned): scaled norm needs 1 <= nranks <= 256");
-    T *scr = (T *)((unsigned char *)ctx->coef + mik_ctx::COEF_SAFE_SLOT);
-    const int grid = (int)std::min<int64_t>((std::max<int64_t>(n, 1) + MIK_BLOCK - 1) / MIK_BLOCK, 1024);
-    MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * (size_t)std::max<int64_t>(std::max<int64_t>(nseg, grid), 1)));
-    hipLaunchKernelGGL((k_amax<T>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, x, (T *)ctx->partials);
-    MIK_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL((k_amax<T>), dim3(1), dim3(MIK_BLOCK), 0, ctx->stream, (int64_t)grid, (const T *)ctx->partials, scr);
-    MIK_LAUNCH_CHECK(ctx);
-    std::vector<T> v((size_t)P, T(0));
-    MIK_HIP(ctx, hipMemcpyAsync(&v[(size_t)rank], scr, sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-    MIK_HIP(ctx, mik_wait(ctx));
-    MIK_TRY(gm_reduce<T>(g, v.data(), P));
-    T amax = T(0);
-    for (T a : v) amax = (a > amax || a != a) ? a : amax;
-    if (amax == T(0) || amax != amax || amax > std::numeric_limits<T>::max()) { *nrm = amax; return MIK_OK; }
-    int e;
-    (void)std::frexp((double)amax, &e);
-    e = std::max(-NrmRange<T>::EC, std::min(NrmRange<T>::EC, e));
-    const T sc = (T)std::ldexp(1.0, -e), sinv = (T)std::ldexp(1.0, e);
-    OpScaledSq<T> op{x, sc};
-    MIK_TRY((launch_map<T>(ctx, n, op, mik_aligned16(x), (T *)ctx->partials, nullptr)));
-    hipLaunchKernelGGL((k_finalize_store<T>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)ctx->partials, nseg, (int64_t)0, scr, (const int *)nullptr);
-    MIK_LAUNCH_CHECK(ctx);
-    T t2;
-    MIK_HIP(ctx, hipMemcpyAsync(&t2, scr, sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-    MIK_HIP(ctx, mik_wait(ctx));
-    MIK_TRY(gm_reduce<T>(g, &t2, 1));
-    *nrm = (T)std::sqrt(t2) * sinv;
-    return MIK_OK;
-}
-
-// orthogonalize_and_normalize! over a row partition (src/orthogonalize.jl:13-79): the same sweeps as
-// orthogonalize_impl on the local rows; every projection / norm^2 is finalised to a host scalar, summed
-// over the ranks by the caller's reduce() and fed back as a kernel argument.
-template <typename T>
-static int orthogonalize_part(mik_gmres *g, int k, const T *V, int64_t ldv, T *w, T *h, T *nrm_out, int method)
-{
-    mik_ctx *ctx = g->ctx;
-    const int64_t n = g->n;
-    if ((size_t)(2 * k + 4) * sizeof(T) > mik_ctx::COEF_SAFE_SLOT) return mik_fail(ctx, MIK_ERR_NOTIMPL, "orthogonalize: k = %d too large", k);
-    const int64_t nseg = mik_nseg<T>(n);
-    MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * (size_t)std::max<int64_t>(nseg, 1) * (size_t)std::max(k, 1)));
-    T *hd = (T *)ctx->coef;
-    T *part = (T *)ctx->partials;
-    const bool vecw = mik_aligned16(w);
-    const bool vec = vecw && mik_aligned16(V) && (ldv % VT<T>::W == 0);
-    auto fetch = [&](int slot, T *dst) -> int {     // level 2 of the local tree -> host -> sum over ranks
-        MIK_TRY(finalize_store<T>(ctx, nseg, 1, hd + slot));
-        MIK_TRY(coef_download<T>(ctx, slot, dst, 1));
-        return gm_reduce<T>(g, dst, 1);
-    };
-    OpDot<T> dn{w, w};
-    T ss = T(0);
-    if (method == MIK_MGS) {                                             // :69-76
-        if (k > 0) {
-            OpDot<T> d0{V, w};
-            MIK_TRY((launch_map<T>(ctx, n, d0, vec, part, nullptr)));
-            MIK_TRY(fetch(0, &h[0]));
-            for (int i = 0; i + 1 < k; ++i) {
-                OpMgsPass<T, false> op{w, V + (int64_t)i * ldv, V + (int64_t)(i + 1) * ldv, coef_val<T>(h[i])};
-                MIK_TRY((launch_map<T>(ctx, n, op, vec, part, nullptr)));
-                MIK_TRY(fetch(0, &h[i + 1]));
-            }
-            OpMgsPass<T, true> last{w, V + (int64_t)(k - 1) * ldv, nullptr, coef_val<T>(h[k - 1])};
-            MIK_TRY((launch_map<T>(ctx, n, last, vec, part, nullptr)));
-        } else {
-            MIK_TRY((launch_map<T>(ctx, n, dn, vecw, part, nullptr)));
-        }
-        MIK_TRY(fetch(0, &ss));
-    } else {                                                             // :15-17 / :43-45
-        auto project = [&](int slot, T *coef) -> int {   // coef = V' w over all ranks; w -= V coef
-            if (k == 0) return MIK_OK;
-            MIK_TRY(multidot<T>(ctx, n, k, V, ldv, w, hd + slot));
-            MIK_TRY(coef_download<T>(ctx, slot, coef, k));
-            MIK_TRY(gm_reduce<T>(g, coef, k));
-            MIK_TRY(coef_upload<T>(ctx, slot, coef, k));
-            return gemv_n_dev<T>(ctx, n, k, V, ldv, hd + slot, T(-1), w);
-        };
-        MIK_TRY(project(0, h));
-        MIK_TRY((launch_map<T>(ctx, n, dn, vecw, part, nullptr)));
-        MIK_TRY(fetch(k, &ss));
-        if (method == MIK_DGKS) {
-            std::vector<T> corr((size_t)std::max(k, 1));
-            auto small_norm = [](const T *v, int len) { T s = T(0); for (int j = 0; j < len; ++j) { T p = v[j] * v[j]; s = s + p; } return (T)std::sqrt(s); };
-            const T eta = T(1) / std::sqrt(T(2));                        // :20
-            T nrm;
-            MIK_TRY(gm_part_norm<T>(g, w, ss, &nrm));
-            T projection_size = small_norm(h, k);                        // :22
-            while (nrm < eta * projection_size) {                        // :26
-                MIK_TRY(project(k + 2, corr.data()));                    // :27, :30
-                MIK_TRY((launch_map<T>(ctx, n, dn, vecw, part, nullptr)));
-                MIK_TRY(fetch(k, &ss));                                  // :32
-                MIK_TRY(gm_part_norm<T>(g, w, ss, &nrm));
-                projection_size = small_norm(corr.data(), k);            // :28
-                for (int j = 0; j < k; ++j) h[j] = h[j] + corr[j];       // :31
-            }
-        }
-    }
-    T nrm;
-    MIK_TRY(gm_part_norm<T>(g, w, ss, &nrm));
-    const T inv = T(1) / nrm;
-    OpScal<T> sc{w, coef_val<T>(inv)};                                   // w .*= inv(nrm)  :76 / :48 / :36
-    MIK_TRY((launch_map<T>(ctx, n, sc, vecw, (T *)nullptr, nullptr)));
-    *nrm_out = nrm;
-    return MIK_OK;
-}
-
-
-// ---- the same over a DEVICE-DRIVEN link (mik_partition.link; csrc/mik_comm.hip "mik_plink") -------------------------------------------
-// Every reduction is finalised AND summed over the ranks by one kernel (plink_fin_sum: level 2 of the local tree, the rank totals through the
-// peer-mapped mailboxes, added in rank order -- the additions of gm_reduce's callback, the same bits); the sweeps take their coefficients from
-// device memory, so the k + 1 dependent reductions of an Arnoldi column run back to back on the stream and the host waits ONCE per inner
-// iteration, for the column of H (src/orthogonalize.jl:69-76).
-
-// norm(x) over the partition when the plain sum of squares left the safe range (the kernels flagged it with NaN): gm_part_norm's scaled
-// recomputation with the exchanges on the device
-template <typename T> static int gm_link_norm_slow(mik_gmres *g, const T *x, T *nrm)
-{
-    mik_ctx *ctx = g->ctx;
-    mik_plink *pl = g->part.link;
-    const int64_t n = g->n, nseg = mik_nseg<T>(n);
-    const int P = plink_nranks(pl), rank = plink_rank(pl);
-    T *scr = (T *)((unsigned char *)ctx->coef + mik_ctx::COEF_SAFE_SLOT);          // P scalars (P <= 64: the mailbox's limit)
-    if ((size_t)(P + 2) * sizeof(T) > mik_ctx::COEF_SAFE_SLOT) return mik_fail(ctx, MIK_ERR_NOTIMPL, "gmres (row-partitioned): scaled norm with %d ranks", P);
-    const int grid = (int)std::min<int64_t>((std::max<int64_t>(n, 1) + MIK_BLOCK - 1) / MIK_BLOCK, 1024);
-    MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * (size_t)std::max<int64_t>(std::max<int64_t>(nseg, grid), 1)));
-    hipLaunchKernelGGL((k_amax<T>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, x, (T *)ctx->partials);
-    MIK_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL((k_amax<T>), dim3(1), dim3(MIK_BLOCK), 0, ctx->stream, (int64_t)grid, (const T *)ctx->partials, scr + rank);
-    MIK_LAUNCH_CHECK(ctx);
-    MIK_TRY(plink_gather(pl, scr));
-    std::vector<T> v((size_t)P, T(0));
-    MIK_HIP(ctx, hipMemcpyAsync(v.data(), scr, sizeof(T) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
-    MIK_HIP(ctx, mik_wait(ctx));
-    MIK_TRY(plink_check(pl, "gmres (row-partitioned)"));
-    T amax = T(0);
-    for (T a : v) amax = (a > amax || a != a) ? a : amax;
-    if (amax == T(0) || amax != amax || amax > std::numeric_limits<T>::max()) { *nrm = amax; return MIK_OK; }
-    int e;
-    (void)std::frexp((double)amax, &e);
-    e = std::max(-NrmRange<T>::EC, std::min(NrmRange<T>::EC, e));
-    const T sc = (T)std::ldexp(1.0, -e), sinv = (T)std::ldexp(1.0, e);
-    OpScaledSq<T> op{x, sc};
-    MIK_TRY((launch_map<T>(ctx, n, op, mik_aligned16(x), (T *)ctx->partials, nullptr)));
-    MIK_TRY(plink_fin_sum(pl, ctx->partials, nseg, scr, 0));
-    T t2;
-    MIK_HIP(ctx, hipMemcpyAsync(&t2, scr, sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-    MIK_HIP(ctx, mik_wait(ctx));
-    MIK_TRY(plink_check(pl, "gmres (row-partitioned)"));
-    *nrm = (T)std::sqrt(t2) * sinv;
-    return MIK_OK;
-}
-
-// The DGKS loop (src/orthogonalize.jl:26-33) over a link, from a first projection on: w unscaled on entry, scaled on exit; every round = batched dot,
-// one exchange of the k sums, the update, the norm over the ranks, ONE host wait.  Entered by the chain below and by the single launch's hand-back.
-template <typename T>
-static int dgks_link_loop(mik_gmres *g, int k, const T *V, int64_t ldv, T *w, T *h, T *nrm_io, T projection_size)
-{
-    mik_ctx *ctx = g->ctx;
-    mik_plink *pl = g->part.link;
-    const int64_t n = g->n, nseg = mik_nseg<T>(n);
-    if ((size_t)(2 * k + 4) * sizeof(T) > mik_ctx::COEF_SAFE_SLOT) return mik_fail(ctx, MIK_ERR_NOTIMPL, "orthogonalize: k = %d too large", k);
-    MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * (size_t)std::max<int64_t>(nseg, 1) * (size_t)std::max(k, 1)));
-    T *hd = (T *)ctx->coef, *part = (T *)ctx->partials;          // [k] nrm, [k + 1] 1 / nrm, [k + 2, 2k + 2) the round's correction
-    const bool vecw = mik_aligned16(w);
-    OpDot<T> dn{w, w};
-    std::vector<T> corr((size_t)std::max(k, 1));
-    const T eta = T(1) / std::sqrt(T(2));                                // :20
-    T nrm = *nrm_io;
-    while (nrm < eta * projection_size) {                                // :26
-        if (k > 0) {                                                     // :27, :30
-            MIK_TRY(multidot<T>(ctx, n, k, V, ldv, w, hd + k + 2));
-            MIK_TRY(plink_sum_vec(pl, hd + k + 2, k));
-            MIK_TRY(gemv_n_dev<T>(ctx, n, k, V, ldv, hd + k + 2, T(-1), w));
-        }
-        MIK_TRY((launch_map<T>(ctx, n, dn, vecw, part, nullptr)));       // :32
-        MIK_TRY(plink_fin_sum(pl, part, nseg, hd + k, 1));
-        MIK_TRY(coef_download<T>(ctx, k + 2, corr.data(), k));
-        MIK_TRY(coef_download<T>(ctx, k, &nrm, 1));
-        MIK_TRY(plink_check(pl, "gmres (row-partitioned)"));
-        if (nrm != nrm) MIK_TRY(gm_link_norm_slow<T>(g, w, &nrm));
-        projection_size = dgks_small_norm<T>(corr.data(), k);            // :28
-        for (int j = 0; j < k; ++j) h[j] = h[j] + corr[(size_t)j];       // :31
-    }
-    OpScal<T> sc{w, coef_val<T>(T(1) / nrm)};                            // :36
-    MIK_TRY((launch_map<T>(ctx, n, sc, vecw, (T *)nullptr, nullptr)));
-    *nrm_io = nrm;
-    return MIK_OK;
-}
-
-template <typename T>
-static int orthogonalize_link(mik_gmres *g, int k, const T *V, int64_t ldv, T *w, T *h, T *nrm_out, int method)
-{
-    mik_ctx *ctx = g->ctx;
-    mik_plink *pl = g->part.link;
-    const int64_t n = g->n;
-    if ((size_t)(2 * k + 4) * sizeof(T) > mik_ctx::COEF_SAFE_SLOT) return mik_fail(ctx, MIK_ERR_NOTIMPL, "orthogonalize: k = %d too large", k);
-    const int64_t nseg = mik_nseg<T>(n);
-    MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * (size_t)std::max<int64_t>(nseg, 1) * (size_t)std::max(k, 1)));
-    T *hd = (T *)ctx->coef;                    // [0, k) h, [k] nrm, [k + 1] 1 / nrm, [k + 2, 2k + 2) DGKS correction
-    T *part = (T *)ctx->partials;
-    const bool vecw = mik_aligned16(w);
-    const bool vec = vecw && mik_aligned16(V) && (ldv % VT<T>::W == 0);
-    OpDot<T> dn{w, w};
-    std::vector<T> out((size_t)k + 2);
-    auto download = [&](int slot, T *dst, int cnt) -> int {      // the one host wait of the column (DGKS: of the round)
-        MIK_TRY(coef_download<T>(ctx, slot, dst, cnt));
-        return plink_check(pl, "gmres (row-partitioned)");
-    };
-    T nrm;
-    if (method == MIK_MGS && nseg <= mik_resident_cap(ctx) && ctx->tuning[MIK_KNOB_GS] != 1) {
-        // the launch-lean chain: every pass finalises AND exchanges the previous reduction itself (k + 2 launches; csrc/mik_comm.hip plink_mgs_lean).
-        // At most one segment per compute unit (256 on an unpartitioned MI355X): every workgroup of a pass spins on the mailbox, and ranks that share a GPU must all be resident on it.
-        MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * 2048));
-        MIK_TRY(plink_mgs_lean(pl, n, k, V, ldv, w, hd, ctx->partials, vec, vecw, mik_mgs_pass_hints(ctx, n, sizeof(T))));
-        MIK_TRY(download(0, out.data(), k + 1));
-        for (int j = 0; j < k; ++j) h[j] = out[(size_t)j];
-        nrm = out[(size_t)k];
-        if (nrm != nrm) {                                                // w was left unscaled
-            MIK_TRY(gm_link_norm_slow<T>(g, w, &nrm));
-            OpScal<T> sc2{w, coef_val<T>(T(1) / nrm)};
-            MIK_TRY((launch_map<T>(ctx, n, sc2, vecw, (T *)nullptr, nullptr)));
-        }
-        *nrm_out = nrm;
-        return MIK_OK;
-    }
-    if (method == MIK_MGS) {                                             // :69-76
-        if (k > 0) {
-            OpDot<T> d0{V, w};
-            MIK_TRY((launch_map<T>(ctx, n, d0, vec, part, nullptr)));
-            MIK_TRY(plink_fin_sum(pl, part, nseg, hd, 0));
-            for (int i = 0; i + 1 < k; ++i) {
-                OpMgsPass<T, false> op{w, V + (int64_t)i * ldv, V + (int64_t)(i + 1) * ldv, coef_ptr<T>(hd + i), mik_mgs_pass_hints(ctx, n, sizeof(T))};
-                MIK_TRY((launch_map<T>(ctx, n, op, vec, part, nullptr)));
-                MIK_TRY(plink_fin_sum(pl, part, nseg, hd + i + 1, 0));
-            }
-            OpMgsPass<T, true> last{w, V + (int64_t)(k - 1) * ldv, nullptr, coef_ptr<T>(hd + k - 1), mik_mgs_pass_hints(ctx, n, sizeof(T))};
-            MIK_TRY((launch_map<T>(ctx, n, last, vec, part, nullptr)));
-        } else {
-            MIK_TRY((launch_map<T>(ctx, n, dn, vecw, part, nullptr)));
-        }
-        MIK_TRY(plink_fin_sum(pl, part, nseg, hd + k, 1));               // nrm, 1 / nrm (NaN, 1 outside the safe range)
-        OpScal<T> sc{w, coef_ptr<T>(hd + k + 1)};                        // w .*= inv(nrm)  :76
-        MIK_TRY((launch_map<T>(ctx, n, sc, vecw, (T *)nullptr, nullptr)));
-        MIK_TRY(download(0, out.data(), k + 1));
-        for (int j = 0; j < k; ++j) h[j] = out[(size_t)j];
-        nrm = out[(size_t)k];
-        if (nrm != nrm) {                                                // w was left unscaled
-            MIK_TRY(gm_link_norm_slow<T>(g, w, &nrm));
-            OpScal<T> sc2{w, coef_val<T>(T(1) / nrm)};
-            MIK_TRY((launch_map<T>(ctx, n, sc2, vecw, (T *)nullptr, nullptr)));
-        }
-        *nrm_out = nrm;
-        return MIK_OK;
-    }
-    // :15-17 / :43-45: h = V' w (batched dot, summed over the ranks in one exchange), w -= V h, norm
-    auto project = [&](int slot) -> int {
-        if (k == 0) return MIK_OK;
-        MIK_TRY(multidot<T>(ctx, n, k, V, ldv, w, hd + slot));
-        MIK_TRY(plink_sum_vec(pl, hd + slot, k));
-        return gemv_n_dev<T>(ctx, n, k, V, ldv, hd + slot, T(-1), w);
-    };
-    auto norm_w = [&](T *dst) -> int {           // norm(w) over the partition into hd[k] (and the host), scaled pass if flagged
-        MIK_TRY((launch_map<T>(ctx, n, dn, vecw, part, nullptr)));
-        return plink_fin_sum(pl, part, nseg, hd + k, 1);
-    };
-    MIK_TRY(project(0));
-    MIK_TRY(norm_w(&nrm));
-    if (method == MIK_CGS) {
-        OpScal<T> sc{w, coef_ptr<T>(hd + k + 1)};                        // :48
-        MIK_TRY((launch_map<T>(ctx, n, sc, vecw, (T *)nullptr, nullptr)));
-        MIK_TRY(download(0, out.data(), k + 1));
-        for (int j = 0; j < k; ++j) h[j] = out[(size_t)j];
-        nrm = out[(size_t)k];
-        if (nrm != nrm) {
-            MIK_TRY(gm_link_norm_slow<T>(g, w, &nrm));
-            OpScal<T> sc2{w, coef_val<T>(T(1) / nrm)};
-            MIK_TRY((launch_map<T>(ctx, n, sc2, vecw, (T *)nullptr, nullptr)));
-        }
-        *nrm_out = nrm;
-        return MIK_OK;
-    }
-    // DGKS (:19-36): the loop condition lives on the host, one wait per round
-    MIK_TRY(download(0, out.data(), k + 1));
-    for (int j = 0; j < k; ++j) h[j] = out[(size_t)j];
-    nrm = out[(size_t)k];
-    if (nrm != nrm) MIK_TRY(gm_link_norm_slow<T>(g, w, &nrm));
-    MIK_TRY(dgks_link_loop<T>(g, k, V, ldv, w, h, &nrm, dgks_small_norm<T>(h, k)));   // :22
-    *nrm_out = nrm;
-    return MIK_OK;
-}
+// the Gram-Schmidt sums of this iterable: one GPU, or its row partition (through the callbacks or the link)
+template <typename T> static GsSums<T> gm_sums(mik_gmres *g, int k, T *h) { return GsSums<T>(g->ctx, g->dist ? &g->part : nullptr, g->n, k, h); }
 
 template <typename T> static std::vector<T> &gm_H(mik_gmres *g);
 template <> std::vector<double> &gm_H<double>(mik_gmres *g) { return g->H64; }
@@ -1504,43 +1299,9 @@ template <typename T> static int gmres_init_residual(mik_gmres *g, int initially
         OpDot<T> dn{V0, V0};
         MIK_TRY((launch_map<T>(ctx, n, dn, mik_aligned16(V0), (T *)ctx->partials, nullptr)));
     }
-    T *hd = (T *)ctx->coef;
-    if (g->dist && g->part.link) {                                        // device-driven: norm over the ranks and 1 / norm inside the finaliser
-        MIK_TRY(plink_fin_sum(g->part.link, ctx->partials, nseg, hd, 1)); // :252
-        OpScal<T> scd{V0, coef_ptr<T>(hd + 1)};                           // :253
-        MIK_TRY((launch_map<T>(ctx, n, scd, mik_aligned16(V0), (T *)nullptr, nullptr)));
-        T out[2];
-        MIK_TRY(coef_download<T>(ctx, 0, out, 2));
-        MIK_TRY(plink_check(g->part.link, "gmres (row-partitioned)"));
-        *beta_out = out[0];
-        if (out[0] != out[0]) {                                           // badly scaled residual: scaled norm across the ranks, then :253
-            MIK_TRY(gm_link_norm_slow<T>(g, V0, beta_out));
-            OpScal<T> sc2{V0, coef_val<T>(T(1) / *beta_out)};
-            MIK_TRY((launch_map<T>(ctx, n, sc2, mik_aligned16(V0), (T *)nullptr, nullptr)));
-        }
-        return MIK_OK;
-    }
-    if (g->dist) {
-        T ss;
-        MIK_TRY(finalize_store<T>(ctx, nseg, 1, hd));
-        MIK_TRY(coef_download<T>(ctx, 0, &ss, 1));
-        MIK_TRY(gm_reduce<T>(g, &ss, 1));
-        T beta;
-        MIK_TRY(gm_part_norm<T>(g, V0, ss, &beta));                       // :252
-        const T inv = T(1) / beta;
-        OpScal<T> scd{V0, coef_val<T>(inv)};                              // :253
-        MIK_TRY((launch_map<T>(ctx, n, scd, mik_aligned16(V0), (T *)nullptr, nullptr)));
-        *beta_out = beta;
-        return MIK_OK;
-    }
-    MIK_TRY(finalize_nrm_inv<T>(ctx, nseg, hd));                          // :252
-    OpScal<T> sc{V0, coef_ptr<T>(hd + 1)};                                // :253
-    MIK_TRY((launch_map<T>(ctx, n, sc, mik_aligned16(V0), (T *)nullptr, nullptr)));
-    T out[2];
-    MIK_TRY(coef_download<T>(ctx, 0, out, 2));
-    *beta_out = out[0];
-    if (out[0] != out[0]) MIK_TRY(orth_rescale<T>(ctx, n, V0, beta_out));   // badly scaled residual: scaled norm, then :253
-    return MIK_OK;
+    GsSums<T> S = gm_sums<T>(g, 0, nullptr);
+    MIK_TRY(S.finish(0, true));                                           // :252
+    return S.close(V0, beta_out);                                         // :253 (a badly scaled residual: the scaled norm first)
 }
 
 template <typename T> static int gmres_create_impl(mik_gmres *g, double abstol, double reltol, int initially_zero)
@@ -1720,8 +1481,8 @@ template <typename T> static int gm_expand(mik_gmres *g, T *vk, T *vk1)
     return MIK_OK;
 }
 
-// orthogonalize_and_normalize! with ModifiedGramSchmidt as ONE launch (k_mgs_fused) + one poll of a host-mapped mirror:
-// n up to 256 reduction segments, where the k + 2 launches of the chain are pure dependent-launch latency.
+// orthogonalize_and_normalize! as ONE launch (k_mgs_fused / k_cgs_fused: up to 8 reduction segments per workgroup, one workgroup per compute unit;
+// k_mgs_resident beyond) + one poll of a host-mapped mirror, where the k + 2 launches of the chain are pure dependent-launch latency.
 // Split into "enqueue" (expand! + the kernel for Arnoldi column k) and "wait" (poll + read h, nrm), so that the column
 // AFTER the current one can be put on the stream before the host has seen the current result: its inputs are all on the
 // device, only "did the solve just converge?" is not known yet -- then the extra column is simply never read.
@@ -1830,27 +1591,16 @@ template <typename T> static int gm_fused_wait(mik_gmres *g, int k, int slot, T 
     for (int j = 0; j < k; ++j) h_out[j] = out[j];
     *nrm_out = out[k];
     *rescaled = false;
+    T *w = (T *)g->V + (int64_t)k * g->ldv;
+    GsSums<T> S = gm_sums<T>(g, k, h_out);      // (over a partition every rank sees the same totals: all of them take the same branch together)
     if (g->method == MIK_DGKS && mir->pad) {    // the kernel stopped before the DGKS loop ended (round limit / unsafe norm): w is unscaled
-        T *w = (T *)g->V + (int64_t)k * g->ldv;
-        T nrm = out[k];
-        if (g->dist) {                          // (every rank sees the same totals: all of them come here together)
-            if (nrm != nrm) MIK_TRY(gm_link_norm_slow<T>(g, w, &nrm));
-            MIK_TRY(dgks_link_loop<T>(g, k, (const T *)g->V, g->ldv, w, h_out, &nrm, out[k + 1]));
-        } else {
-            if (nrm != nrm) MIK_TRY(mik_safe_norm_slow<T>(ctx, g->n, w, &nrm));
-            MIK_TRY(dgks_host_loop<T>(ctx, g->n, k, (const T *)g->V, g->ldv, w, h_out, &nrm, out[k + 1]));
-        }
-        *nrm_out = nrm;
+        if (*nrm_out != *nrm_out) MIK_TRY(S.scaled_norm(w, nrm_out));
+        MIK_TRY(gs_dgks<T>(S, (const T *)g->V, g->ldv, w, nrm_out, out[k + 1]));
         *rescaled = true;
         return MIK_OK;
     }
     if (out[k] != out[k]) {                     // sum of squares outside the safe range: the kernel left w unscaled
-        T *w = (T *)g->V + (int64_t)k * g->ldv;
-        if (g->dist) {                          // ... on every rank alike (identical totals): the scaled norm across the ranks
-            MIK_TRY(gm_link_norm_slow<T>(g, w, nrm_out));
-            OpScal<T> sc{w, coef_val<T>(T(1) / *nrm_out)};
-            MIK_TRY((launch_map<T>(ctx, g->n, sc, mik_aligned16(w), (T *)nullptr, nullptr)));
-        } else MIK_TRY(orth_rescale<T>(ctx, g->n, w, nrm_out));
+        MIK_TRY(S.rescale(w, nrm_out, true));
         *rescaled = true;
     }
     return MIK_OK;
@@ -1901,16 +1651,14 @@ template <typename T> static int gmres_iterate_impl(mik_gmres *g, int64_t iterat
                 else g->fused_off = true;
                 g->pre_k = 0;
                 MIK_TRY(gm_expand<T>(g, vk, vk1));
-                MIK_TRY(orthogonalize_impl<T>(ctx, g->n, k, V, g->ldv, vk1, &Hat(0, k - 1), &nrm, g->method));
+                MIK_TRY(gs_orthogonalize<T>(gm_sums<T>(g, k, &Hat(0, k - 1)), V, g->ldv, vk1, &nrm, g->method));
             } else {
                 MIK_TRY(rcw);
                 if (ahead && !rescaled) { g->pre_k = k + 1; g->pre_slot = slot ^ 1; }    // rescaled: column k + 1 was built on an unscaled w
             }
         } else {
             MIK_TRY(gm_expand<T>(g, vk, vk1));
-            if (g->dist && g->part.link) MIK_TRY(orthogonalize_link<T>(g, k, V, g->ldv, vk1, &Hat(0, k - 1), &nrm, g->method));
-            else if (g->dist) MIK_TRY(orthogonalize_part<T>(g, k, V, g->ldv, vk1, &Hat(0, k - 1), &nrm, g->method));
-            else MIK_TRY(orthogonalize_impl<T>(ctx, g->n, k, V, g->ldv, vk1, &Hat(0, k - 1), &nrm, g->method));
+            MIK_TRY(gs_orthogonalize<T>(gm_sums<T>(g, k, &Hat(0, k - 1)), V, g->ldv, vk1, &nrm, g->method));
         }
     }
     g->mv_products += 1;                                                  // :65

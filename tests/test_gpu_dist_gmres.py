@@ -367,6 +367,28 @@ def test_device_driven_partitioned_dgks_reorthogonalises_across_the_ranks(pkg, o
     assert np.array_equal(np.concatenate([np.load(tmp_path / f"x{r}.npy") for r in range(world)]), xo)
 
 
+@pytest.mark.parametrize("P", [2, 3])
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+def test_partitioned_dgks_reorthogonalises_through_the_callbacks(pkg, orc, ctx, dist, P, dtype_name):
+    """The system of test_device_driven_partitioned_dgks_reorthogonalises_across_the_ranks on host-thread ranks: the DGKS loop
+    (src/orthogonalize.jl:26) runs with every round's projections and norm summed through the reduce callback.  Bit-exact against
+    the partition-aware oracle, which differs from its own CGS run (the loop really ran)."""
+    dtype = np.dtype(dtype_name)
+    n, S, b = _reorth_system(dtype)
+    offsets, out = run_threads(pkg, dist, S.tocsr(), b, P, restart=12, maxiter=20, reltol=0.0, orth_meth=pkg.DGKS())
+    A = orc.CSC.from_scipy(S).astype(dtype)
+    orc.set_partition(offsets)
+    try:
+        xo, ho = orc.gmres(A, b, restart=12, orth_meth="dgks", mode="tree", shape=ctx.reduce_shape(dtype), maxiter=20, reltol=0.0)
+        xc, hc = orc.gmres(A, b, restart=12, orth_meth="cgs", mode="tree", shape=ctx.reduce_shape(dtype), maxiter=20, reltol=0.0)
+    finally:
+        orc.set_partition(None)
+    assert not np.array_equal(ho["resnorm"], hc["resnorm"]) or not np.array_equal(xo, xc)
+    for o in out:
+        assert np.array_equal(o["hist"], ho["resnorm"]) and o["mvps"] == ho["mvps"] and o["conv"] == ho["isconverged"]
+    assert np.array_equal(np.concatenate([o["x"] for o in out]), xo)
+
+
 def _link_precond_worker(rank, world, port, out_dir, orth):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), MIK_MAILBOX_TIMEOUT_MS="20000")
     import torch
