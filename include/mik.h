@@ -469,7 +469,7 @@ int mik_gather(mik_ctx *ctx, int dtype, int64_t m, const int32_t *idx, const voi
 /* Rank `rank` of `nranks` owns a contiguous block of n_loc rows.  A_loc is that block as an
  * n_loc x (n_loc + n_ghost) operator: columns [0, n_loc) are the owned entries of a vector, columns
  * [n_loc, n_loc + n_ghost) the halo entries the host receives from the neighbours into the tail of
- * u_ext before phase 1 / 11.  x, b, r, c: device n_loc-vectors; u_ext: device (n_loc + n_ghost)-
+ * u_ext before STEP_B / INIT_B.  x, b, r, c: device n_loc-vectors; u_ext: device (n_loc + n_ghost)-
  * vector; send_idx / send_buf: local indices to pack and the packed buffer (n_send entries);
  * dot_all / rr_all: device arrays of nranks scalars -- every rank writes slot [rank], the host
  * all-gathers them between phases (RCCL over xGMI via torch.distributed, gloo in CPU tests).
@@ -480,16 +480,26 @@ int mik_cgd_create(mik_ctx *ctx, const mik_csr *A_loc, void *x, const void *b, v
                    void *rr_all, int rank, int nranks, double abstol, double reltol, int64_t maxiter,
                    int initially_zero, mik_cgd **out);
 int mik_cgd_destroy(mik_cgd *it);
-/* Enqueue one phase (no host synchronisation).  cg_iterator! (src/cg.jl:120-155): 10 = pack x's
- * halo, [exchange], 11 = r = b - A x and local |r|^2, [all-gather rr], 12 = residual, tolerance.
- * iterate (src/cg.jl:43-66): 0 = u = r + beta u and pack, [exchange], 1 = c = A u with local
- * dot(u, c), [all-gather dot], 2 = alpha, x += alpha u, r -= alpha c, local |r|^2, [all-gather rr],
- * 3 = residual, beta, stopping test of src/cg.jl:36 for iteration + 1 (later steps become no-ops). */
+/* The phases a host may drive itself; [..] is the exchange the host runs between two of them.
+ * cg_iterator! (src/cg.jl:120-155): INIT_A, [halo of x], INIT_B, [all-gather rr], INIT_C.
+ * iterate (src/cg.jl:43-66): STEP_A, [halo of u], STEP_B, [all-gather dot], STEP_C, [all-gather rr], STEP_D. */
+enum mik_cgd_phase_id {
+    MIK_CGD_STEP_A = 0,            /* u = r + beta u; pack the halo of u */
+    MIK_CGD_STEP_B = 1,            /* c = A u with the local dot(u, c) */
+    MIK_CGD_STEP_C = 2,            /* alpha; x += alpha u; r -= alpha c; local |r|^2 */
+    MIK_CGD_STEP_D = 3,            /* residual, beta, stopping test of src/cg.jl:36 for iteration + 1 (later steps become no-ops) */
+    MIK_CGD_STEP_B_INTERIOR = 4,   /* STEP_B on the row-blocks of mik_cgd_set_interior only */
+    MIK_CGD_STEP_B_REST = 5,       /* ... on all other row-blocks, then the local dot(u, c) */
+    MIK_CGD_INIT_A = 10,           /* pack the halo of x (nothing if x is zero) */
+    MIK_CGD_INIT_B = 11,           /* r = b - A x; local |r|^2; u = 0 */
+    MIK_CGD_INIT_C = 12            /* residual, tolerance */
+};
+/* Enqueue one phase (no host synchronisation). */
 int mik_cgd_phase(mik_cgd *it, int phase, int64_t iteration);
 /* Overlap of the halo exchange with the SpMV: row-blocks (256 rows each) [rb_begin, rb_end) of this rank contain no
- * row that references a halo column.  Step B may then be issued as phase 4 (those row-blocks; needs no halo, so
- * it runs while the exchange is in flight) followed by phase 5 (the remaining row-blocks + the local dot) -- same
- * results as phase 1.  MIK_ERR_NOTIMPL if the operator's layout cannot be launched over a range. */
+ * row that references a halo column.  Step B may then be issued as STEP_B_INTERIOR (those row-blocks; needs no halo, so
+ * it runs while the exchange is in flight) followed by STEP_B_REST (the remaining row-blocks + the local dot) -- same
+ * results as STEP_B.  MIK_ERR_NOTIMPL if the operator's layout cannot be launched over a range. */
 int mik_cgd_set_interior(mik_cgd *it, int64_t rb_begin, int64_t rb_end);
 /* Wait for everything enqueued; residual / tol / done of the last step and the residuals of the
  * steps executed since the previous wait (at most 1024 steps may be enqueued between waits). */

@@ -1148,7 +1148,7 @@ template <typename T> static int cgd_norm_stage1(mik_cgd *it, bool *direct)
     (void)std::frexp((double)amax, &e);
     e = std::max(-NrmRange<T>::EC, std::min(NrmRange<T>::EC, e));
     it->norm_scale = std::ldexp(1.0, -e);
-    return mik_cgd_phase(it, 22, 0);
+    return mik_cgd_phase(it, CGD_NORM_SCALED_SQ, 0);
 }
 
 template <typename T> static int cgd_norm_stage2(mik_cgd *it)
@@ -1174,48 +1174,29 @@ static int cgd_require_transport(mik_cgd *it, const char *who)
     return MIK_OK;
 }
 
-static int comm_scaled_norm(mik_cgd *it)
+// cg_iterator! (src/cg.jl:120-155) over the partition, on the ranks `rk` stands for (CgdComm / CgdGroup below): INIT_A, [halo of x],
+// INIT_B, [gather |r|^2], INIT_C, then one wait; a norm(r) outside the safe range (on every rank alike) is redone with a common scale.
+template <class R> static int cgd_init_ranks(R &rk, double *residual, double *tol)
 {
-    bool direct = false;
-    MIK_TRY(mik_cgd_phase(it, 20, 0));
-    MIK_TRY(gather_scalar(it, it->rr_all, 2));
-    MIK_TRY(cgd_norm_stage1_any(it, &direct));
-    if (direct) return MIK_OK;
-    MIK_TRY(gather_scalar(it, it->rr_all, 2));
-    return cgd_norm_stage2_any(it);
-}
-
-// cg_iterator! (src/cg.jl:120-155) over the partition: phases 10, [halo of x], 11, [gather |r|^2], 12, then one wait.
-extern "C" int mik_cgd_init(mik_cgd *it, double *residual, double *tol)
-{
-    if (!it) return MIK_ERR_INVALID;
-    MIK_TRY(cgd_require_transport(it, "mik_cgd_init"));
-    MIK_TRY(mik_cgd_phase(it, 10, 0));
-    bool pending = false;
-    if (!it->initially_zero) MIK_TRY(halo_begin(it, &pending));
-    MIK_TRY(halo_end(it, pending));
-    MIK_TRY(mik_cgd_phase(it, 11, 0));
-    MIK_TRY(gather_scalar(it, it->rr_all, 2));
-    MIK_TRY(mik_cgd_phase(it, 12, 0));
-    int done = 0;
-    int64_t steps = 0;
+    MIK_TRY(rk.phase(MIK_CGD_INIT_A));
+    MIK_TRY(rk.halo_x());
+    MIK_TRY(rk.phase(MIK_CGD_INIT_B));
+    MIK_TRY(rk.gather_rr_init());
+    MIK_TRY(rk.phase(MIK_CGD_INIT_C));
     CgMirror m;
-    MIK_TRY(cgd_wait_raw(it, &m));
-    if (m.range) {                                                  // norm(r) outside the safe range on every rank alike: common scale
-        MIK_TRY(comm_scaled_norm(it));
-        MIK_TRY(mik_cgd_phase(it, 24, 0));
-        MIK_TRY(cgd_wait_raw(it, &m));
+    MIK_TRY(rk.wait(&m));
+    if (m.range) {
+        MIK_TRY(rk.scaled_norm());
+        MIK_TRY(rk.phase(CGD_FIX_INIT));
+        MIK_TRY(rk.wait(&m));
     }
-    MIK_TRY(mailbox_check(it->comm, "mik_cgd_init"));
-    MIK_TRY(cgd_collect(it, m, residual, tol, &done, nullptr, 0, &steps));
-    it->initialised = true;
-    return MIK_OK;
+    int64_t steps = 0;
+    return rk.collect(m, residual, tol, nullptr, 0, &steps);
 }
 
-// one iterate() (src/cg.jl:43-66) of this rank, enqueued without any host synchronisation, in two halves: the HEAD writes
-// only u (with its halo), c and this rank's dot slot -- all of its inputs are final once the previous tail has run -- so the
-// head of the step after a call is enqueued before the host waits (as in the single-GPU path, cg_enqueue_head); every rank
-// takes the same decision (same iteration counts, identical stopping scalars), so the RCCL call sequences stay aligned.
+// One iterate() (src/cg.jl:43-66) of this rank, enqueued without any host synchronisation, as the head and the tail of cg_run_batch
+// (csrc/mik_iter.h); every rank takes the same decisions (same iteration counts, identical stopping scalars), so the RCCL call
+// sequences stay aligned.
 // the step's two scalar exchanges inside the finalising kernels: a connected mailbox, more than one rank (or MIK_KNOB_TRANSPORT bit 2),
 // not switched to the one-wave gather launches (bit 3) or to RCCL (bit 1)
 static bool mail_fused(const mik_cgd *it)
@@ -1251,15 +1232,15 @@ template <typename T> static int mail_fin_rr(mik_cgd *it, int64_t iteration)
     return MIK_OK;
 }
 
-// the local dot(u, c) of the head and its sum over the ranks: phase `with_fin` (SpMV + finaliser into the rank's slot) and a gather, or
-// phase `without` and the finaliser that exchanges by itself
-static int head_spmv_dot(mik_cgd *it, int with_fin, int without, int64_t iteration)
+// the local dot(u, c) of the head and its sum over the ranks: STEP_B (rest = false) or STEP_B_REST with the finaliser into the rank's
+// slot and a gather, or their NOFIN forms and the finaliser that exchanges by itself
+static int head_spmv_dot(mik_cgd *it, bool rest, int64_t iteration)
 {
     if (mail_fused(it)) {
-        MIK_TRY(mik_cgd_phase(it, without, iteration));
+        MIK_TRY(mik_cgd_phase(it, rest ? CGD_STEP_B_REST_NOFIN : CGD_STEP_B_NOFIN, iteration));
         return it->base.dtype == MIK_F64 ? mail_fin_dot<double>(it) : mail_fin_dot<float>(it);
     }
-    MIK_TRY(mik_cgd_phase(it, with_fin, iteration));
+    MIK_TRY(mik_cgd_phase(it, rest ? MIK_CGD_STEP_B_REST : MIK_CGD_STEP_B, iteration));
     return gather_scalar(it, it->dot_all, 0);
 }
 
@@ -1274,52 +1255,108 @@ static int cgd_enqueue_head(mik_cgd *it, int64_t iteration)
         // launch waits for it, and the SpMV is ONE launch over all row-blocks -- no interior / boundary split: every launch costs the
         // compute stream ~5 us whatever it does (profiles/r04_dist_selfhalo_timeline_*.txt), and the split bought overlap that the
         // sweep already provides.
-        MIK_TRY(mik_cgd_phase(it, it->early_merged ? 9 : 7, iteration));   // u on the rows the neighbours need; pack
+        MIK_TRY(mik_cgd_phase(it, it->early_merged ? CGD_STEP_A_EARLY_MERGED : CGD_STEP_A_EARLY, iteration));   // u on the rows the neighbours need; pack
         MIK_TRY(halo_mark(it));                                     // "packed": a one-thread launch (the pack kernel publishing the flag itself --
                                                                     // write-through stores, a two-level ticket of its 2,048 workgroups -- cost it 8 us
                                                                     // more than this launch costs: 15.8 us against 8.1 + 5.7, round 4)
-        MIK_TRY(mik_cgd_phase(it, 8, iteration));                   // the bulk of the sweep over u is on the compute stream ...
+        MIK_TRY(mik_cgd_phase(it, CGD_STEP_A_BULK, iteration));                   // the bulk of the sweep over u is on the compute stream ...
         MIK_TRY(halo_issue(it, &pending));                          // ... before the host enters RCCL
         MIK_TRY(halo_end(it, pending));
-        return head_spmv_dot(it, 1, 14, iteration);                 // c = A u, local dot(u, c), summed over the ranks
+        return head_spmv_dot(it, false, iteration);                 // c = A u, local dot(u, c), summed over the ranks
     }
     if (early) {
-        MIK_TRY(mik_cgd_phase(it, it->early_merged ? 9 : 7, iteration));   // u on the rows the neighbours need; pack
+        MIK_TRY(mik_cgd_phase(it, it->early_merged ? CGD_STEP_A_EARLY_MERGED : CGD_STEP_A_EARLY, iteration));   // u on the rows the neighbours need; pack
         MIK_TRY(halo_mark(it));
-        MIK_TRY(mik_cgd_phase(it, 8, iteration));                   // the bulk of the sweep over u ...
+        MIK_TRY(mik_cgd_phase(it, CGD_STEP_A_BULK, iteration));                   // the bulk of the sweep over u ...
         if (it->int_end > it->int_begin) {
-            MIK_TRY(mik_cgd_phase(it, 4, iteration));               // ... and the interior row-blocks are on the compute stream
+            MIK_TRY(mik_cgd_phase(it, MIK_CGD_STEP_B_INTERIOR, iteration));               // ... and the interior row-blocks are on the compute stream
             MIK_TRY(halo_issue(it, &pending));                 // before the host enters RCCL: the halo travels underneath them
             MIK_TRY(halo_end(it, pending));
-            return head_spmv_dot(it, 5, 13, iteration);             // boundary row-blocks + local dot(u, c), summed over the ranks
+            return head_spmv_dot(it, true, iteration);             // boundary row-blocks + local dot(u, c), summed over the ranks
         }
         MIK_TRY(halo_issue(it, &pending));
     } else {
-        MIK_TRY(mik_cgd_phase(it, 0, iteration));                   // u = r + beta u; pack the halo
+        MIK_TRY(mik_cgd_phase(it, MIK_CGD_STEP_A, iteration));                   // u = r + beta u; pack the halo
         MIK_TRY(halo_begin(it, &pending));
     }
     if (pending && it->int_end > it->int_begin) {
-        MIK_TRY(mik_cgd_phase(it, 4, iteration));                   // interior row-blocks while the halo is in flight
+        MIK_TRY(mik_cgd_phase(it, MIK_CGD_STEP_B_INTERIOR, iteration));                   // interior row-blocks while the halo is in flight
         MIK_TRY(halo_end(it, pending));
-        return head_spmv_dot(it, 5, 13, iteration);                 // boundary row-blocks + local dot(u, c), summed over the ranks
+        return head_spmv_dot(it, true, iteration);                 // boundary row-blocks + local dot(u, c), summed over the ranks
     }
     MIK_TRY(halo_end(it, pending));
-    return head_spmv_dot(it, 1, 14, iteration);
+    return head_spmv_dot(it, false, iteration);
 }
 
 static int cgd_enqueue_tail(mik_cgd *it, int64_t iteration)
 {
     if (mail_fused(it)) {
-        MIK_TRY(mik_cgd_phase(it, 16, iteration));                  // x, r update with the alpha k_cgd_fin_dot_mail stored; local |r|^2 partials
+        MIK_TRY(mik_cgd_phase(it, CGD_STEP_C_NOFIN, iteration));                  // x, r update with the alpha k_cgd_fin_dot_mail stored; local |r|^2 partials
         return it->base.dtype == MIK_F64 ? mail_fin_rr<double>(it, iteration) : mail_fin_rr<float>(it, iteration);   // ... summed over the ranks; residual, stopping test
     }
-    MIK_TRY(mik_cgd_phase(it, 2, iteration));                       // alpha; x, r update; local |r|^2
+    MIK_TRY(mik_cgd_phase(it, MIK_CGD_STEP_C, iteration));                       // alpha; x, r update; local |r|^2
     MIK_TRY(gather_scalar(it, it->rr_all, 1));
-    return mik_cgd_phase(it, 3, iteration);                         // residual, beta, stopping test
+    return mik_cgd_phase(it, MIK_CGD_STEP_D, iteration);                         // residual, beta, stopping test
 }
 
-// Up to max_steps iterate() calls of this rank with ONE host wait (every rank makes the same call; the stopping test
-// runs on the device from identical scalars, so all ranks execute the same number of steps).
+// The ranks of cg_run_batch / cgd_init_ranks for ONE iterable on a communicator (RCCL / mailbox); the other ranks run the same calls in
+// their own processes.
+struct CgdComm {
+    mik_cgd *it;
+    mik_cg &base() { return it->base; }
+    int phase(int ph) { return mik_cgd_phase(it, ph, 0); }
+    int halo_x()
+    {
+        bool pending = false;
+        if (!it->initially_zero) MIK_TRY(halo_begin(it, &pending));
+        return halo_end(it, pending);
+    }
+    int gather_rr_init() { return gather_scalar(it, it->rr_all, 2); }
+    int head(int64_t iteration) { return cgd_enqueue_head(it, iteration); }
+    int tail(int64_t iteration, int64_t) { return cgd_enqueue_tail(it, iteration); }
+    int flush_x() { return phase(CGD_X_FLUSH); }
+    int wait(CgMirror *m) { return cgd_wait_raw(it, m); }
+    // The frozen step's x .+= alpha .* u has been applied by now whatever came behind it: by the head of the next (no-op) step of
+    // the batch, by the head enqueued ahead or by CGD_X_FLUSH -- but without the mail-fused finalisers only a TAIL clears the pending
+    // flag (k_cgd_fin_slot_alpha / k_cgd_alpha), and none follows the head ahead when the frozen step was the last of the batch.
+    // Left set, the fresh head of the next call would add the same alpha u to x a second time: clear it behind everything that is
+    // enqueued.  (A single-GPU head clears the flag itself, and the group enqueues nothing ahead: CgLocal, CgdGroup.)
+    int clear_pending() { return it->base.fuse_x ? phase(CGD_CLEAR_PENDING) : MIK_OK; }
+    int scaled_norm()
+    {
+        bool direct = false;
+        MIK_TRY(phase(CGD_NORM_AMAX));
+        MIK_TRY(gather_rr_init());
+        MIK_TRY(cgd_norm_stage1_any(it, &direct));
+        if (direct) return MIK_OK;
+        MIK_TRY(gather_rr_init());
+        return cgd_norm_stage2_any(it);
+    }
+    int close_frozen(int64_t it_next, int hist_index)
+    {
+        it->norm_fix_index = hist_index;
+        it->norm_it_next = it_next;
+        return phase(CGD_FIX_STEP);
+    }
+    int collect(const CgMirror &m, double *residual, double *tol, double *history, int64_t cap, int64_t *steps)
+    {
+        int done = 0;
+        MIK_TRY(mailbox_check(it->comm, "row-partitioned cg"));
+        return cgd_collect(it, m, residual, tol, &done, history, cap, steps);
+    }
+};
+
+extern "C" int mik_cgd_init(mik_cgd *it, double *residual, double *tol)
+{
+    if (!it) return MIK_ERR_INVALID;
+    MIK_TRY(cgd_require_transport(it, "mik_cgd_init"));
+    CgdComm rk{it};
+    MIK_TRY(cgd_init_ranks(rk, residual, tol));
+    it->initialised = true;
+    return MIK_OK;
+}
+
+// Up to max_steps iterate() calls of this rank with ONE host wait (every rank makes the same call: cg_run_batch, csrc/mik_iter.h).
 extern "C" int mik_cgd_iterate_many(mik_cgd *it, int64_t iteration, int64_t max_steps, double *residuals, int64_t *steps_done)
 {
     if (!it || !steps_done || iteration < 0) return MIK_ERR_INVALID;
@@ -1331,37 +1368,8 @@ extern "C" int mik_cgd_iterate_many(mik_cgd *it, int64_t iteration, int64_t max_
     max_steps = std::min<int64_t>(std::min<int64_t>(max_steps, bs.maxiter - iteration), bs.hist_cap);
     const bool ahead_ok = bs.ctx->tuning[MIK_KNOB_NO_LOOKAHEAD] == 0 && iteration + max_steps < bs.maxiter;      // MIK_KNOB_NO_LOOKAHEAD: nothing ahead of the host
     bs.fuse_x = (bs.ctx->tuning[MIK_KNOB_CG_STEP] & 1) == 0;                              // x .+= alpha .* u rides on the next sweep over u (as in mik_cg_*)
-    CgMirror m;
-    for (int64_t j0 = 0;;) {
-        for (int64_t j = j0; j < max_steps; ++j) {
-            if (!bs.head_ahead) MIK_TRY(cgd_enqueue_head(it, iteration + j));
-            bs.head_ahead = false;
-            MIK_TRY(cgd_enqueue_tail(it, iteration + j));
-        }
-        if (ahead_ok) MIK_TRY(cgd_enqueue_head(it, iteration + max_steps));
-        else if (bs.fuse_x) MIK_TRY(mik_cgd_phase(it, 6, iteration + max_steps - 1));   // no sweep over u follows: apply the last x update now
-        MIK_TRY(cgd_wait_raw(it, &m));
-        if (!m.range) { bs.head_ahead = ahead_ok && !m.done; break; }  // stopped: the head ahead was a no-op on every rank
-        // Step m.nhist of this call updated x and r, but |r|^2 summed over the ranks left the range in which sqrt(sum of squares)
-        // is safe: every rank froze its batch on the same total; finish that step with the norm rescaled across the ranks and
-        // go on (the single-GPU iterable does the same on its own, cg_iterate_many_impl).
-        bs.head_ahead = false;
-        // The frozen step's x .+= alpha .* u has been applied by now whatever came behind it: by the head of the next (no-op) step of
-        // the batch, by the head enqueued ahead (ahead_ok) or by the flush of phase 6 -- but only a TAIL clears the pending flag, and
-        // none follows the head ahead when the frozen step was the last of the batch.  Left set, the fresh head of the next call
-        // would add the same alpha u to x a second time: clear it behind everything that is enqueued.
-        if (bs.fuse_x) MIK_TRY(mik_cgd_phase(it, 25, 0));
-        MIK_TRY(comm_scaled_norm(it));
-        it->norm_fix_index = (int)m.nhist;
-        it->norm_it_next = iteration + m.nhist + 1;
-        MIK_TRY(mik_cgd_phase(it, 23, 0));
-        MIK_TRY(cgd_wait_raw(it, &m));
-        j0 = m.nhist;
-        if (m.done || j0 >= max_steps) break;
-    }
-    int done = 0;
-    MIK_TRY(mailbox_check(it->comm, "mik_cgd_iterate_many"));
-    return cgd_collect(it, m, nullptr, nullptr, &done, residuals, max_steps, steps_done);
+    CgdComm rk{it};
+    return cg_run_batch(rk, iteration, max_steps, ahead_ok, residuals, steps_done);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1383,7 +1391,6 @@ struct GroupState {
             for (hipEvent_t e : *v) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : ev.side) if (s) (void)hipStreamDestroy(s);
     }
-    bool peer_access = true;         // hipDeviceEnablePeerAccess succeeded between every pair of devices
 };
 
 // groups are keyed by their rank-0 handle and live until mik_cgd_group_release (or process exit)
@@ -1431,8 +1438,7 @@ static int group_get(mik_cgd **its, int P, GroupState **out)
                 if (its[q]->base.ctx->device != ctx->device) {
                     // (not fatal: the copies below are hipMemcpyPeerAsync, which the runtime stages through the host where two devices
                     // cannot address each other -- the group is the transport of last resort and must come up on any topology)
-                    hipError_t e = hipDeviceEnablePeerAccess(its[q]->base.ctx->device, 0);
-                    if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) g->peer_access = false;
+                    (void)hipDeviceEnablePeerAccess(its[q]->base.ctx->device, 0);
                     (void)hipGetLastError();
                 }
             for (auto *v : {&g->ev.packed, &g->ev.halo, &g->ev.dot, &g->ev.rr}) MIK_HIP(ctx, hipEventCreateWithFlags(&(*v)[p], hipEventDisableTiming));
@@ -1529,87 +1535,133 @@ static int group_gather_scalar(GroupState *g, int which)
     return MIK_OK;
 }
 
-static int group_all(GroupState *g, int phase, int64_t iteration)
-{
-    for (int p = 0; p < g->P; ++p) {
-        MIK_HIP(g->its[p]->base.ctx, hipSetDevice(g->its[p]->base.ctx->device));
-        MIK_TRY(mik_cgd_phase(g->its[p], phase, iteration));
+// The ranks of cg_run_batch / cgd_init_ranks for the in-process group: P iterables driven by one host thread, peer copies for the
+// exchanges, nothing enqueued ahead of the host.
+struct CgdGroup {
+    GroupState *g;
+    bool split = false, early = false;     // every rank has an interior range / early rows too (mik_cgd_group_iterate_many decides)
+    std::vector<char> pending;
+    std::vector<CgMirror> ms;
+    mik_cg &base() { return g->its[0]->base; }
+    int set_device(int p) { MIK_HIP(g->its[p]->base.ctx, hipSetDevice(g->its[p]->base.ctx->device)); return MIK_OK; }
+    int phase(int ph, int64_t iteration = 0)
+    {
+        for (int p = 0; p < g->P; ++p) {
+            MIK_TRY(set_device(p));
+            MIK_TRY(mik_cgd_phase(g->its[p], ph, iteration));
+        }
+        return MIK_OK;
     }
-    return MIK_OK;
-}
-
-static int group_halo_end(GroupState *g, const std::vector<char> &pending, int p)
-{
-    if (pending[(size_t)p]) MIK_HIP(g->its[p]->base.ctx, hipStreamWaitEvent(g->its[p]->base.ctx->stream, g->ev.halo[p], 0));
-    return MIK_OK;
-}
-
-static int group_wait_raw(GroupState *g, std::vector<CgMirror> &ms)
-{
-    for (int p = 0; p < g->P; ++p) {
-        MIK_HIP(g->its[p]->base.ctx, hipSetDevice(g->its[p]->base.ctx->device));
-        MIK_TRY(cgd_wait_raw(g->its[p], &ms[(size_t)p]));
-        if (ms[(size_t)p].range != ms[0].range)
-            return mik_fail(g->its[p]->base.ctx, MIK_ERR_MISMATCH, "row-partitioned cg: rank %d disagrees with rank 0 on the range of |r|^2", p);
+    int halo_end_all()
+    {
+        for (int p = 0; p < g->P; ++p)
+            if (pending[(size_t)p]) MIK_HIP(g->its[p]->base.ctx, hipStreamWaitEvent(g->its[p]->base.ctx->stream, g->ev.halo[p], 0));
+        return MIK_OK;
     }
-    return MIK_OK;
-}
-
-// the scaled norm of r over the group's ranks (cgd_norm_stage*): every rank repeats the host arithmetic on identical slots
-static int group_scaled_norm(GroupState *g)
-{
-    const int P = g->P;
-    MIK_TRY(group_all(g, 20, 0));
-    MIK_TRY(group_gather_scalar(g, 1));
-    bool direct = false;
-    for (int p = 0; p < P; ++p) {
-        bool dp = false;
-        MIK_HIP(g->its[p]->base.ctx, hipSetDevice(g->its[p]->base.ctx->device));
-        MIK_TRY(cgd_norm_stage1_any(g->its[p], &dp));
-        if (p == 0) direct = dp;
-        else if (dp != direct) return mik_fail(g->its[p]->base.ctx, MIK_ERR_MISMATCH, "row-partitioned cg: rank %d disagrees with rank 0 on max |r|", p);
+    int halo_x()
+    {
+        if (g->its[0]->initially_zero) return MIK_OK;
+        MIK_TRY(group_halo_begin(g, pending));
+        return halo_end_all();
     }
-    if (direct) return MIK_OK;
-    MIK_TRY(group_gather_scalar(g, 1));
-    for (int p = 0; p < P; ++p) {
-        MIK_HIP(g->its[p]->base.ctx, hipSetDevice(g->its[p]->base.ctx->device));
-        MIK_TRY(cgd_norm_stage2_any(g->its[p]));
+    int gather_rr_init() { return group_gather_scalar(g, 1); }
+    int head(int64_t itn)                                           // the step structure of cgd_enqueue_head, with peer copies for RCCL
+    {
+        if (early) {
+            for (int p = 0; p < g->P; ++p) {
+                MIK_TRY(set_device(p));
+                MIK_TRY(mik_cgd_phase(g->its[p], g->its[p]->early_merged ? CGD_STEP_A_EARLY_MERGED : CGD_STEP_A_EARLY, itn));
+            }
+            MIK_TRY(group_halo_begin(g, pending));
+            MIK_TRY(phase(CGD_STEP_A_BULK, itn));
+        } else {
+            MIK_TRY(phase(MIK_CGD_STEP_A, itn));
+            MIK_TRY(group_halo_begin(g, pending));
+        }
+        if (split) {
+            MIK_TRY(phase(MIK_CGD_STEP_B_INTERIOR, itn));
+            MIK_TRY(halo_end_all());
+            MIK_TRY(phase(MIK_CGD_STEP_B_REST, itn));
+        } else {
+            MIK_TRY(halo_end_all());
+            MIK_TRY(phase(MIK_CGD_STEP_B, itn));
+        }
+        return group_gather_scalar(g, 0);
     }
-    return MIK_OK;
-}
+    int tail(int64_t itn, int64_t)
+    {
+        MIK_TRY(phase(MIK_CGD_STEP_C, itn));
+        MIK_TRY(group_gather_scalar(g, 1));
+        return phase(MIK_CGD_STEP_D, itn);
+    }
+    int flush_x() { return phase(CGD_X_FLUSH); }
+    int wait(CgMirror *m)
+    {
+        ms.resize((size_t)g->P);
+        for (int p = 0; p < g->P; ++p) {
+            MIK_TRY(set_device(p));
+            MIK_TRY(cgd_wait_raw(g->its[p], &ms[(size_t)p]));
+            if (ms[(size_t)p].range != ms[0].range)
+                return mik_fail(g->its[p]->base.ctx, MIK_ERR_MISMATCH, "row-partitioned cg: rank %d disagrees with rank 0 on the range of |r|^2", p);
+        }
+        *m = ms[0];
+        return MIK_OK;
+    }
+    // nothing to do: no head runs ahead here, so a frozen last step is followed by CGD_X_FLUSH, which clears the flag (see CgdComm)
+    int clear_pending() { return MIK_OK; }
+    // (cgd_norm_stage*): every rank repeats the host arithmetic on identical slots
+    int scaled_norm()
+    {
+        MIK_TRY(phase(CGD_NORM_AMAX));
+        MIK_TRY(group_gather_scalar(g, 1));
+        bool direct = false;
+        for (int p = 0; p < g->P; ++p) {
+            bool dp = false;
+            MIK_TRY(set_device(p));
+            MIK_TRY(cgd_norm_stage1_any(g->its[p], &dp));
+            if (p == 0) direct = dp;
+            else if (dp != direct) return mik_fail(g->its[p]->base.ctx, MIK_ERR_MISMATCH, "row-partitioned cg: rank %d disagrees with rank 0 on max |r|", p);
+        }
+        if (direct) return MIK_OK;
+        MIK_TRY(group_gather_scalar(g, 1));
+        for (int p = 0; p < g->P; ++p) {
+            MIK_TRY(set_device(p));
+            MIK_TRY(cgd_norm_stage2_any(g->its[p]));
+        }
+        return MIK_OK;
+    }
+    int close_frozen(int64_t it_next, int hist_index)
+    {
+        for (mik_cgd *it : g->its) { it->norm_fix_index = hist_index; it->norm_it_next = it_next; }
+        return phase(CGD_FIX_STEP);
+    }
+    // every rank's scalars and history must equal rank 0's
+    int collect(const CgMirror &, double *residual, double *tol, double *history, int64_t cap, int64_t *steps)
+    {
+        std::vector<double> h0((size_t)cap), hp((size_t)cap);
+        for (int p = 0; p < g->P; ++p) {
+            mik_cgd *it = g->its[p];
+            double res = 0, tl = 0;
+            int done = 0;
+            int64_t st = 0;
+            MIK_TRY(set_device(p));
+            MIK_TRY(cgd_collect(it, ms[(size_t)p], &res, &tl, &done, p == 0 ? h0.data() : hp.data(), cap, &st));
+            if (p == 0) { *steps = st; if (residual) *residual = res; if (tol) *tol = tl; }
+            else if (st != *steps || !std::equal(h0.begin(), h0.begin() + st, hp.begin()) || res != base().residual || tl != base().tol)
+                return mik_fail(it->base.ctx, MIK_ERR_MISMATCH, "row-partitioned cg (group): rank %d disagrees with rank 0 on the residuals", p);
+        }
+        if (history) std::copy(h0.begin(), h0.begin() + *steps, history);
+        return MIK_OK;
+    }
+};
 
 extern "C" int mik_cgd_group_init(mik_cgd **its, int P, double *residual, double *tol)
 {
     MIK_TRY(group_check(its, P, "mik_cgd_group_init"));
-    GroupState *g = nullptr;
-    MIK_TRY(group_get(its, P, &g));
-    std::vector<char> pending;
-    MIK_TRY(group_all(g, 10, 0));
-    if (!its[0]->initially_zero) {
-        MIK_TRY(group_halo_begin(g, pending));
-        for (int p = 0; p < P; ++p) MIK_TRY(group_halo_end(g, pending, p));
-    }
-    MIK_TRY(group_all(g, 11, 0));
-    MIK_TRY(group_gather_scalar(g, 1));
-    MIK_TRY(group_all(g, 12, 0));
-    std::vector<CgMirror> ms((size_t)P);
-    MIK_TRY(group_wait_raw(g, ms));
-    if (ms[0].range) {
-        MIK_TRY(group_scaled_norm(g));
-        MIK_TRY(group_all(g, 24, 0));
-        MIK_TRY(group_wait_raw(g, ms));
-    }
-    for (int p = 0; p < P; ++p) {
-        double res = 0, tl = 0;
-        int done = 0;
-        int64_t steps = 0;
-        MIK_HIP(its[p]->base.ctx, hipSetDevice(its[p]->base.ctx->device));
-        MIK_TRY(cgd_collect(its[p], ms[(size_t)p], &res, &tl, &done, nullptr, 0, &steps));
-        its[p]->initialised = true;
-        if (p == 0) { if (residual) *residual = res; if (tol) *tol = tl; }
-        else if (res != its[0]->base.residual || tl != its[0]->base.tol)
-            return mik_fail(its[p]->base.ctx, MIK_ERR_MISMATCH, "mik_cgd_group_init: rank %d disagrees with rank 0 on the initial residual", p);
-    }
+    CgdGroup rk{};
+    MIK_TRY(group_get(its, P, &rk.g));
+    MIK_TRY(cgd_init_ranks(rk, residual, tol));
+    for (int p = 0; p < P; ++p) its[p]->initialised = true;
     return MIK_OK;
 }
 
@@ -1618,74 +1670,18 @@ extern "C" int mik_cgd_group_iterate_many(mik_cgd **its, int P, int64_t iteratio
     MIK_TRY(group_check(its, P, "mik_cgd_group_iterate_many"));
     if (!steps_done || iteration < 0) return MIK_ERR_INVALID;
     *steps_done = 0;
-    GroupState *g = nullptr;
-    MIK_TRY(group_get(its, P, &g));
+    CgdGroup rk{};
+    MIK_TRY(group_get(its, P, &rk.g));
     mik_cg &b0 = its[0]->base;
     for (int p = 0; p < P; ++p) if (!its[p]->initialised) return mik_fail(b0.ctx, MIK_ERR_INVALID, "mik_cgd_group_iterate_many: call mik_cgd_group_init first");
     if (max_steps <= 0 || iteration >= b0.maxiter || b0.residual <= b0.tol) return MIK_OK;
     max_steps = std::min<int64_t>(std::min<int64_t>(max_steps, b0.maxiter - iteration), b0.hist_cap);
-    bool split = true, early = true;
+    rk.split = rk.early = true;
     for (int p = 0; p < P; ++p) {
-        split = split && its[p]->int_end > its[p]->int_begin;
-        early = early && its[p]->n_early > 0;
+        rk.split = rk.split && its[p]->int_end > its[p]->int_begin;
+        rk.early = rk.early && its[p]->n_early > 0;
         its[p]->base.fuse_x = (its[p]->base.ctx->tuning[MIK_KNOB_CG_STEP] & 1) == 0;                // as mik_cgd_iterate_many: x .+= alpha .* u rides on the next sweep over u
     }
-    early = early && split;
-    std::vector<char> pending;
-    std::vector<CgMirror> ms((size_t)P);
-    for (int64_t j0 = 0;;) {
-        for (int64_t j = j0; j < max_steps; ++j) {
-            const int64_t itn = iteration + j;
-            if (early) {                                                // the step structure of cgd_enqueue_head, with peer copies for RCCL
-                for (int p = 0; p < P; ++p) {
-                    MIK_HIP(its[p]->base.ctx, hipSetDevice(its[p]->base.ctx->device));
-                    MIK_TRY(mik_cgd_phase(its[p], its[p]->early_merged ? 9 : 7, itn));
-                }
-                MIK_TRY(group_halo_begin(g, pending));
-                MIK_TRY(group_all(g, 8, itn));
-            } else {
-                MIK_TRY(group_all(g, 0, itn));
-                MIK_TRY(group_halo_begin(g, pending));
-            }
-            if (split) {
-                MIK_TRY(group_all(g, 4, itn));
-                for (int p = 0; p < P; ++p) MIK_TRY(group_halo_end(g, pending, p));
-                MIK_TRY(group_all(g, 5, itn));
-            } else {
-                for (int p = 0; p < P; ++p) MIK_TRY(group_halo_end(g, pending, p));
-                MIK_TRY(group_all(g, 1, itn));
-            }
-            MIK_TRY(group_gather_scalar(g, 0));
-            MIK_TRY(group_all(g, 2, itn));
-            MIK_TRY(group_gather_scalar(g, 1));
-            MIK_TRY(group_all(g, 3, itn));
-        }
-        if (its[0]->base.fuse_x) MIK_TRY(group_all(g, 6, iteration + max_steps - 1));     // nothing runs ahead here: apply the last x update now
-        MIK_TRY(group_wait_raw(g, ms));
-        if (!ms[0].range) break;
-        // a frozen step (|r|^2 outside the safe range on every rank alike): scaled norm over the ranks, close the step, go on
-        MIK_TRY(group_scaled_norm(g));
-        for (int p = 0; p < P; ++p) {
-            its[p]->norm_fix_index = (int)ms[(size_t)p].nhist;
-            its[p]->norm_it_next = iteration + ms[(size_t)p].nhist + 1;
-        }
-        MIK_TRY(group_all(g, 23, 0));
-        MIK_TRY(group_wait_raw(g, ms));
-        j0 = ms[0].nhist;
-        if (ms[0].done || j0 >= max_steps) break;
-    }
-    std::vector<double> h0((size_t)max_steps), hp((size_t)max_steps);
-    int64_t n0 = 0;
-    for (int p = 0; p < P; ++p) {
-        int done = 0;
-        int64_t steps = 0;
-        MIK_HIP(its[p]->base.ctx, hipSetDevice(its[p]->base.ctx->device));
-        MIK_TRY(cgd_collect(its[p], ms[(size_t)p], nullptr, nullptr, &done, p == 0 ? h0.data() : hp.data(), max_steps, &steps));
-        if (p == 0) n0 = steps;
-        else if (steps != n0 || !std::equal(h0.begin(), h0.begin() + n0, hp.begin()))
-            return mik_fail(its[p]->base.ctx, MIK_ERR_MISMATCH, "mik_cgd_group_iterate_many: rank %d disagrees with rank 0 on the residual history", p);
-    }
-    if (residuals) std::copy(h0.begin(), h0.begin() + n0, residuals);
-    *steps_done = n0;
-    return MIK_OK;
+    rk.early = rk.early && rk.split;
+    return cg_run_batch(rk, iteration, max_steps, false, residuals, steps_done);
 }

@@ -114,7 +114,6 @@ template <typename T> __device__ __forceinline__ bool level2_sum_spread(const T 
     return last;
 }
 
-
 // residual = norm(r) of a row-partitioned step from the rank-ordered total of |r|^2 (src/cg.jl:61-62), history, beta and the stopping test
 // of :36 for the next iterate() call; one thread.  A total outside the range of a safe sqrt(sum of squares) freezes the batch on every
 // rank alike (identical totals): x and r of the step are final, the hosts finish it with the scaled norm over the partition.
@@ -144,6 +143,42 @@ __device__ __forceinline__ void cgd_close_step(CgDev<T> *d, T tot, T *__restrict
 // Wait until the device has published step `it->seq` in the host-mapped mirror (bounded spin).
 int cg_wait_mirror(mik_cg *it);
 
+// Up to max_steps iterate() calls (src/cg.jl:43-66) with ONE host wait, on the ranks `rk` stands for: one local iterable
+// (CgLocal, csrc/mik_krylov.hip), one iterable on a communicator or the in-process group (CgdComm / CgdGroup, csrc/mik_comm.hip).
+// The stopping test runs on the device (steps behind a stop are no-ops) from scalars that are identical on every rank, so all
+// ranks execute the same steps.  One iterate() = HEAD (u = r + beta u; c = A u; dot(u, c)) + TAIL (x, r update; residual, stopping test):
+// the head only writes u, c and scalars and all of its inputs are final once the previous tail has run, so with `ahead_ok` the
+// head of the step AFTER this call goes on the stream before the host waits and the device never idles while the host reacts.
+// rk supplies: base() (rank 0's handle), head(iteration), tail(iteration, hist_index), flush_x(), wait(&m) (rank 0's mirror, the
+// others checked against it), clear_pending(), scaled_norm(), close_frozen(it_next, hist_index), collect(m, &residual, &tol, history, cap, &steps).
+template <class R> static int cg_run_batch(R &rk, int64_t iteration, int64_t max_steps, bool ahead_ok, double *residuals, int64_t *steps_done)
+{
+    mik_cg &b0 = rk.base();
+    CgMirror m;
+    for (int64_t j0 = 0;;) {
+        for (int64_t j = j0; j < max_steps; ++j) {
+            if (!b0.head_ahead) MIK_TRY(rk.head(iteration + j));
+            b0.head_ahead = false;
+            MIK_TRY(rk.tail(iteration + j, j));
+        }
+        if (ahead_ok) MIK_TRY(rk.head(iteration + max_steps));
+        else if (b0.fuse_x) MIK_TRY(rk.flush_x());                     // no sweep over u follows: apply the last x .+= alpha .* u now
+        MIK_TRY(rk.wait(&m));
+        if (!m.range) { b0.head_ahead = ahead_ok && !m.done; break; }  // stopped: the head ahead was a no-op (on every rank)
+        b0.head_ahead = false;                                         // frozen batch: so was everything behind the frozen step
+        // Step m.nhist of this call updated x and r, but |r|^2 (summed over the ranks) left the range in which sqrt(sum of squares)
+        // is safe (include/mik.h "Norms"): the device froze the batch (every rank on the same total); finish that step with the
+        // scaled norm and go on.
+        MIK_TRY(rk.clear_pending());
+        MIK_TRY(rk.scaled_norm());
+        MIK_TRY(rk.close_frozen(iteration + m.nhist + 1, (int)m.nhist));
+        MIK_TRY(rk.wait(&m));
+        j0 = m.nhist;
+        if (m.done || j0 >= max_steps) break;
+    }
+    return rk.collect(m, nullptr, nullptr, residuals, max_steps, steps_done);
+}
+
 struct mik_comm;
 struct mik_plink;
 struct mik_cgd {
@@ -171,10 +206,27 @@ struct mik_cgd {
     int n_early = 0;
     bool early_merged = false;            // every send index occurs once: update + pack are one launch (k_cgd_early)
     int64_t early_a[2] = {0, 0}, early_b[2] = {0, 0};
-    // the over-/underflow-safe norm across the partition (phases 20-24; csrc/mik_comm.hip cgd_norm_stage)
+    // the over-/underflow-safe norm across the partition (CGD_NORM_*, CGD_FIX_*; csrc/mik_comm.hip cgd_norm_stage)
     double norm_scale = 1.0, norm_res = 0.0;
     int norm_fix_index = 0;
     int64_t norm_it_next = 0;
+};
+
+// Phases of mik_cgd_phase that only the library's own loops enqueue (csrc/mik_comm.hip); mik_cgd_phase_id of include/mik.h has the
+// ones a host may drive.  "nofin": without the finaliser -- the mailbox transport finalises and exchanges in one kernel.
+enum cgd_phase_internal {
+    CGD_X_FLUSH = 6,                 // the x update that is still due when no head follows (end of a call without look-ahead)
+    CGD_STEP_A_EARLY = 7,            // STEP_A on the rows the neighbours need, then pack: the halo leaves first
+    CGD_STEP_A_BULK = 8,             // STEP_A's sweep on all other rows, while the halo is on the wire
+    CGD_STEP_A_EARLY_MERGED = 9,     // STEP_A_EARLY as one launch (every send index occurs once: mik_cgd_set_halo_plan)
+    CGD_STEP_B_REST_NOFIN = 13,
+    CGD_STEP_B_NOFIN = 14,
+    CGD_STEP_C_NOFIN = 16,           // ... and without alpha formation: alpha is the scalar k_cgd_fin_dot_mail stored
+    CGD_NORM_AMAX = 20,              // scaled norm of r over the partition, pass 1: this rank's max |r_i| -> rr_all[rank]
+    CGD_NORM_SCALED_SQ = 22,         // pass 2: this rank's tree sum of (r_i * s)^2, s = the common power of two (norm_scale) -> rr_all[rank]
+    CGD_FIX_STEP = 23,               // the frozen step closes with the scaled norm (norm_res), as k_cg_fix_res does on one GPU
+    CGD_FIX_INIT = 24,               // cg_iterator! closes with the scaled norm
+    CGD_CLEAR_PENDING = 25           // the pending x update of a frozen step has been applied: drop the flag
 };
 
 // waits for the last enqueued phase and copies the mirror; a frozen step (range) is reported in the copy, not as an error

@@ -515,7 +515,10 @@ __device__ __forceinline__ bool level2_sum_spread2(const T *__restrict__ S1, con
     return last;
 }
 
-// after norm(r) of cg_iterator! (src/cg.jl:140-152)
+// after norm(r) of cg_iterator! (src/cg.jl:140-152), for all four initialising kernels.  x_pending is NOT touched: the device struct
+// of a single-GPU iterable comes straight from hipMalloc, so k_cg_fin_init / k_cg_set_init clear the flag themselves; a
+// row-partitioned one is zeroed at creation and may be initialised again after a batch whose head ran ahead over RCCL, where
+// only a tail clears the flag -- k_cgd_fin_init / k_cgd_fix_init have always left it as it is, and still do.
 template <typename T> __device__ __forceinline__ void cg_init_scalars(CgDev<T> *d, T tot, T res, T reltol, T abstol, long long maxiter)
 {
     const T a = reltol * res;
@@ -529,7 +532,6 @@ template <typename T> __device__ __forceinline__ void cg_init_scalars(CgDev<T> *
     d->dot_uc = T(0);
     d->done = (0 >= maxiter || res <= d->tol) ? 1 : 0;
     d->nhist = 0;
-    d->x_pending = 0;
 }
 
 template <typename T>
@@ -538,13 +540,14 @@ __global__ __launch_bounds__(MIK_FIN_THREADS) void k_cg_fin_init(const T *__rest
 {
     __shared__ T lds16[16];
     T tot = level2_sum(S, m, lds16);
-    if (threadIdx.x == 0) cg_init_scalars(d, tot, mik_sqrt(tot), reltol, abstol, maxiter);   // the host re-does this if tot is out of range
+    if (threadIdx.x == 0) { cg_init_scalars(d, tot, mik_sqrt(tot), reltol, abstol, maxiter); d->x_pending = 0; }   // the host re-does this if tot is out of range
 }
 
 // the same with a residual norm the host obtained through the scaled pass (mik_safe_norm_slow)
 template <typename T> __global__ void k_cg_set_init(CgDev<T> *d, T res, T reltol, T abstol, long long maxiter)
 {
     cg_init_scalars(d, res * res, res, reltol, abstol, maxiter);
+    d->x_pending = 0;
 }
 
 // alpha = residual^2 / dot(u, c) (src/cg.jl:55) or rho / dot(u, c) (:90)
@@ -730,19 +733,80 @@ static inline int cg_stream_hints(const mik_ctx *ctx, bool fused_x = false, cons
     return fused_x ? (mik_spmv_is_light(A) ? 248 : 121) : 57;
 }
 
-// One iterate() = HEAD (u = r + beta u [after c = Pl \ r, rho]; c = A u; alpha) + TAIL (x, r update; residual, stopping test).
-// The head only writes the iterable's internal vectors u and c and scalars, and all of its inputs are final once the previous
-// tail has run -- so the head of step k + 1 may be put on the stream BEFORE the host waits for the residual of step k
-// (cg_iterate_many_impl): the device never idles while the host reacts.  If step k met the stopping test the head kernels
-// early-exit on the device's `done` flag like every later step of a batch.
+// ---- the vector sweeps of a step, each written once: the single-GPU head / tail below and the phases of the row-partitioned
+// iterable (cgd_phase_impl) call them.  `vec`: every vector the sweep touches is 16-byte aligned at its first row.
+
+// hints of the sweep over u when it reads r (cg_stream_hints: bit 3 = the x that rides on it)
+static inline int cg_sweep_u_hints(const mik_cg *it) { return it->fuse_x ? cg_stream_hints(it->ctx, true, it->A) & 15 : cg_stream_hints(it->ctx) & 7; }
+
+// u .= src .+ beta .* u on rows [lo, lo + len) (src/cg.jl:50-51; :86 with src = c = Pl \ r), and with fuse_x the pending
+// x .+= alpha .* u of the previous step on the u this sweep reads anyway (OpXpbyX)
+template <typename T> static int cg_sweep_u(mik_cg *it, const T *src, int64_t lo, int64_t len, bool vec, int hints)
+{
+    CgDev<T> *d = (CgDev<T> *)it->dev;
+    T *x = (T *)it->x, *u = (T *)it->u;
+    if (it->fuse_x) {
+        OpXpbyX<T> op{src + lo, u + lo, x + lo, coef_ptr<T>(&d->beta), coef_ptr<T>(&d->alpha), &d->done, &d->x_pending, hints};
+        return launch_map<T>(it->ctx, len, op, vec, (T *)nullptr, (const int *)nullptr);
+    }
+    OpXpby<T> op{src + lo, u + lo, coef_ptr<T>(&d->beta), hints};
+    return launch_map<T>(it->ctx, len, op, vec, (T *)nullptr, &d->done);
+}
+
+// x .+= alpha .* u (left to the next sweep over u with fuse_x); r .-= alpha .* c; local |r|^2 -> seg_vec      src/cg.jl:58-62
+// alpha: the stored scalar (coef_ptr) or, with fuse_x only, formed by the sweep from the ranks' dot(u, c) (CoefAlphaRanks)
+template <typename T, typename C> static int cg_update_xr(mik_cg *it, C alpha, bool vec)
+{
+    CgDev<T> *d = (CgDev<T> *)it->dev;
+    T *x = (T *)it->x, *u = (T *)it->u, *r = (T *)it->r, *c = (T *)it->c;
+    if (it->fuse_x) {
+        OpCgUpdateR<T, C> up{r, c, alpha, cg_stream_hints(it->ctx, true, it->A) >> 3};
+        return launch_map<T>(it->ctx, it->n, up, vec, (T *)it->seg_vec, &d->done);
+    }
+    if constexpr (std::is_same<C, Coef<T>>::value) {
+        OpCgUpdate<T> up{x, r, u, c, alpha, cg_stream_hints(it->ctx) >> 3};
+        return launch_map<T>(it->ctx, it->n, up, vec, (T *)it->seg_vec, &d->done);
+    }
+    return mik_fail(it->ctx, MIK_ERR_INVALID, "cg: alpha formed inside the sweep needs the x update on the next sweep over u");
+}
+
+template <typename T> __global__ void k_cg_clear_pending(CgDev<T> *d) { d->x_pending = 0; }
+
+// the x .+= alpha .* u that is still due when no sweep over u follows
+template <typename T> static int cg_flush_x(mik_cg *it)
+{
+    mik_ctx *ctx = it->ctx;
+    CgDev<T> *d = (CgDev<T> *)it->dev;
+    T *x = (T *)it->x, *u = (T *)it->u;
+    OpXFlush<T> op{u, x, coef_ptr<T>(&d->alpha), &d->x_pending};
+    MIK_TRY((launch_map<T>(ctx, it->n, op, mik_aligned16(x) && mik_aligned16(u), (T *)nullptr, (const int *)nullptr)));
+    hipLaunchKernelGGL((k_cg_clear_pending<T>), dim3(1), dim3(1), 0, ctx->stream, d);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
+// r = b - A x0 with the local |r|^2 -> seg_vec (src/cg.jl:130-138); x0 = the vector the operator is applied to, NULL: x is zero, r = b
+template <typename T> static int cg_init_residual(mik_cg *it, const T *x0, bool vec)
+{
+    mik_ctx *ctx = it->ctx;
+    T *c = (T *)it->c;
+    it->mv_products = x0 ? 1 : 0;                                         // :134 / :136
+    if (x0) {
+        if (it->A) MIK_TRY(mik_spmv_launch<T>(ctx, it->A, x0, c, false, nullptr, nullptr));   // :137
+        else if (it->op_mul(it->op_user, x0, c) != 0) return mik_fail(ctx, MIK_ERR_CALLBACK, "cg: the operator callback failed");
+    }
+    OpSubNrm<T> op{(const T *)it->b, x0 ? c : nullptr, (T *)it->r};       // copyto!(r, b) :130, r = b - c :138
+    return launch_map<T>(ctx, it->n, op, vec, (T *)it->seg_vec, nullptr);
+}
+
+// The HEAD of one iterate() (u = r + beta u [after c = Pl \ r, rho]; c = A u; alpha); cg_enqueue_tail is the other half
+// (cg_run_batch, csrc/mik_iter.h).  Behind a stop its kernels early-exit on the device's `done` flag.
 template <typename T> static int cg_enqueue_head(mik_cg *it)
 {
     mik_ctx *ctx = it->ctx;
     CgDev<T> *d = (CgDev<T> *)it->dev;
     const int *done = &d->done;
-    const int64_t n = it->n;
-    const int64_t nseg = mik_nseg<T>(n);
-    const int64_t nb = mik_spmv_nwg(n);
+    const int64_t n = it->n, nseg = mik_nseg<T>(n);
     T *x = (T *)it->x, *u = (T *)it->u, *r = (T *)it->r, *c = (T *)it->c;
     const bool vec = mik_aligned16(x) && mik_aligned16(u) && mik_aligned16(r) && mik_aligned16(c) && (!it->diag || mik_aligned16(it->diag));
     const int pcg = (it->diag || it->pl_fn) ? 1 : 0;
@@ -758,60 +822,27 @@ template <typename T> static int cg_enqueue_head(mik_cg *it)
         OpDot<T> dcr{c, r};
         MIK_TRY((launch_map<T>(ctx, n, dcr, vec, (T *)it->seg_vec, done)));
     }
-    if (pcg) {
-        if (!it->pcg_fused) {
-            hipLaunchKernelGGL((k_cg_fin_rho<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)it->seg_vec, nseg, d, (FinScratch<T> *)it->fin);
-            MIK_LAUNCH_CHECK(ctx);
-        }
-        // u .= c .+ beta .* u                                           src/cg.jl:86
+    if (pcg && !it->pcg_fused) {
+        hipLaunchKernelGGL((k_cg_fin_rho<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)it->seg_vec, nseg, d, (FinScratch<T> *)it->fin);
+        MIK_LAUNCH_CHECK(ctx);
+    }
+    {   // u .= r .+ beta .* u (src/cg.jl:50-51); PCG: u .= c .+ beta .* u (:86), and c = Pl \\ r is dead after this sweep: streamed
         CgProfileScope ps(it, 1);
-        if (it->fuse_x) {
-            OpXpbyX<T> op{c, u, x, coef_ptr<T>(&d->beta), coef_ptr<T>(&d->alpha), done, &d->x_pending, (cg_stream_hints(ctx, true, it->A) & 8) | 1};   // c = Pl \\ r is dead after this sweep: streamed
-            MIK_TRY((launch_map<T>(ctx, n, op, vec, (T *)nullptr, (const int *)nullptr)));
-        } else {
-            OpXpby<T> op{c, u, coef_ptr<T>(&d->beta), cg_stream_hints(ctx) & 1};   // c = Pl \\ r is dead after this sweep
-            MIK_TRY((launch_map<T>(ctx, n, op, vec, (T *)nullptr, done)));
-        }
-    } else {
-        // u .= r .+ beta .* u                                           src/cg.jl:50-51
-        CgProfileScope ps(it, 1);
-        if (it->fuse_x) {   // ... and x .+= alpha .* u of the previous step, on the u this sweep reads anyway (OpXpbyX)
-            OpXpbyX<T> op{r, u, x, coef_ptr<T>(&d->beta), coef_ptr<T>(&d->alpha), done, &d->x_pending, cg_stream_hints(ctx, true, it->A) & 15};
-            MIK_TRY((launch_map<T>(ctx, n, op, vec, (T *)nullptr, (const int *)nullptr)));
-        } else {
-            OpXpby<T> op{r, u, coef_ptr<T>(&d->beta), cg_stream_hints(ctx) & 7};
-            MIK_TRY((launch_map<T>(ctx, n, op, vec, (T *)nullptr, done)));
-        }
+        const int pcg_hints = it->fuse_x ? (cg_stream_hints(ctx, true, it->A) & 8) | 1 : cg_stream_hints(ctx) & 1;
+        MIK_TRY(cg_sweep_u<T>(it, pcg ? c : r, 0, n, vec, pcg ? pcg_hints : cg_sweep_u_hints(it)));
     }
     // c = A * u with the dot(u, c) epilogue                             src/cg.jl:54-55
     if (it->A) {
-        {
-            CgProfileScope ps(it, 0);
-            const int rc_spmv = mik_spmv_launch<T>(ctx, it->A, u, c, true, (T *)it->seg_spmv, done);
-            MIK_TRY(rc_spmv);
-        }
-        hipLaunchKernelGGL((k_cg_fin_alpha<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)it->seg_spmv, nb, d, pcg, (FinScratch<T> *)it->fin);
+        CgProfileScope ps(it, 0);
+        MIK_TRY(mik_spmv_launch<T>(ctx, it->A, u, c, true, (T *)it->seg_spmv, done));
     } else {
         // any operator: mul!(c, A, u) through the callback; dot(u, c) as its own sweep with the vector tree shape
         if (it->op_mul(it->op_user, u, c) != 0) return mik_fail(ctx, MIK_ERR_CALLBACK, "cg: the operator callback failed");
         OpDot<T> duc{u, c};
         MIK_TRY((launch_map<T>(ctx, n, duc, vec, (T *)it->seg_vec, done)));
-        hipLaunchKernelGGL((k_cg_fin_alpha<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)it->seg_vec, nseg, d, pcg, (FinScratch<T> *)it->fin);
     }
-    MIK_LAUNCH_CHECK(ctx);
-    return MIK_OK;
-}
-
-template <typename T> __global__ void k_cg_clear_pending(CgDev<T> *d) { d->x_pending = 0; }
-
-template <typename T> static int cg_enqueue_xflush(mik_cg *it)
-{
-    mik_ctx *ctx = it->ctx;
-    CgDev<T> *d = (CgDev<T> *)it->dev;
-    T *x = (T *)it->x, *u = (T *)it->u;
-    OpXFlush<T> op{u, x, coef_ptr<T>(&d->alpha), &d->x_pending};
-    MIK_TRY((launch_map<T>(ctx, it->n, op, mik_aligned16(x) && mik_aligned16(u), (T *)nullptr, (const int *)nullptr)));
-    hipLaunchKernelGGL((k_cg_clear_pending<T>), dim3(1), dim3(1), 0, ctx->stream, d);
+    hipLaunchKernelGGL((k_cg_fin_alpha<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)(it->A ? it->seg_spmv : it->seg_vec), it->A ? mik_spmv_nwg(n) : nseg,
+                       d, pcg, (FinScratch<T> *)it->fin);
     MIK_LAUNCH_CHECK(ctx);
     return MIK_OK;
 }
@@ -821,8 +852,7 @@ template <typename T> static int cg_enqueue_tail(mik_cg *it, long long it_next, 
     mik_ctx *ctx = it->ctx;
     CgDev<T> *d = (CgDev<T> *)it->dev;
     const int *done = &d->done;
-    const int64_t n = it->n;
-    const int64_t nseg = mik_nseg<T>(n);
+    const int64_t n = it->n, nseg = mik_nseg<T>(n);
     T *x = (T *)it->x, *u = (T *)it->u, *r = (T *)it->r, *c = (T *)it->c;
     const bool vec = mik_aligned16(x) && mik_aligned16(u) && mik_aligned16(r) && mik_aligned16(c) && (!it->diag || mik_aligned16(it->diag));
     // x .+= alpha .* u; r .-= alpha .* c; norm(r)                       src/cg.jl:58-62
@@ -844,13 +874,7 @@ template <typename T> static int cg_enqueue_tail(mik_cg *it, long long it_next, 
     }
     {
         CgProfileScope ps(it, 2);
-        if (it->fuse_x) {
-            OpCgUpdateR<T> up{r, c, coef_ptr<T>(&d->alpha), cg_stream_hints(ctx, true, it->A) >> 3};
-            MIK_TRY((launch_map<T>(ctx, n, up, vec, (T *)it->seg_vec, done)));
-        } else {
-            OpCgUpdate<T> up{x, r, u, c, coef_ptr<T>(&d->alpha), cg_stream_hints(ctx) >> 3};
-            MIK_TRY((launch_map<T>(ctx, n, up, vec, (T *)it->seg_vec, done)));
-        }
+        MIK_TRY(cg_update_xr<T>(it, coef_ptr<T>(&d->alpha), vec));
     }
     it->seq += 1;
     hipLaunchKernelGGL((k_cg_fin_res<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)it->seg_vec, nseg, d, (T *)it->hist,
@@ -893,24 +917,12 @@ template <typename T>
 static int cg_init_impl(mik_cg *it, double abstol, double reltol, int initially_zero)
 {
     mik_ctx *ctx = it->ctx;
-    const int64_t n = it->n;
-    const int64_t nseg = mik_nseg<T>(n);
-    T *x = (T *)it->x, *u = (T *)it->u, *r = (T *)it->r, *c = (T *)it->c;
-    const T *b = (const T *)it->b;
+    const int64_t n = it->n, nseg = mik_nseg<T>(n);
+    T *u = (T *)it->u, *r = (T *)it->r, *c = (T *)it->c;
     OpFill<T> z{u, T(0)};                                                 // u .= 0          :129
     MIK_TRY((launch_map<T>(ctx, n, z, mik_aligned16(u), (T *)nullptr, nullptr)));
-    const bool vec = mik_aligned16(r) && mik_aligned16(b) && mik_aligned16(c);
-    if (initially_zero) {
-        it->mv_products = 0;                                              // :134
-        OpSubNrm<T> op{b, nullptr, r};                                    // copyto!(r, b)   :130
-        MIK_TRY((launch_map<T>(ctx, n, op, vec, (T *)it->seg_vec, nullptr)));
-    } else {
-        it->mv_products = 1;                                              // :136
-        if (it->A) MIK_TRY(mik_spmv_launch<T>(ctx, it->A, x, c, false, nullptr, nullptr));   // :137
-        else if (it->op_mul(it->op_user, x, c) != 0) return mik_fail(ctx, MIK_ERR_CALLBACK, "cg: the operator callback failed");
-        OpSubNrm<T> op{b, c, r};                                          // r = b - c       :130,138
-        MIK_TRY((launch_map<T>(ctx, n, op, vec, (T *)it->seg_vec, nullptr)));
-    }
+    const bool vec = mik_aligned16(r) && mik_aligned16(it->b) && mik_aligned16(c);
+    MIK_TRY(cg_init_residual<T>(it, initially_zero ? nullptr : (const T *)it->x, vec));
     hipLaunchKernelGGL((k_cg_fin_init<T>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)it->seg_vec, nseg,
                        (CgDev<T> *)it->dev, (T)reltol, (T)abstol, (long long)it->maxiter);
     MIK_LAUNCH_CHECK(ctx);
@@ -1032,6 +1044,50 @@ extern "C" int mik_cg_destroy(mik_cg *it)
     return MIK_OK;
 }
 
+// The ranks of cg_run_batch (csrc/mik_iter.h) for one single-GPU iterable.
+template <typename T> struct CgLocal {
+    mik_cg *it;
+    T res = T(0);                  // scaled_norm -> close_frozen
+    mik_cg &base() { return *it; }
+    int head(int64_t) { return cg_enqueue_head<T>(it); }
+    int tail(int64_t iteration, int64_t j) { return cg_enqueue_tail<T>(it, (long long)(iteration + 1), (int)j); }
+    int flush_x() { return cg_flush_x<T>(it); }
+    int wait(CgMirror *m) { MIK_TRY(cg_wait_mirror(it)); *m = *it->mirror; return MIK_OK; }
+    // nothing to do: every head clears the flag (k_cg_fin_alpha, before it looks at `done`), the one enqueued ahead included
+    int clear_pending() { return MIK_OK; }
+    int scaled_norm() { return mik_safe_norm_slow<T>(it->ctx, it->n, (const T *)it->r, &res); }
+    int close_frozen(int64_t it_next, int hist_index)
+    {
+        it->seq += 1;
+        hipLaunchKernelGGL((k_cg_fix_res<T>), dim3(1), dim3(1), 0, it->ctx->stream, (CgDev<T> *)it->dev, res, (T *)it->hist, (long long)it_next,
+                           (long long)it->maxiter, it->mirror, it->seq, hist_index, it->pcg_fused ? 1 : 0);
+        MIK_LAUNCH_CHECK(it->ctx);
+        return MIK_OK;
+    }
+    int collect(const CgMirror &m, double *, double *, double *residuals, int64_t, int64_t *steps_done)
+    {
+        mik_ctx *ctx = it->ctx;
+        const int64_t nd = m.nhist;
+        if (nd == 1) {
+            if (residuals) residuals[0] = m.res;
+        } else if (nd > 1) {
+            std::vector<T> tmp((size_t)nd);
+            MIK_HIP(ctx, hipMemcpyAsync(tmp.data(), it->hist, sizeof(T) * (size_t)nd, hipMemcpyDeviceToHost, ctx->stream));
+            MIK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (residuals) for (int64_t j = 0; j < nd; ++j) residuals[j] = (double)tmp[j];
+        }
+        if (nd > 0) {
+            it->residual = m.res;
+            it->prev_residual = m.prev_res;
+        }
+        it->dev_done = m.done != 0;
+        it->mv_products += nd;
+        *steps_done = nd;
+        if (it->profile) cg_profile_collect(it);
+        return MIK_OK;
+    }
+};
+
 template <typename T>
 static int cg_iterate_many_impl(mik_cg *it, int64_t iteration, int64_t max_steps, double *residuals, int64_t *steps_done)
 {
@@ -1062,60 +1118,17 @@ static int cg_iterate_many_impl(mik_cg *it, int64_t iteration, int64_t max_steps
         MIK_HIP(ctx, hipMalloc(&it->hist, sizeof(T) * (size_t)max_steps));
         it->hist_cap = max_steps;
     }
-    CgDev<T> *d = (CgDev<T> *)it->dev;
     // The device is idle here (the previous call waited for its last step), so the host may reset the
     // step counter in the host-mapped mirror directly.  The stopping flag only needs clearing if a previous
     // call left it set while the host test above said "not done" (e.g. the caller restarted the count).
     it->mirror->nhist = 0;
     it->mirror->range = 0;
-    if (it->dev_done) MIK_HIP(ctx, hipMemsetAsync(&d->done, 0, sizeof(int), ctx->stream));
-    CgMirror m;
+    if (it->dev_done) MIK_HIP(ctx, hipMemsetAsync(&((CgDev<T> *)it->dev)->done, 0, sizeof(int), ctx->stream));
     // the head of the step AFTER this call goes on the stream before the host waits (never with host callbacks, whose call
     // count the caller may observe; MIK_KNOB_NO_LOOKAHEAD: off)
     const bool ahead_ok = ctx->tuning[MIK_KNOB_NO_LOOKAHEAD] == 0 && !it->op_mul && !it->pl_fn && iteration + max_steps < it->maxiter;
-    for (int64_t j0 = 0;;) {
-        for (int64_t j = j0; j < max_steps; ++j) {
-            if (!it->head_ahead) MIK_TRY(cg_enqueue_head<T>(it));
-            it->head_ahead = false;
-            MIK_TRY(cg_enqueue_tail<T>(it, (long long)(iteration + j + 1), (int)j));
-        }
-        if (ahead_ok) MIK_TRY(cg_enqueue_head<T>(it));
-        else if (it->fuse_x) MIK_TRY(cg_enqueue_xflush<T>(it));         // no sweep over u follows: apply the last x .+= alpha .* u now
-        MIK_TRY(cg_wait_mirror(it));
-        m = *it->mirror;
-        if (!m.range) { it->head_ahead = ahead_ok && !m.done; break; }       // stopped: the head ahead was a no-op
-        it->head_ahead = false;                                              // frozen batch: so was everything behind the frozen step
-        // Step m.nhist of this call updated x and r, but |r|^2 left the range in which sqrt(sum of squares) is safe
-        // (include/mik.h "Norms"): the device froze the batch; finish that step with the scaled norm and go on.
-        T res;
-        MIK_TRY(mik_safe_norm_slow<T>(ctx, it->n, (const T *)it->r, &res));
-        it->seq += 1;
-        hipLaunchKernelGGL((k_cg_fix_res<T>), dim3(1), dim3(1), 0, ctx->stream, d, res, (T *)it->hist, (long long)(iteration + m.nhist + 1),
-                           (long long)it->maxiter, it->mirror, it->seq, (int)m.nhist, it->pcg_fused ? 1 : 0);
-        MIK_LAUNCH_CHECK(ctx);
-        MIK_TRY(cg_wait_mirror(it));
-        m = *it->mirror;
-        j0 = m.nhist;
-        if (m.done || j0 >= max_steps) break;
-    }
-    const int64_t nd = m.nhist;
-    if (nd == 1) {
-        if (residuals) residuals[0] = m.res;
-    } else if (nd > 1) {
-        std::vector<T> tmp((size_t)nd);
-        MIK_HIP(ctx, hipMemcpyAsync(tmp.data(), it->hist, sizeof(T) * (size_t)nd, hipMemcpyDeviceToHost, ctx->stream));
-        MIK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (residuals) for (int64_t j = 0; j < nd; ++j) residuals[j] = (double)tmp[j];
-    }
-    if (nd > 0) {
-        it->residual = m.res;
-        it->prev_residual = m.prev_res;
-    }
-    it->dev_done = m.done != 0;
-    it->mv_products += nd;
-    *steps_done = nd;
-    if (it->profile) cg_profile_collect(it);
-    return MIK_OK;
+    CgLocal<T> rk{it};
+    return cg_run_batch(rk, iteration, max_steps, ahead_ok, residuals, steps_done);
 }
 
 extern "C" int mik_cg_iterate_many(mik_cg *it, int64_t iteration, int64_t max_steps, double *residuals, int64_t *steps_done)
@@ -1530,7 +1543,7 @@ template <typename T> static int gm_fused_enqueue(mik_gmres *g, int k, int slot)
         else MIK_MGS_GO(VECV, GG);                                                                   \
     } while (0)
     if (g->mgs_res_S > 0) {
-        // the resident-w form: ceil(nseg / S) workgroups of 512 threads, one per compute unit (128 KB of LDS each)
+        // the resident-w form: ceil(nseg / S) workgroups of 512 threads, one per compute unit (144 KB of static LDS each)
         const int S = g->mgs_res_S, wgs = (nseg + S - 1) / S;
         hipLaunchKernelGGL((k_mgs_resident<T, 512, MIK_MGS_RES_RR, MIK_MGS_RES_RL>), dim3(wgs), dim3(512), 0, ctx->stream, n, k, (const T *)V, g->ldv, w, (T *)g->mgs_P, g->restart,
                            stride, nseg, S, g->mgs_parity, gm_mirror(g, slot), g->mgs_seq);
@@ -1788,14 +1801,7 @@ extern "C" int mik_gmres_state(const mik_gmres *g, double *residual, double *tol
 // host side (dist.py) runs the exchanges with torch.distributed (RCCL over xGMI on the GPU box,
 // gloo in the CPU tests) between the phases below; every phase only enqueues kernels.
 //
-//   phase 10  init A: (x given) copy x into u_ext, pack the halo send buffer
-//   phase 11  init B: r = b - A*u_ext (or r = b), local sum of r.^2 -> rr_all[rank]; u_ext = 0
-//   phase 12  init C: residual = sqrt(sum_p rr_all[p]), tol, beta; publish
-//   phase  0  step A: u = r + beta*u (src/cg.jl:51); pack the halo send buffer
-//   phase  1  step B: c = A_loc * u_ext with the local dot(u, c) -> dot_all[rank]   (:54-55)
-//   phase  2  step C: alpha = residual^2 / sum_p dot_all[p]; x += alpha*u; r -= alpha*c;
-//                     local sum of r.^2 -> rr_all[rank]                               (:55-59)
-//   phase  3  step D: residual = sqrt(sum_p rr_all[p]) (:62); beta; stopping test; publish
+// The phases: mik_cgd_phase_id (include/mik.h) and, for the library's own loops only, cgd_phase_internal (csrc/mik_iter.h).
 //
 // Cross-rank sums run in rank order 0..P-1 on every rank, so all ranks hold bit-identical
 // scalars and the history is reproducible (and equals the single-GPU path for P = 1).
@@ -1884,6 +1890,14 @@ template <typename T> __global__ void k_cgd_alpha(const T *__restrict__ dot_all,
     d->alpha = (d->res * d->res) / tot;
 }
 
+// the scalars of cg_init_scalars the host needs, into the mirror; one thread
+template <typename T> __device__ __forceinline__ void cgd_publish_init(const CgDev<T> *d, CgMirror *mirror, unsigned long long seq)
+{
+    mirror->res = (double)d->res; mirror->prev_res = 1.0; mirror->done = d->done; mirror->nhist = 0;
+    mirror->tol = (double)d->tol; mirror->tol_valid = 1;
+    __hip_atomic_store(&mirror->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 template <typename T>
 __global__ void k_cgd_fin_init(const T *__restrict__ rr_all, int nranks, CgDev<T> *d, T reltol, T abstol, long long maxiter, CgMirror *mirror,
                                unsigned long long seq)
@@ -1891,22 +1905,13 @@ __global__ void k_cgd_fin_init(const T *__restrict__ rr_all, int nranks, CgDev<T
     const T tot = rank_sum(rr_all, nranks);
     if (!mik_nrm_in_range(tot)) {
         // |r|^2 left the range of a safe sqrt(sum of squares) -- every rank sees the same total and takes this branch: the hosts
-        // recompute the norm with a common scale (phases 20-24) and finish the initialisation with k_cgd_fix_init
+        // recompute the norm with a common scale (CGD_NORM_*) and finish the initialisation with k_cgd_fix_init
         d->done = 1; mirror->done = 0; mirror->range = 1;
         __hip_atomic_store(&mirror->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         return;
     }
-    const T res = mik_sqrt(tot);
-    const T a = reltol * res;
-    d->rr = tot; d->res = res; d->prev_res = T(1); d->rho = T(1);
-    d->tol = a > abstol ? a : abstol;
-    d->beta = (res * res) / (T(1) * T(1));
-    d->alpha = T(0); d->dot_uc = T(0);
-    d->done = (0 >= maxiter || res <= d->tol) ? 1 : 0;
-    d->nhist = 0;
-    mirror->res = (double)res; mirror->prev_res = 1.0; mirror->done = d->done; mirror->nhist = 0;
-    mirror->tol = (double)d->tol; mirror->tol_valid = 1;
-    __hip_atomic_store(&mirror->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    cg_init_scalars(d, tot, mik_sqrt(tot), reltol, abstol, maxiter);
+    cgd_publish_init(d, mirror, seq);
 }
 
 template <typename T>
@@ -1921,17 +1926,9 @@ __global__ void k_cgd_fin_res(const T *__restrict__ rr_all, int nranks, CgDev<T>
 template <typename T>
 __global__ void k_cgd_fix_init(CgDev<T> *d, T res, T reltol, T abstol, long long maxiter, CgMirror *mirror, unsigned long long seq)
 {
-    const T a = reltol * res;
-    d->rr = res * res; d->res = res; d->prev_res = T(1); d->rho = T(1);
-    d->tol = a > abstol ? a : abstol;
-    d->beta = (res * res) / (T(1) * T(1));
-    d->alpha = T(0); d->dot_uc = T(0);
-    d->done = (0 >= maxiter || res <= d->tol) ? 1 : 0;
-    d->nhist = 0;
+    cg_init_scalars(d, res * res, res, reltol, abstol, maxiter);
     mirror->range = 0;
-    mirror->res = (double)res; mirror->prev_res = 1.0; mirror->done = d->done; mirror->nhist = 0;
-    mirror->tol = (double)d->tol; mirror->tol_valid = 1;
-    __hip_atomic_store(&mirror->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    cgd_publish_init(d, mirror, seq);
 }
 
 extern "C" int mik_cgd_create(mik_ctx *ctx, const mik_csr *A_loc, void *x, const void *b, void *u_ext, void *r, void *c,
@@ -2014,55 +2011,38 @@ template <typename T> static int cgd_phase_impl(mik_cgd *it, int phase, int64_t 
     const int *done = &d->done;
     const int64_t n = bs.n, nseg = mik_nseg<T>(n), nb = mik_spmv_nwg(n);
     T *x = (T *)bs.x, *u = (T *)it->u_ext, *r = (T *)bs.r, *c = (T *)bs.c;
-    const T *b = (const T *)bs.b;
     T *dot_slot = (T *)it->dot_all + it->rank, *rr_slot = (T *)it->rr_all + it->rank;
-    const bool vec = mik_aligned16(x) && mik_aligned16(u) && mik_aligned16(r) && mik_aligned16(c) && mik_aligned16(b);
+    const bool vec = mik_aligned16(x) && mik_aligned16(u) && mik_aligned16(r) && mik_aligned16(c) && mik_aligned16(bs.b);
     switch (phase) {
-    case 10:   // init A
+    case MIK_CGD_INIT_A:
         if (!it->initially_zero) {
             MIK_HIP(ctx, hipMemcpyAsync(u, x, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
             MIK_TRY(gather_launch<T>(ctx, it->n_send, it->send_idx, u, (T *)it->send_buf, nullptr));
         }
         return MIK_OK;
-    case 11: { // init B
-        if (it->initially_zero) {
-            bs.mv_products = 0;
-            OpSubNrm<T> op{b, nullptr, r};
-            MIK_TRY((launch_map<T>(ctx, n, op, vec, (T *)bs.seg_vec, nullptr)));
-        } else {
-            bs.mv_products = 1;
-            MIK_TRY(mik_spmv_launch<T>(ctx, bs.A, u, c, false, nullptr, nullptr));
-            OpSubNrm<T> op{b, c, r};
-            MIK_TRY((launch_map<T>(ctx, n, op, vec, (T *)bs.seg_vec, nullptr)));
-        }
+    case MIK_CGD_INIT_B: {
+        MIK_TRY(cg_init_residual<T>(&bs, it->initially_zero ? nullptr : u, vec));       // x (with its halo) is in u_ext
         hipLaunchKernelGGL((k_finalize_store<T>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)bs.seg_vec, nseg, (int64_t)0, rr_slot,
                            (const int *)nullptr);
         MIK_LAUNCH_CHECK(ctx);
         OpFill<T> z{u, T(0)};   // u .= 0 (src/cg.jl:129), halo included
         return launch_map<T>(ctx, it->n_ext, z, mik_aligned16(u), (T *)nullptr, nullptr);
     }
-    case 12:   // init C
+    case MIK_CGD_INIT_C:
         bs.seq += 1;
         hipLaunchKernelGGL((k_cgd_fin_init<T>), dim3(1), dim3(1), 0, ctx->stream, (const T *)it->rr_all, it->nranks, d, (T)it->reltol, (T)it->abstol,
                            (long long)bs.maxiter, bs.mirror, bs.seq);
         MIK_LAUNCH_CHECK(ctx);
         return MIK_OK;
-    case 0: {  // step A
-        if (bs.fuse_x) {   // ... with x .+= alpha .* u of the previous step on the u this sweep reads anyway (OpXpbyX)
-            OpXpbyX<T> op{r, u, x, coef_ptr<T>(&d->beta), coef_ptr<T>(&d->alpha), done, &d->x_pending, cg_stream_hints(ctx, true, bs.A) & 15};
-            MIK_TRY((launch_map<T>(ctx, n, op, vec, (T *)nullptr, (const int *)nullptr)));
-        } else {
-            OpXpby<T> op{r, u, coef_ptr<T>(&d->beta), cg_stream_hints(ctx) & 7};
-            MIK_TRY((launch_map<T>(ctx, n, op, vec, (T *)nullptr, done)));
-        }
+    case MIK_CGD_STEP_A:
+        MIK_TRY(cg_sweep_u<T>(&bs, r, 0, n, vec, cg_sweep_u_hints(&bs)));
         return gather_launch<T>(ctx, it->n_send, it->send_idx, u, (T *)it->send_buf, done);
-    }
-    case 7:    // step A, early part: u (and the pending x update) on the rows the neighbours need, then pack -- the halo leaves first
-    case 8: {  // step A, bulk: the same sweep on all other rows, while the halo is on the wire
+    case CGD_STEP_A_EARLY:
+    case CGD_STEP_A_BULK: {
         if (it->n_early <= 0) return mik_fail(ctx, MIK_ERR_INVALID, "mik_cgd_phase: no early rows (mik_cgd_set_halo_plan)");
         int64_t lo[3], hi[3];
         int nr = 0;
-        if (phase == 7) {
+        if (phase == CGD_STEP_A_EARLY) {
             for (int q = 0; q < it->n_early; ++q) { lo[nr] = it->early_a[q]; hi[nr] = it->early_b[q]; ++nr; }
         } else {
             int64_t at = 0;
@@ -2072,21 +2052,12 @@ template <typename T> static int cgd_phase_impl(mik_cgd *it, int phase, int64_t 
             }
             if (at < n) { lo[nr] = at; hi[nr] = n; ++nr; }
         }
-        for (int q = 0; q < nr; ++q) {
-            const int64_t o = lo[q], len = hi[q] - lo[q];
-            const bool v2 = vec && (o % VT<T>::W == 0);
-            if (bs.fuse_x) {
-                OpXpbyX<T> op{r + o, u + o, x + o, coef_ptr<T>(&d->beta), coef_ptr<T>(&d->alpha), done, &d->x_pending, cg_stream_hints(ctx, true, bs.A) & 15};
-                MIK_TRY((launch_map<T>(ctx, len, op, v2, (T *)nullptr, (const int *)nullptr)));
-            } else {
-                OpXpby<T> op{r + o, u + o, coef_ptr<T>(&d->beta), cg_stream_hints(ctx) & 7};
-                MIK_TRY((launch_map<T>(ctx, len, op, v2, (T *)nullptr, done)));
-            }
-        }
-        if (phase == 7) return gather_launch<T>(ctx, it->n_send, it->send_idx, u, (T *)it->send_buf, done);
+        for (int q = 0; q < nr; ++q)
+            MIK_TRY(cg_sweep_u<T>(&bs, r, lo[q], hi[q] - lo[q], vec && (lo[q] % VT<T>::W == 0), cg_sweep_u_hints(&bs)));
+        if (phase == CGD_STEP_A_EARLY) return gather_launch<T>(ctx, it->n_send, it->send_idx, u, (T *)it->send_buf, done);
         return MIK_OK;
     }
-    case 9: {  // step A, early part as one launch (every send index occurs once: mik_cgd_set_halo_plan)
+    case CGD_STEP_A_EARLY_MERGED: {
         if (it->n_early <= 0 || !it->early_merged) return mik_fail(ctx, MIK_ERR_INVALID, "mik_cgd_phase: no merged early part");
         const int grid = (int)std::min<int64_t>((it->n_send + MIK_BLOCK - 1) / MIK_BLOCK, mik_max_grid(ctx));
         hipLaunchKernelGGL((k_cgd_early<T>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, it->n_send, it->send_idx, (const T *)r, u, x, (const T *)&d->beta,
@@ -2094,30 +2065,28 @@ template <typename T> static int cgd_phase_impl(mik_cgd *it, int phase, int64_t 
         MIK_LAUNCH_CHECK(ctx);
         return MIK_OK;
     }
-    case 6: {  // the x update that is still due when no head follows (end of a call without look-ahead)
-        OpXFlush<T> op{u, x, coef_ptr<T>(&d->alpha), &d->x_pending};
-        MIK_TRY((launch_map<T>(ctx, n, op, mik_aligned16(x) && mik_aligned16(u), (T *)nullptr, (const int *)nullptr)));
-        hipLaunchKernelGGL((k_cg_clear_pending<T>), dim3(1), dim3(1), 0, ctx->stream, d);
+    case CGD_X_FLUSH: return cg_flush_x<T>(&bs);
+    case MIK_CGD_STEP_B:
+    case CGD_STEP_B_NOFIN:
+    case MIK_CGD_STEP_B_REST:        // the row-blocks before and after the interior range (all of them: STEP_B), then the local dot(u, c)
+    case CGD_STEP_B_REST_NOFIN: {
+        const bool rest = phase == MIK_CGD_STEP_B_REST || phase == CGD_STEP_B_REST_NOFIN;
+        {
+            CgProfileScope ps(&bs, 0);
+            if (rest) MIK_TRY(mik_spmv_launch_outside<T>(ctx, bs.A, u, c, true, (T *)bs.seg_spmv, done, (int)it->int_begin, (int)it->int_end));
+            else MIK_TRY(mik_spmv_launch<T>(ctx, bs.A, u, c, true, (T *)bs.seg_spmv, done));
+        }
+        if (phase == CGD_STEP_B_NOFIN || phase == CGD_STEP_B_REST_NOFIN) return MIK_OK;
+        hipLaunchKernelGGL((k_cgd_fin_slot<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)bs.seg_spmv, nb, dot_slot, done, (FinScratch<T> *)bs.fin);
         MIK_LAUNCH_CHECK(ctx);
         return MIK_OK;
     }
-    case 1:    // step B
-        { CgProfileScope ps(&bs, 0); MIK_TRY(mik_spmv_launch<T>(ctx, bs.A, u, c, true, (T *)bs.seg_spmv, done)); }
-        hipLaunchKernelGGL((k_cgd_fin_slot<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)bs.seg_spmv, nb, dot_slot, done, (FinScratch<T> *)bs.fin);
-        MIK_LAUNCH_CHECK(ctx);
-        return MIK_OK;
-    case 4:    // step B1: the row-blocks that reference no halo column -- runs while the halo is in flight
+    case MIK_CGD_STEP_B_INTERIOR:    // the row-blocks that reference no halo column -- runs while the halo is in flight
         if (it->int_end <= it->int_begin) return mik_fail(ctx, MIK_ERR_INVALID, "mik_cgd_phase: no interior range set (mik_cgd_set_interior)");
         { CgProfileScope ps(&bs, 0); return mik_spmv_launch_range<T>(ctx, bs.A, u, c, true, (T *)bs.seg_spmv, done, (int)it->int_begin, (int)(it->int_end - it->int_begin)); }
-    case 5:    // step B2: the row-blocks before and after the interior range, then the local dot(u, c) as in step B
-        { CgProfileScope ps(&bs, 0); MIK_TRY(mik_spmv_launch_outside<T>(ctx, bs.A, u, c, true, (T *)bs.seg_spmv, done, (int)it->int_begin, (int)it->int_end)); }
-        hipLaunchKernelGGL((k_cgd_fin_slot<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)bs.seg_spmv, nb, dot_slot, done, (FinScratch<T> *)bs.fin);
-        MIK_LAUNCH_CHECK(ctx);
-        return MIK_OK;
-    case 2: {  // step C
+    case MIK_CGD_STEP_C: {
         if (bs.fuse_x && (ctx->tuning[MIK_KNOB_CG_STEP] & 8) == 0) {   // alpha inside the sweep, its bookkeeping inside the finaliser (MIK_KNOB_CG_STEP bit 3: the separate k_cgd_alpha)
-            OpCgUpdateR<T, CoefAlphaRanks<T>> up{r, c, CoefAlphaRanks<T>{(const T *)it->dot_all, it->nranks, &d->res}, cg_stream_hints(ctx, true, bs.A) >> 3};
-            MIK_TRY((launch_map<T>(ctx, n, up, vec, (T *)bs.seg_vec, done)));
+            MIK_TRY(cg_update_xr<T>(&bs, CoefAlphaRanks<T>{(const T *)it->dot_all, it->nranks, &d->res}, vec));
             hipLaunchKernelGGL((k_cgd_fin_slot_alpha<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)bs.seg_vec, nseg, rr_slot, done,
                                (FinScratch<T> *)bs.fin, (const T *)it->dot_all, it->nranks, d);
             MIK_LAUNCH_CHECK(ctx);
@@ -2125,18 +2094,12 @@ template <typename T> static int cgd_phase_impl(mik_cgd *it, int phase, int64_t 
         }
         hipLaunchKernelGGL((k_cgd_alpha<T>), dim3(1), dim3(1), 0, ctx->stream, (const T *)it->dot_all, it->nranks, d);
         MIK_LAUNCH_CHECK(ctx);
-        if (bs.fuse_x) {
-            OpCgUpdateR<T> up{r, c, coef_ptr<T>(&d->alpha), cg_stream_hints(ctx, true, bs.A) >> 3};
-            MIK_TRY((launch_map<T>(ctx, n, up, vec, (T *)bs.seg_vec, done)));
-        } else {
-            OpCgUpdate<T> up{x, r, u, c, coef_ptr<T>(&d->alpha), cg_stream_hints(ctx) >> 3};
-            MIK_TRY((launch_map<T>(ctx, n, up, vec, (T *)bs.seg_vec, done)));
-        }
+        MIK_TRY(cg_update_xr<T>(&bs, coef_ptr<T>(&d->alpha), vec));
         hipLaunchKernelGGL((k_cgd_fin_slot<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)bs.seg_vec, nseg, rr_slot, done, (FinScratch<T> *)bs.fin);
         MIK_LAUNCH_CHECK(ctx);
         return MIK_OK;
     }
-    case 3:    // step D
+    case MIK_CGD_STEP_D:
         if (it->hist_total >= bs.hist_cap) return mik_fail(ctx, MIK_ERR_INVALID, "mik_cgd_phase: more than %lld steps enqueued without mik_cgd_wait", (long long)bs.hist_cap);
         it->hist_total += 1;
         bs.seq += 1;
@@ -2144,7 +2107,7 @@ template <typename T> static int cgd_phase_impl(mik_cgd *it, int phase, int64_t 
                            (long long)(iteration + 1), (long long)bs.maxiter, bs.mirror, bs.seq, (int)(it->hist_total - 1), bs.fuse_x ? 1 : 0);
         MIK_LAUNCH_CHECK(ctx);
         return MIK_OK;
-    case 20: {  // scaled norm of r over the partition, pass 1: this rank's max |r_i| -> rr_all[rank]   (mik_safe_norm_slow, per rank)
+    case CGD_NORM_AMAX: {          // (mik_safe_norm_slow, per rank)
         const int grid = (int)std::min<int64_t>((std::max<int64_t>(n, 1) + MIK_BLOCK - 1) / MIK_BLOCK, 1024);
         MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * (size_t)std::max<int64_t>(std::max<int64_t>(nseg, grid), 1)));
         hipLaunchKernelGGL((k_amax<T>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, (const T *)r, (T *)ctx->partials);
@@ -2153,7 +2116,7 @@ template <typename T> static int cgd_phase_impl(mik_cgd *it, int phase, int64_t 
         MIK_LAUNCH_CHECK(ctx);
         return MIK_OK;
     }
-    case 22: {  // pass 2: this rank's tree sum of (r_i * s)^2, s = the common power of two (it->norm_scale) -> rr_all[rank]
+    case CGD_NORM_SCALED_SQ: {
         MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * (size_t)std::max<int64_t>(nseg, 1)));
         OpScaledSq<T> op{(const T *)r, (T)it->norm_scale};
         MIK_TRY((launch_map<T>(ctx, n, op, mik_aligned16(r), (T *)ctx->partials, nullptr)));
@@ -2162,34 +2125,19 @@ template <typename T> static int cgd_phase_impl(mik_cgd *it, int phase, int64_t 
         MIK_LAUNCH_CHECK(ctx);
         return MIK_OK;
     }
-    case 23:    // the frozen step closes with the scaled norm (it->norm_res), as k_cg_fix_res does on one GPU
+    case CGD_FIX_STEP:
         bs.seq += 1;
         it->hist_total = it->norm_fix_index + 1;
         hipLaunchKernelGGL((k_cg_fix_res<T>), dim3(1), dim3(1), 0, ctx->stream, d, (T)it->norm_res, (T *)bs.hist, (long long)it->norm_it_next,
                            (long long)bs.maxiter, bs.mirror, bs.seq, it->norm_fix_index);
         MIK_LAUNCH_CHECK(ctx);
         return MIK_OK;
-    case 13: {  // step B2 without the finaliser (the mailbox transport finalises and exchanges in one kernel: csrc/mik_comm.hip)
-        CgProfileScope ps(&bs, 0);
-        return mik_spmv_launch_outside<T>(ctx, bs.A, u, c, true, (T *)bs.seg_spmv, done, (int)it->int_begin, (int)it->int_end);
-    }
-    case 14: {  // step B without the finaliser
-        CgProfileScope ps(&bs, 0);
-        return mik_spmv_launch<T>(ctx, bs.A, u, c, true, (T *)bs.seg_spmv, done);
-    }
-    case 16: {  // step C without alpha formation and without the finaliser: alpha is the stored scalar (k_cgd_fin_dot_mail)
-        if (bs.fuse_x) {
-            OpCgUpdateR<T> up{r, c, coef_ptr<T>(&d->alpha), cg_stream_hints(ctx, true, bs.A) >> 3};
-            return launch_map<T>(ctx, n, up, vec, (T *)bs.seg_vec, done);
-        }
-        OpCgUpdate<T> up{x, r, u, c, coef_ptr<T>(&d->alpha), cg_stream_hints(ctx) >> 3};
-        return launch_map<T>(ctx, n, up, vec, (T *)bs.seg_vec, done);
-    }
-    case 25:    // the pending x update of a frozen step has been applied (by a no-op head, the head ahead or phase 6): drop the flag
+    case CGD_STEP_C_NOFIN: return cg_update_xr<T>(&bs, coef_ptr<T>(&d->alpha), vec);
+    case CGD_CLEAR_PENDING:      // (applied by a no-op head, the head ahead or CGD_X_FLUSH)
         hipLaunchKernelGGL((k_cg_clear_pending<T>), dim3(1), dim3(1), 0, ctx->stream, d);
         MIK_LAUNCH_CHECK(ctx);
         return MIK_OK;
-    case 24:    // cg_iterator! closes with the scaled norm
+    case CGD_FIX_INIT:
         bs.seq += 1;
         hipLaunchKernelGGL((k_cgd_fix_init<T>), dim3(1), dim3(1), 0, ctx->stream, d, (T)it->norm_res, (T)it->reltol, (T)it->abstol, (long long)bs.maxiter,
                            bs.mirror, bs.seq);
@@ -2256,7 +2204,7 @@ extern "C" int mik_cgd_wait(mik_cgd *it, double *residual, double *tol, int *don
     if (m.range) {
         mik_ctx *ctx = it->base.ctx;
         if (it->base.fuse_x && it->initialised) {              // the frozen step's x .+= alpha .* u must not stay pending
-            (void)mik_cgd_phase(it, 6, 0);
+            (void)mik_cgd_phase(it, CGD_X_FLUSH, 0);
             (void)mik_wait(ctx);
         }
         return mik_fail(ctx, MIK_ERR_RANGE, "cg (row-partitioned, host-driven phases): |r|^2 left the range of a safe norm; use mik_cgd_init / "

@@ -7,6 +7,10 @@ import numpy as np
 import scipy.sparse as sp
 import torch
 
+# the phases this double implements (mik_cgd_phase_id, include/mik.h; tests/test_abi.py checks the values)
+INIT_A, INIT_B, INIT_C = 10, 11, 12
+STEP_A, STEP_B, STEP_C, STEP_D = 0, 1, 2, 3
+
 
 class NumpyEngine:
     def __init__(self, orc, ptr, local_idx, val, plan, b_loc, x_loc=None, *, abstol, reltol, maxiter, shape=(1, 1, 2, 2)):
@@ -53,11 +57,11 @@ class NumpyEngine:
     def phase(self, ph, iteration=0):
         n, p = self.plan.n_loc, self.plan
         Wd, Ld, W, L = self.shape
-        if ph == 10:
+        if ph == INIT_A:
             if not self.initially_zero:
                 self._u[:n] = self.x
                 self._send[:p.n_send] = self._u[p.send_idx]
-        elif ph == 11:
+        elif ph == INIT_B:
             if self.initially_zero:
                 self.r[:] = self.b
             else:
@@ -65,7 +69,7 @@ class NumpyEngine:
                 self.r[:] = self.b - self.c
             self._rr[p.rank] = self.orc.dot(self.r, self.r, "tree", W, L)
             self._u[:] = 0
-        elif ph == 12:
+        elif ph == INIT_C:
             self.res = float(np.sqrt(self._ranksum(self._rr)))
             self.prev = 1.0
             self.tol = max(self.reltol * self.res, self.abstol)
@@ -74,18 +78,18 @@ class NumpyEngine:
             self.hist = []
         elif self.done:
             return
-        elif ph == 0:
+        elif ph == STEP_A:
             self._u[:n] = self.r + self.beta * self._u[:n]
             self._send[:p.n_send] = self._u[p.send_idx]
-        elif ph == 1:
+        elif ph == STEP_B:
             self.c[:] = self._spmv()
             self._dot[p.rank] = self.orc.dot(self._u[:n].copy(), self.c, "tree", Wd, Ld)
-        elif ph == 2:
+        elif ph == STEP_C:
             self.alpha = (self.res * self.res) / self._ranksum(self._dot)
             self.x += self.alpha * self._u[:n]
             self.r -= self.alpha * self.c
             self._rr[p.rank] = self.orc.dot(self.r, self.r, "tree", W, L)
-        elif ph == 3:
+        elif ph == STEP_D:
             prev = self.res
             self.res = float(np.sqrt(self._ranksum(self._rr)))
             self.prev = prev

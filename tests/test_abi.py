@@ -37,6 +37,21 @@ def test_development_knob_table_is_small_named_and_every_knob_is_referenced_by_a
         assert used, f"development knob MIK_KNOB_{name} is not referenced by any test"
 
 
+def test_python_phase_constants_equal_the_header_enum(pkg):
+    """mik_cgd_phase_id (include/mik.h) names the phases a host may drive; dist.py and the CPU double tests/dist_double.py cannot include
+    the header, so their constants are checked against it here."""
+    import importlib
+    import dist_double
+    dist = importlib.import_module(pkg.__name__ + ".dist")
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = re.search(r"enum\s+mik_cgd_phase_id\s*\{(.*?)\}", src, flags=re.S).group(1)
+    enum = {m.group(1): int(m.group(2)) for m in re.finditer(r"MIK_CGD_([A-Z_]+)\s*=\s*(\d+)", body)}
+    assert sorted(enum.values()) == [0, 1, 2, 3, 4, 5, 10, 11, 12] and len(enum) == 9
+    assert {k: getattr(dist, k) for k in enum} == enum
+    mirrored = {k: v for k, v in vars(dist_double).items() if re.fullmatch(r"(INIT|STEP)_[A-Z_]+", k)}
+    assert len(mirrored) == 7 and all(enum[k] == v for k, v in mirrored.items())
+
+
 def test_header_declares_something():
     syms = declared_symbols()
     assert "mik_spmv" in syms and "mik_cg_iterate" in syms and "mik_gmres_iterate" in syms and len(syms) >= 35
