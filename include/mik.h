@@ -649,6 +649,33 @@ int mik_forward_sub(mik_stationary *S, const void *alpha, void *x, const void *b
 /* backward_sub!(F, x) -- :109-124; backward_sub!(alpha, F, x, beta, y) -- :126-142.  As mik_forward_sub. */
 int mik_backward_sub(mik_stationary *S, const void *alpha, void *x, const void *beta, const void *y, int scalar_dtype);
 
+/* ---- svdl: Golub-Kahan-Lanczos bidiagonalisation with thick restart (src/svdl.jl) ------------------------------------------
+ * The Lanczos loop of extend! (:542-609) runs on mik_spmv (A and its adjoint as two operators), mik_gemv_t / mik_gemv_n and the fused
+ * sweeps above; the k x k SVD of a restart stays on the host.  Two things no entry above does in one pass (added without a version bump,
+ * additive): */
+/* Y[:, 0:l] = V[:, 0:k] * F[0:k, 0:l] -- the basis rotations of the restarts, view(L.Q, :, 1:k) * view(F.V, :, 1:l) and
+ * view(L.P, :, 1:k) * view(F.U, :, 1:l) (src/svdl.jl:384, :392), L.Q * view(Q, :, 1:k+1) and L.P * view(U, :, 1:k) (:470, :471), and the
+ * singular vectors (:231, :237).  V, Y: DEVICE, column-major, leading dimensions ldv / ldy in elements; F: HOST, column-major k x l with
+ * leading dimension ldf, of `dtype` (read before the call returns).  Exactly
+ *   Y[i, j] = (...((V[i, 0] * F[0, j]) + V[i, 1] * F[1, j]) + ...) + V[i, k-1] * F[k-1, j],
+ * columns ascending, every product and every sum rounded on its own (no FMA, no matrix cores): an element depends on its own row
+ * only, so the result is independent of the launch shape and equal to the loop `acc = V[:, 0] * F[0, j]; acc = acc + V[:, c] * F[c, j]`
+ * bit for bit.  One pass: every element of V is read once (twice when l > 32) and every element of Y written once.
+ * 1 <= l <= k <= 64, else MIK_ERR_NOTIMPL; Y must not overlap V (MIK_ERR_INVALID).  Asynchronous on the ctx stream. */
+int mik_basis_rotate(mik_ctx *ctx, int dtype, int64_t n, int k, int l, const void *V, int64_t ldv, const void *F, int64_t ldf,
+                     void *Y, int64_t ldy);
+/* The re-orthogonalisation of a new Lanczos vector and its normalisation -- src/svdl.jl:567-577 (right vectors; :587-597 for the left ones):
+ *   old = norm(q); q -= Q * (Q' q); if norm(q) <= alpha * old: q -= Q * (Q' q); beta = norm(q); q .*= inv(beta)
+ * Q: DEVICE n x k basis (leading dimension ldq); q: DEVICE n-vector, updated in place; alpha, beta_out: HOST scalars of `dtype`;
+ * *passes_out: 1 or 2, the Gram-Schmidt passes that ran.  Bit-identical to issuing mik_nrm2, mik_gemv_t, mik_gemv_n (alpha = -1), mik_nrm2, the
+ * comparison on the host in `dtype`, (mik_gemv_t, mik_gemv_n, mik_nrm2), mik_scal by 1 / beta one after another, the scaled recomputation
+ * of "Norms" included -- but a pass is two sweeps: the squared norm of q rides on the projection sweep (before) and on the update
+ * sweep (after), through the same fixed tree, so Q is read twice per pass and q is not swept for its norms; the closing scaling is one
+ * more sweep over q (the norm it divides by is only complete when the update sweep has ended).  k = 0: norm and scaling only.
+ * beta == 0 is returned as it is and q is then left unscaled (the reference divides by zero).  Synchronises. */
+int mik_svdl_reorth(mik_ctx *ctx, int dtype, int64_t n, int k, const void *Q, int64_t ldq, void *q, const void *alpha, void *beta_out,
+                    int *passes_out);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Time `reps` back-to-back launches of the SpMV (optionally with the fused dot epilogue used by
  * the CG step) with HIP events on the ctx stream; returns average milliseconds per launch. */

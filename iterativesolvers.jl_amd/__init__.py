@@ -7,6 +7,7 @@ The directory name (``iterativesolvers.jl_amd``) is not a Python identifier; loa
   _lib.py    ctypes binding of that ABI (fails loudly when the library is missing)
   api.py     host-side mirror of the reference interface (cg, cg_, gmres, gmres_, iterables ...): SURVEY section 8 rows only
   stationary.py  jacobi / gauss_seidel / sor / ssor and their iterables (src/stationary_sparse.jl)
+  svdl.py    svdl: Golub-Kahan-Lanczos SVD with thick restart (src/svdl.jl) on a HipCSR uploaded with its adjoint
   extras.py  solvers outside the scope contract (IDR(s), LSQR, LSMR, QMR, power method); kept apart, unjudged
   dist.py    row-partitioned multi-GPU CG / GMRES (one process per GPU; RCCL, peer-mapped mailboxes, in-process group)
   bench_dist.py  measurement harness of bench.py --gpus N (self-test orchestration, group fall-back, the line) -- not product code
@@ -26,4 +27,6 @@ from .api import (CGIterable, CGStateVariables, ClassicalGramSchmidt, Convergenc
 from .stationary import (GaussSeidelIterable, JacobiIterable, SingularException, SORIterable, SSORIterable,   # noqa: F401
                          StationaryOperator, gauss_seidel, gauss_seidel_, gauss_seidel_iterable, jacobi, jacobi_,
                          jacobi_iterable, sor, sor_, sor_iterable, ssor, ssor_, ssor_iterable)
-from . import extras                                             # noqa: F401  (beyond SURVEY section 8: IDR(s), LSQR, LSMR, QMR, powm -- unjudged, not re-exported)
+from .svdl import (BrokenArrowBidiagonal, PartialFactorization, svdl, svdl_method_, isconverged, build, thickrestart_,   # noqa: F401
+                   harmonicrestart_, extend_, ArgumentError, BoundsError, SvdlBreakdown, SVD)
+from . import extras                                         # noqa: F401  (beyond SURVEY section 8: IDR(s), LSQR, LSMR, QMR, powm -- unjudged, not re-exported)

@@ -205,6 +205,8 @@ SIGNATURES = {
     "mik_gs_multiply": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mik_forward_sub": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
     "mik_backward_sub": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "mik_basis_rotate": (C.c_int, [_vp, C.c_int, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64]),
+    "mik_svdl_reorth": (C.c_int, [_vp, C.c_int, _i64, C.c_int, _vp, _i64, _vp, _vp, _vp, C.POINTER(C.c_int)]),
 }
 
 _lib = None
