@@ -259,3 +259,59 @@ def test_long_row_shape_stays_inside_the_error_bound_of_the_sequential_loop(orc,
     err_seq = np.abs(yseq[long_rows].astype(np.longdouble) - exact).astype(np.float64)
     assert np.all(err_wave <= bound) and np.all(err_seq <= bound)
     assert np.sqrt(np.mean((err_wave / mag) ** 2)) <= np.sqrt(np.mean((err_seq / mag) ** 2))
+
+
+# ---- the oracle's tree at the sizes of tests/test_gpu_large_reductions.py, against a sum that shares no code with it ------------------
+_BASE = {}
+
+
+def ladder_vectors(dtype, n):
+    """two fixed pseudo-random vectors, generated once per dtype at the ladder's largest size and sliced"""
+    if dtype not in _BASE:
+        from ladder import ladder
+        W, L = (2, 2) if dtype == np.float64 else (4, 2)
+        top = max(nn for _, nn, _ in ladder(W, L, 8192).values())
+        rng = np.random.default_rng(20240229)
+        _BASE[dtype] = (top, rng.standard_normal(top, dtype=dtype), rng.standard_normal(top, dtype=dtype))
+    top, x, y = _BASE[dtype]
+    assert n <= top
+    return x[:n], y[:n]
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("rung", ["m1024", "m1025", "batch8_minus1", "batch8_plus500", "cap_plus1", "two_cap_plus37", "batch32_minus524",
+                                  "batch32_plus517", "control_16k"])
+def test_tree_oracle_at_the_large_ladder_stays_inside_the_derived_bound(orc, pkg, dtype, rung):
+    """orc.dot / orc.nrm2 in TREE mode were written to mirror the device, so a mistake both share at large segment counts would cancel out
+    in the GPU suite's bit comparison.  Here the tree is held against the exact sum of the exact products (ladder.exact_dot: math.fsum on the
+    two rungs around m = 1024, numpy's pairwise np.longdouble sums -- at most 64 roundings of 2^-64, checked against math.fsum on those two
+    rungs -- on the larger ones, where math.fsum takes 5 to 11 s per sum).  The tolerance is derived: along any path the tree adds at most
+    D = W*L + 6 + 3 + ceil(m/1024) + 6 + 15 times (ladder.depth), the product is one more rounding, so
+    |tree - exact| <= gamma_{D+1} * sum |x_i y_i| with gamma_k = k eps / (1 - k eps), eps = eps(dtype); for the norm the same bound through the
+    square root (ladder.nrm_bound).  (W, L) is what mik_reduce_shape reports; the grid cap is that of a 256-CU MI355X, 32 * 256 -- no device is
+    needed, and none is asked.  That every ladder size can be allocated on the host is checked by allocating it."""
+    import ctypes as C
+    from ladder import depth, dot_bound, exact_dot, ladder, nrm_bound
+    w, l = C.c_int(), C.c_int()
+    assert pkg.lib().mik_reduce_shape(pkg._lib.dtype_code(dtype), C.byref(w), C.byref(l)) == 0
+    W, L = w.value, l.value
+    m, n, what = ladder(W, L, 8192)[rung]
+    try:
+        x, y = ladder_vectors(dtype, n)
+    except MemoryError:
+        pytest.fail(f"the host cannot allocate the ladder's vectors of {n} {np.dtype(dtype).name} elements")
+    D = depth(W, L, m)
+    assert D == W * L + 6 + 3 + -(-m // 1024) + 6 + 15
+    ld = np.longdouble
+    small = rung in ("m1024", "m1025")
+    d = orc.dot(x, y, "tree", W, L)
+    s, a, err = exact_dot(x, y, use_fsum=small)
+    print(f"{np.dtype(dtype).name} {rung}: m={m} n={n} D={D} [{what}]  |dot - exact| = {float(abs(ld(d) - s)):.3e}  bound {float(dot_bound(W, L, m, dtype, a, err)):.3e}")
+    assert abs(ld(d) - s) <= dot_bound(W, L, m, dtype, a, err)
+    nr = orc.nrm2(x, "tree", W, L)
+    s2, a2, err2 = exact_dot(x, x, use_fsum=small)
+    print(f"    |nrm2 - exact| = {float(abs(ld(nr) - np.sqrt(s2))):.3e}  bound {float(nrm_bound(W, L, m, dtype, s2, err2)):.3e}")
+    assert abs(ld(nr) - np.sqrt(s2)) <= nrm_bound(W, L, m, dtype, s2, err2)
+    if small:                                            # the cheaper reference of the larger rungs, held against math.fsum where both are affordable
+        sp, ap, errp = exact_dot(x, y)
+        assert abs(sp - s) <= errp + err and ap == a
