@@ -8,6 +8,7 @@ The directory name (``iterativesolvers.jl_amd``) is not a Python identifier; loa
   api.py     host-side mirror of the reference interface (cg, cg_, gmres, gmres_, iterables ...): SURVEY section 8 rows only
   stationary.py  jacobi / gauss_seidel / sor / ssor and their iterables (src/stationary_sparse.jl)
   svdl.py    svdl: Golub-Kahan-Lanczos SVD with thick restart (src/svdl.jl) on a HipCSR uploaded with its adjoint
+  lobpcg.py  lobpcg: block eigensolver (src/lobpcg.jl) on HipCSR operators, every sweep on a block of columns
   extras.py  solvers outside the scope contract (IDR(s), LSQR, LSMR, QMR, power method); kept apart, unjudged
   dist.py    row-partitioned multi-GPU CG / GMRES (one process per GPU; RCCL, peer-mapped mailboxes, in-process group)
   bench_dist.py  measurement harness of bench.py --gpus N (self-test orchestration, group fall-back, the line) -- not product code
@@ -29,4 +30,5 @@ from .stationary import (GaussSeidelIterable, JacobiIterable, SingularException,
                          jacobi_iterable, sor, sor_, sor_iterable, ssor, ssor_, ssor_iterable)
 from .svdl import (BrokenArrowBidiagonal, PartialFactorization, svdl, svdl_method_, isconverged, build, thickrestart_,   # noqa: F401
                    harmonicrestart_, extend_, ArgumentError, BoundsError, SvdlBreakdown, SVD)
-from . import extras                                         # noqa: F401  (beyond SURVEY section 8: IDR(s), LSQR, LSMR, QMR, powm -- unjudged, not re-exported)
+from .lobpcg import (LOBPCGIterator, LOBPCGResults, LOBPCGState, LobpcgCholeskyError, LobpcgRefusal, lobpcg, lobpcg_)   # noqa: F401
+from . import extras                                      # noqa: F401  (beyond SURVEY section 8: IDR(s), LSQR, LSMR, QMR, powm -- unjudged, not re-exported)

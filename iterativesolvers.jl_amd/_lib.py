@@ -207,6 +207,10 @@ SIGNATURES = {
     "mik_backward_sub": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
     "mik_basis_rotate": (C.c_int, [_vp, C.c_int, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64]),
     "mik_svdl_reorth": (C.c_int, [_vp, C.c_int, _i64, C.c_int, _vp, _i64, _vp, _vp, _vp, C.POINTER(C.c_int)]),
+    "mik_spmm": (C.c_int, [_vp, _vp, C.c_int, _vp, _i64, _vp, _i64]),
+    "mik_block_gram": (C.c_int, [_vp, C.c_int, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64]),
+    "mik_block_rdiv": (C.c_int, [_vp, C.c_int, _i64, C.c_int, _vp, _i64, _vp, _i64]),
+    "mik_block_update": (C.c_int, [_vp, C.c_int, _i64, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
 }
 
 _lib = None

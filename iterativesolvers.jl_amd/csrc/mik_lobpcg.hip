@@ -1,0 +1,210 @@
+// mik_lobpcg.hip -- the four block entries lobpcg (src/lobpcg.jl) needs beyond the vector entries of mik_core.hip / mik_krylov.hip:
+//   mik_spmm           Y = A * X for a block of columns, the operator read once per column block
+//   mik_block_gram     G = X' * Y, every entry with the bits of mik_dot
+//   mik_block_rdiv     X <- X * inv(R), R upper triangular (CholQR)
+//   mik_block_update   the Ritz update of one block triple in one pass
+// Kernels: csrc/mik_lobpcg.h.  Nothing an existing entry launches is touched.
+#include <algorithm>
+#include <vector>
+
+#include "mik_lobpcg.h"
+
+namespace {
+
+bool blk_overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
+size_t blk_bytes(size_t es, int64_t n, int cols, int64_t ld)
+{
+    return (n > 0 && cols > 0) ? es * ((size_t)(cols - 1) * (size_t)ld + (size_t)n) : 0;
+}
+
+// A small host matrix (rows x cols, leading dimension ldm), packed to leading dimension `rows`, at the head of ctx->partials.  Through the
+// context's pinned staging area when it fits, else straight from a packed copy with a wait: either way the caller's array has been read
+// when this returns.
+template <typename T>
+int blk_stage(mik_ctx *ctx, const T *M, int rows, int cols, int64_t ldm, T **dev_out)
+{
+    const size_t bytes = sizeof(T) * (size_t)rows * (size_t)cols;
+    MIK_TRY(mik_ensure_partials(ctx, bytes));
+    T *Md = (T *)ctx->partials;
+    if (bytes <= mik_ctx::COEF_BYTES) {
+        MIK_HIP(ctx, mik_wait(ctx));                        // staging buffer must be idle
+        T *st = (T *)ctx->coef_host;
+        for (int j = 0; j < cols; ++j) memcpy(st + (size_t)j * rows, M + (size_t)j * ldm, sizeof(T) * (size_t)rows);
+        MIK_HIP(ctx, hipMemcpyAsync(Md, st, bytes, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        std::vector<T> pk((size_t)rows * (size_t)cols);
+        for (int j = 0; j < cols; ++j) memcpy(pk.data() + (size_t)j * rows, M + (size_t)j * ldm, sizeof(T) * (size_t)rows);
+        MIK_HIP(ctx, hipMemcpyAsync(Md, pk.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        MIK_HIP(ctx, mik_wait(ctx));
+    }
+    *dev_out = Md;
+    return MIK_OK;
+}
+
+unsigned row_grid(mik_ctx *ctx, int64_t n)
+{
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + MIK_BLOCK - 1) / MIK_BLOCK, mik_max_grid(ctx)));
+}
+
+// ---- mik_spmm ---------------------------------------------------------------------------------
+template <typename T, int CB>
+int spmm_launch(mik_ctx *ctx, const mik_csr *A, int b, const T *X, int64_t ldx, T *Y, int64_t ldy)
+{
+    const dim3 grid((unsigned)mik_spmv_nwg(A->n_rows), (unsigned)((b + CB - 1) / CB));
+    hipLaunchKernelGGL((k_spmm_rowgather<T, CB>), grid, dim3(MIK_BLOCK), 0, ctx->stream, (int)A->n_rows, b, A->rowptr, A->col, (const T *)A->val, X, ldx,
+                       Y, ldy);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
+template <typename T>
+int spmm_impl(mik_ctx *ctx, const mik_csr *A, int b, const T *X, int64_t ldx, T *Y, int64_t ldy)
+{
+    if (A->n_rows == 0) return MIK_OK;
+    if (!A->col || A->n_long) {                             // CSR arrays released, or split-off long rows: column by column
+        for (int j = 0; j < b; ++j) MIK_TRY(mik_spmv(ctx, A, X + (int64_t)j * ldx, Y + (int64_t)j * ldy));
+        return MIK_OK;
+    }
+    if (b == 1) return spmm_launch<T, 1>(ctx, A, b, X, ldx, Y, ldy);
+    if (b == 2) return spmm_launch<T, 2>(ctx, A, b, X, ldx, Y, ldy);
+    if (b <= 4) return spmm_launch<T, 4>(ctx, A, b, X, ldx, Y, ldy);
+    return spmm_launch<T, 8>(ctx, A, b, X, ldx, Y, ldy);
+}
+
+// ---- mik_block_gram ---------------------------------------------------------------------------
+template <typename T>
+int gram_impl(mik_ctx *ctx, int64_t n, int p, int q, const T *X, int64_t ldx, const T *Y, int64_t ldy, T *G, int64_t ldg)
+{
+    const int np = p * q;
+    const int64_t nseg = mik_nseg<T>(n);
+    if (nseg == 0) {                                        // empty vectors: every dot is +0
+        for (int j = 0; j < q; ++j)
+            for (int i = 0; i < p; ++i) G[(size_t)j * ldg + i] = T(0);
+        return MIK_OK;
+    }
+    MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * ((size_t)nseg + 1) * (size_t)np));
+    T *part = (T *)ctx->partials, *out = part + (size_t)nseg * (size_t)np;
+    const int tiles = ((p + MIK_GRAM_TP - 1) / MIK_GRAM_TP) * ((q + MIK_GRAM_TQ - 1) / MIK_GRAM_TQ);
+    const dim3 grid((unsigned)std::min<int64_t>(nseg, mik_max_grid(ctx)), (unsigned)tiles);
+    const bool vec = mik_aligned16(X) && mik_aligned16(Y) && ldx % VT<T>::W == 0 && ldy % VT<T>::W == 0;
+    if (vec) hipLaunchKernelGGL((k_block_gram<T, true>), grid, dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, p, q, X, ldx, Y, ldy, part);
+    else hipLaunchKernelGGL((k_block_gram<T, false>), grid, dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, p, q, X, ldx, Y, ldy, part);
+    MIK_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL((k_finalize_store<T>), dim3(np), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)part, nseg, nseg, out, (const int *)nullptr);
+    MIK_LAUNCH_CHECK(ctx);
+    std::vector<T> host((size_t)np);
+    const int chunk = (int)(mik_ctx::PUB_BYTES / sizeof(T));
+    for (int at = 0; at < np; at += chunk) MIK_TRY(mik_read_scalars<T>(ctx, out + at, std::min(chunk, np - at), host.data() + at));
+    for (int j = 0; j < q; ++j)
+        for (int i = 0; i < p; ++i) G[(size_t)j * ldg + i] = host[(size_t)j * p + i];
+    return MIK_OK;
+}
+
+// ---- mik_block_rdiv ---------------------------------------------------------------------------
+template <typename T, int S>
+int rdiv_launch(mik_ctx *ctx, int64_t n, int s, const T *Rd, T *X, int64_t ldx)
+{
+    hipLaunchKernelGGL((k_block_rdiv<T, S>), dim3(row_grid(ctx, n)), dim3(MIK_BLOCK), 0, ctx->stream, n, s, Rd, X, ldx);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
+template <typename T>
+int rdiv_impl(mik_ctx *ctx, int64_t n, int s, const T *R, int64_t ldr, T *X, int64_t ldx)
+{
+    T *Rd = nullptr;
+    MIK_TRY(blk_stage<T>(ctx, R, s, s, ldr, &Rd));
+    if (s <= 4) return rdiv_launch<T, 4>(ctx, n, s, Rd, X, ldx);
+    if (s <= 8) return rdiv_launch<T, 8>(ctx, n, s, Rd, X, ldx);
+    if (s <= 16) return rdiv_launch<T, 16>(ctx, n, s, Rd, X, ldx);
+    return rdiv_launch<T, 32>(ctx, n, s, Rd, X, ldx);
+}
+
+// ---- mik_block_update -------------------------------------------------------------------------
+template <typename T, int LB>
+int update_launch(mik_ctx *ctx, int64_t n, int sx, int b1, int b2, const T *X, int64_t ldx, const T *R, int64_t ldr, const T *P, int64_t ldp,
+                  const T *Vd, T *Xout, int64_t ldxo, T *Pout, int64_t ldpo)
+{
+    hipLaunchKernelGGL((k_block_update<T, LB>), dim3(row_grid(ctx, n)), dim3(MIK_BLOCK), 0, ctx->stream, n, sx, b1, b2, X, ldx, R, ldr, P, ldp, Vd, Xout,
+                       ldxo, Pout, ldpo);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
+template <typename T>
+int update_impl(mik_ctx *ctx, int64_t n, int sx, int b1, int b2, const T *X, int64_t ldx, const T *R, int64_t ldr, const T *P, int64_t ldp,
+                const T *V, int64_t ldv, T *Xout, int64_t ldxo, T *Pout, int64_t ldpo)
+{
+    T *Vd = nullptr;
+    MIK_TRY(blk_stage<T>(ctx, V, sx + b1 + b2, sx, ldv, &Vd));
+    if (sx <= 4) return update_launch<T, 4>(ctx, n, sx, b1, b2, X, ldx, R, ldr, P, ldp, Vd, Xout, ldxo, Pout, ldpo);
+    if (sx <= 8) return update_launch<T, 8>(ctx, n, sx, b1, b2, X, ldx, R, ldr, P, ldp, Vd, Xout, ldxo, Pout, ldpo);
+    if (sx <= 16) return update_launch<T, 16>(ctx, n, sx, b1, b2, X, ldx, R, ldr, P, ldp, Vd, Xout, ldxo, Pout, ldpo);
+    return update_launch<T, 32>(ctx, n, sx, b1, b2, X, ldx, R, ldr, P, ldp, Vd, Xout, ldxo, Pout, ldpo);
+}
+
+}  // namespace
+
+extern "C" int mik_spmm(mik_ctx *ctx, const mik_csr *A, int b, const void *X, int64_t ldx, void *Y, int64_t ldy)
+{
+    if (!ctx || !A || b < 0) return MIK_ERR_INVALID;
+    if (b > MIK_BLK_MAX) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_spmm: b = %d (at most %d columns)", b, MIK_BLK_MAX);
+    if (b == 0) return MIK_OK;
+    if (!X || !Y || ldx < A->n_cols || ldy < A->n_rows) return mik_fail(ctx, MIK_ERR_INVALID, "mik_spmm: null pointer or leading dimension too small");
+    const size_t es = mik_dtype_size(A->dtype);
+    if (blk_overlap(X, blk_bytes(es, A->n_cols, b, ldx), Y, blk_bytes(es, A->n_rows, b, ldy)))
+        return mik_fail(ctx, MIK_ERR_INVALID, "mik_spmm: Y overlaps X");
+    if (A->dtype == MIK_F64) return spmm_impl<double>(ctx, A, b, (const double *)X, ldx, (double *)Y, ldy);
+    return spmm_impl<float>(ctx, A, b, (const float *)X, ldx, (float *)Y, ldy);
+}
+
+extern "C" int mik_block_gram(mik_ctx *ctx, int dtype, int64_t n, int p, int q, const void *X, int64_t ldx, const void *Y, int64_t ldy, void *G,
+                              int64_t ldg)
+{
+    if (!ctx || n < 0 || p < 1 || q < 1 || (dtype != MIK_F64 && dtype != MIK_F32)) return MIK_ERR_INVALID;
+    if (p > MIK_BLK_MAX || q > MIK_BLK_MAX) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_block_gram: %d x %d (at most %d columns a side)", p, q, MIK_BLK_MAX);
+    if (!G || ldg < p || ldx < n || ldy < n || (n && (!X || !Y))) return mik_fail(ctx, MIK_ERR_INVALID, "mik_block_gram: null pointer or leading dimension too small");
+    if (dtype == MIK_F64) return gram_impl<double>(ctx, n, p, q, (const double *)X, ldx, (const double *)Y, ldy, (double *)G, ldg);
+    return gram_impl<float>(ctx, n, p, q, (const float *)X, ldx, (const float *)Y, ldy, (float *)G, ldg);
+}
+
+extern "C" int mik_block_rdiv(mik_ctx *ctx, int dtype, int64_t n, int s, const void *R, int64_t ldr, void *X, int64_t ldx)
+{
+    if (!ctx || n < 0 || s < 1 || (dtype != MIK_F64 && dtype != MIK_F32)) return MIK_ERR_INVALID;
+    if (s > MIK_BLK_MAX) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_block_rdiv: s = %d (at most %d columns)", s, MIK_BLK_MAX);
+    if (!R || ldr < s || ldx < n || (n && !X)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_block_rdiv: null pointer or leading dimension too small");
+    if (n == 0) return MIK_OK;
+    if (dtype == MIK_F64) return rdiv_impl<double>(ctx, n, s, (const double *)R, ldr, (double *)X, ldx);
+    return rdiv_impl<float>(ctx, n, s, (const float *)R, ldr, (float *)X, ldx);
+}
+
+extern "C" int mik_block_update(mik_ctx *ctx, int dtype, int64_t n, int sx, int b1, int b2, const void *X, int64_t ldx, const void *R, int64_t ldr,
+                                const void *P, int64_t ldp, const void *V, int64_t ldv, void *Xout, int64_t ldxo, void *Pout, int64_t ldpo)
+{
+    if (!ctx || n < 0 || sx < 1 || b1 < 0 || b2 < 0 || (dtype != MIK_F64 && dtype != MIK_F32)) return MIK_ERR_INVALID;
+    if (sx > MIK_BLK_MAX || b1 > sx || b2 > sx)
+        return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_block_update: needs b1, b2 <= sx <= %d (sx = %d, b1 = %d, b2 = %d)", MIK_BLK_MAX, sx, b1, b2);
+    if (b1 == 0 && b2 > 0) return mik_fail(ctx, MIK_ERR_INVALID, "mik_block_update: b2 > 0 needs b1 > 0");
+    if (!V || ldv < sx + b1 + b2 || ldx < n || ldxo < n || (n && (!X || !Xout)) || (b1 && (ldr < n || ldpo < n || (n && (!R || !Pout)))) ||
+        (b2 && (ldp < n || (n && !P))))
+        return mik_fail(ctx, MIK_ERR_INVALID, "mik_block_update: null pointer or leading dimension too small");
+    if (n == 0) return MIK_OK;
+    const size_t es = mik_dtype_size(dtype);
+    const void *in[3] = {X, R, P};
+    const size_t inb[3] = {blk_bytes(es, n, sx, ldx), blk_bytes(es, n, b1, ldr), blk_bytes(es, n, b2, ldp)};
+    const size_t xob = blk_bytes(es, n, sx, ldxo), pob = blk_bytes(es, n, b1 ? sx : 0, ldpo);
+    for (int i = 0; i < 3; ++i)
+        if (blk_overlap(in[i], inb[i], Xout, xob) || blk_overlap(in[i], inb[i], Pout, pob))
+            return mik_fail(ctx, MIK_ERR_INVALID, "mik_block_update: an output overlaps an input");
+    if (blk_overlap(Xout, xob, Pout, pob)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_block_update: Xout overlaps Pout");
+    if (dtype == MIK_F64)
+        return update_impl<double>(ctx, n, sx, b1, b2, (const double *)X, ldx, (const double *)R, ldr, (const double *)P, ldp, (const double *)V, ldv,
+                                   (double *)Xout, ldxo, (double *)Pout, ldpo);
+    return update_impl<float>(ctx, n, sx, b1, b2, (const float *)X, ldx, (const float *)R, ldr, (const float *)P, ldp, (const float *)V, ldv,
+                              (float *)Xout, ldxo, (float *)Pout, ldpo);
+}
