@@ -8,45 +8,12 @@ import pytest
 import scipy.sparse as sp
 
 from ladder import ladder
-from lobpcg_double import HostJacobi, NumpyOps, block_rdiv, block_update, operator
+from lobpcg_double import block_rdiv, block_update
+from lobpcg_gpu_util import DTYPES, Blk, both, code, dots, gram_raw, same_trace, spd_b, update_raw, wide
 from stationary_host import arrow
 
 pytestmark = pytest.mark.gpu
 _vp = C.c_void_p
-DTYPES = [np.float64, np.float32]
-
-
-def wide(rng, shape, dt, span=30):
-    """mixed signs, magnitudes spanning 2^-span .. 2^span: a fused multiply-add or another association changes bits"""
-    a = rng.choice([-1.0, 1.0], size=shape) * np.exp2(rng.uniform(-span, span, size=shape)) * (1 + rng.random(shape))
-    return a.astype(dt)
-
-
-class Blk:
-    """an n x k device block: aligned (leading dimension n rounded up to 64), or offset by one element with an odd leading dimension > n"""
-
-    def __init__(self, pkg, ctx, host, offset):
-        self.n, self.k = host.shape
-        self.dt = np.dtype(host.dtype)
-        self.off = 1 if offset else 0
-        self.ld = self.n + 3 + (self.n % 2 == 0) if offset else (self.n + 63) // 64 * 64
-        self.buf = pkg.HipVector(self.ld * self.k + self.off, self.dt, ctx)
-        flat = np.zeros(self.ld * self.k + self.off, self.dt)
-        for j in range(self.k):
-            flat[self.off + j * self.ld: self.off + j * self.ld + self.n] = host[:, j]
-        self.buf.copy_from_host(flat)
-        self.ptr = self.buf.ptr + self.off * self.dt.itemsize
-
-    def col(self, j):
-        return self.buf.view(self.off + j * self.ld, self.n)
-
-    def get(self):
-        flat = self.buf.to_numpy()
-        return np.stack([flat[self.off + j * self.ld: self.off + j * self.ld + self.n] for j in range(self.k)], axis=1)
-
-
-def code(pkg, dt):
-    return pkg._lib.dtype_code(dt)
 
 
 # ---- mik_spmm -----------------------------------------------------------------------------------------------------------------------
@@ -90,17 +57,6 @@ def test_spmm_refusals(pkg, ctx):
 
 
 # ---- mik_block_gram -----------------------------------------------------------------------------------------------------------------
-def gram_raw(pkg, ctx, X, p, Y, q):
-    G = np.zeros((p, q), X.dt, order="F")
-    rc = pkg.lib().mik_block_gram(ctx.handle, code(pkg, X.dt), X.n, p, q, _vp(X.ptr), X.ld, _vp(Y.ptr), Y.ld, G.ctypes.data_as(_vp), p)
-    assert rc == 0, pkg.lib().mik_last_error(ctx.handle)
-    return G
-
-
-def dots(pkg, X, p, Y, q):
-    return np.array([[pkg.dot(X.col(i), Y.col(j)) for j in range(q)] for i in range(p)], X.dt)
-
-
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("n", [1, 255, 4097])
 def test_block_gram_equals_dot_entry_by_entry(pkg, ctx, dt, n):
@@ -159,12 +115,6 @@ def test_block_rdiv_equals_the_numpy_loop(pkg, ctx, dt, n):
 
 
 # ---- mik_block_update ---------------------------------------------------------------------------------------------------------------
-def update_raw(pkg, ctx, n, sx, b1, b2, X, R, P, V, Xo, Po):
-    Vf = np.asfortranarray(V)
-    return pkg.lib().mik_block_update(ctx.handle, code(pkg, X.dt), n, sx, b1, b2, _vp(X.ptr), X.ld, _vp(R.ptr), R.ld, _vp(P.ptr), P.ld,
-                                      Vf.ctypes.data_as(_vp), Vf.shape[0], _vp(Xo.ptr), Xo.ld, _vp(Po.ptr), Po.ld)
-
-
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("n", [1, 255, 4097, 1_000_003])
 def test_block_update_equals_the_composition_of_rotations(pkg, ctx, dt, n):
@@ -210,32 +160,6 @@ def test_block_update_refusals(pkg, ctx):
 def lap12(pkg, dt):
     n, cp, rv, nz = pkg.fixtures.laplace_matrix(12, 3, dtype=dt, index_base=0)
     return sp.csc_matrix((nz, rv, cp), shape=(n, n))
-
-
-def spd_b(n, dt):
-    """tridiagonal (-1, 4, -1): strictly diagonally dominant, SPD"""
-    return sp.diags([-np.ones(n - 1), 4 * np.ones(n), -np.ones(n - 1)], [-1, 0, 1], format="csc", dtype=dt)
-
-
-def both(pkg, orc, ctx, dt, S, Sb, largest, rest, jacobi, **kw):
-    n = S.shape[0]
-    A, B = pkg.HipCSR.from_scipy(S, ctx), (pkg.HipCSR.from_scipy(Sb, ctx) if Sb is not None else None)
-    d = S.diagonal().astype(dt)
-    dev_args = (A, largest) if B is None else (A, B, largest)
-    dbl_args = (operator(orc, S), largest) if Sb is None else (operator(orc, S), operator(orc, Sb), largest)
-    rd = pkg.lobpcg(*dev_args, *rest, P=pkg.JacobiPrec(pkg.HipVector.from_numpy(d, ctx)) if jacobi else None, log=True,
-                    rng=np.random.default_rng(5), **kw)
-    rh = pkg.lobpcg(*dbl_args, *rest, P=HostJacobi(d) if jacobi else None, log=True, rng=np.random.default_rng(5),
-                    ops=NumpyOps(orc, n, dt), **kw)
-    return rd, rh
-
-
-def same_trace(ta, tb):
-    assert len(ta) == len(tb), (len(ta), len(tb))
-    for a, b in zip(ta, tb):
-        assert a.iteration == b.iteration
-        assert np.array_equal(a.ritz_values, b.ritz_values), (a.iteration, a.ritz_values, b.ritz_values)
-        assert np.array_equal(a.residual_norms, b.residual_norms), (a.iteration, a.residual_norms, b.residual_norms)
 
 
 @pytest.mark.parametrize("dt", DTYPES)

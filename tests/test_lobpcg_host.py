@@ -235,7 +235,25 @@ def test_block_definitions_agree_with_dense_algebra():
     assert np.allclose(block_rdiv(X.copy(), U), X @ np.linalg.inv(U))
 
 
-# ---- 10: ABI ------------------------------------------------------------------------------------------------------------------------
+# ---- 10: the operators of tests/test_gpu_lobpcg_paths.py have the properties they were built for -----------------------------------
+@pytest.mark.parametrize("dt", DTYPES)
+def test_fixture_operators_of_the_gpu_path_tests(pkg, dt):
+    """every builder of tests/lobpcg_fixtures.py asserts its own properties (tile passes, straddling rows, empty rows, thresholds, ...)"""
+    import ctypes as C
+
+    import lobpcg_fixtures as fx
+    t = C.c_int()
+    assert pkg.lib().mik_spmv_long_row(C.byref(t)) == 0 and t.value == 256
+    for name, build in fx.SPMM_BUILDERS.items():
+        S = build(dt, t.value)
+        assert S.dtype == dt and S.has_sorted_indices and np.diff(S.indptr).max() <= t.value, name
+    assert len(fx.SPMM_BUILDERS) == 15
+    S = fx.irregular_spd(dt, t.value)
+    assert S.shape == (1500, 1500) and S.dtype == dt
+    assert np.linalg.eigvalsh(S.toarray().astype(np.float64))[0] > 0.5          # Gershgorin, checked
+
+
+# ---- 11: ABI ------------------------------------------------------------------------------------------------------------------------
 def test_the_four_entries_are_declared_bound_and_exported(pkg):
     header = open(os.path.join(ROOT, "include", "mik.h")).read()
     L = pkg.lib()
