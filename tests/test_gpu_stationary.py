@@ -5,6 +5,7 @@ import pytest
 import scipy.sparse as sp
 
 import stationary_host as sh
+from stationary_fixtures import check_methods as _check_methods, dev as _dev       # shared with tests/test_gpu_stationary_paths.py
 
 pytestmark = pytest.mark.gpu
 
@@ -12,11 +13,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="session")
 def ref(tmp_path_factory):
     return sh.build(tmp_path_factory.mktemp("stationary_ref_gpu"))
-
-
-def _dev(pkg, M, i32=False):
-    cp, rv = (M.cp.astype(np.int32), M.rv.astype(np.int32)) if i32 else (M.cp, M.rv)
-    return pkg.HipCSR(M.n, M.n, cp, rv, M.nz, index_base=0)
 
 
 def _mats(pkg, ctx, dtype):
@@ -29,23 +25,6 @@ def _mats(pkg, ctx, dtype):
             "arrow": sh.Mat(sh.arrow(3000, long_row + 40, dtype), dtype),
             "arrow_cut": sh.Mat(sh.arrow(3 * ctx.spmv_long_segment() + 500, 3 * ctx.spmv_long_segment() + 100, dtype), dtype),
             "tridiag": sh.Mat(sh.tridiag(2000, dtype), dtype)}
-
-
-def _check_methods(pkg, ref, M, A, omega, k, rng):
-    T = M.dtype
-    b = rng.standard_normal(M.n).astype(T)
-    x0 = rng.standard_normal(M.n).astype(T)
-    bd = pkg.HipVector.from_numpy(b)
-    x = pkg.HipVector.from_numpy(x0)
-    assert np.array_equal(pkg.jacobi_(x, A, bd, maxiter=k).to_numpy(), ref.jacobi(M, b, x0, k)[0]), "jacobi"
-    x = pkg.HipVector.from_numpy(x0)
-    assert np.array_equal(pkg.gauss_seidel_(x, A, bd, maxiter=k).to_numpy(), ref.gauss_seidel(M, b, x0, k)[0]), "gauss_seidel"
-    x = pkg.HipVector.from_numpy(x0)
-    xr, rr, _ = ref.sor(M, b, x0, omega, k)
-    r = pkg.sor_(x, A, bd, omega, maxiter=k)
-    assert np.array_equal(r.to_numpy(), rr) and np.array_equal(x.to_numpy(), xr), "sor"
-    x = pkg.HipVector.from_numpy(x0)
-    assert np.array_equal(pkg.ssor_(x, A, bd, omega, maxiter=k).to_numpy(), ref.ssor(M, b, x0, omega, k)[0]), "ssor"
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])

@@ -1,6 +1,7 @@
 """The CPU checker of the stationary methods: tests/stationary_ref/stationary_ref.c (the reference's CSC column loops restated in
 C) against numbers Julia printed (docs/src/iterators.md), against the assertions of test/stationary.jl, and against an independent
-sequential ROW-view restatement in numpy, bit for bit.  No GPU."""
+sequential ROW-view restatement in numpy, bit for bit -- also on the operators of tests/stationary_fixtures.py, whose prescribed level
+widths and launch plans are asserted here first.  No GPU."""
 import math
 
 import numpy as np
@@ -8,6 +9,7 @@ import pytest
 import scipy.linalg as sla
 import scipy.sparse as sp
 
+import stationary_fixtures as fx
 import stationary_host as sh
 
 
@@ -210,6 +212,100 @@ def test_row_view_restatement_agrees_bit_for_bit(ref, dtype, omega):
             assert np.array_equal(ref.gauss_seidel(M, b, x0, k)[0], _np_method(R, "gs", b, x0, omega, k, None))
             assert np.array_equal(ref.sor(M, b, x0, omega, k)[1], _np_method(R, "sor", b, x0, omega, k, S))
             assert np.array_equal(ref.ssor(M, b, x0, omega, k)[0], _np_method(R, "ssor", b, x0, omega, k, S))
+
+
+# ---- the operators of tests/stationary_fixtures.py: their level structure, then the checker on them -----------------------------------
+DTYPES = (np.float64, np.float32)
+OMEGAS = [(np.float64, 1.2), (np.float64, np.float32(0.7)), (np.float64, 1), (np.float32, 1.2), (np.float32, np.float32(1.2)), (np.float32, 1)]
+
+
+def test_level_widths_and_launch_plan_on_cases_worked_by_hand():
+    """the two plain-numpy functions every info() expectation rests on"""
+    assert fx.level_widths(sh.Mat(sh.tridiag(5))) == ([1] * 5, [1] * 5)
+    assert fx.level_widths(sh.Mat(sp.identity(7, format="csc"))) == ([7], [7])
+    # rows 0, 1 read nothing below; 2 reads 0; 3 reads 1 and 2; 4 reads 0.  Above: 0 reads 4; 1 reads 2; 2 reads 3; 3, 4 nothing
+    A = sp.csc_matrix((np.ones(12), ([0, 1, 2, 3, 4, 2, 3, 3, 4, 0, 1, 2], [0, 1, 2, 3, 4, 0, 1, 2, 0, 4, 2, 3])), shape=(5, 5))
+    assert fx.level_widths(sh.Mat(A)) == ([2, 2, 1], [2, 2, 1])          # forward {0, 1}, {2, 4}, {3}; backward {3, 4}, {0, 2}, {1}
+    assert fx.level_widths(sh.Mat(sp.csc_matrix((0, 0)))) == ([], [])
+    assert fx.launch_plan([]) == []
+    assert fx.launch_plan([256]) == [("run", 0, 1, 0, 256)] and fx.launch_plan([257]) == [("wide", 0, 1, 0, 257)]
+    assert fx.launch_plan([255, 256, 257, 3, 512, 1, 513, 252]) == [("run", 0, 2, 0, 511), ("wide", 2, 3, 511, 768), ("run", 3, 4, 768, 771),
+                                                                     ("wide", 4, 5, 771, 1283), ("run", 5, 6, 1283, 1284),
+                                                                     ("wide", 6, 7, 1284, 1797), ("run", 7, 8, 1797, 2049)]
+    assert fx.launch_plan([300, 257, 1, 2, 3, 400]) == [("wide", 0, 1, 0, 300), ("wide", 1, 2, 300, 557), ("run", 2, 5, 557, 563), ("wide", 5, 6, 563, 963)]
+    assert fx.launch_plan([3, 4, 5], narrow=3) == [("run", 0, 1, 0, 3), ("wide", 1, 2, 3, 7), ("wide", 2, 3, 7, 12)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", list(fx.FIXTURES))
+def test_level_fixtures_have_their_prescribed_widths_and_plans(name, dtype):
+    """every builder runs its own assertions; here the widths and the number of wide launches are pinned once more, so that a later edit
+    cannot quietly turn a fixture narrow again"""
+    M = fx.fixture(name, dtype)
+    assert M.dtype == dtype and M.widths == fx.level_widths(M) and sum(M.widths[0]) == sum(M.widths[1]) == M.n < 20000
+    want = {"edges": fx.EDGES, "stairs": fx.STAIRS, "hubs": fx.HUBS}.get(name)
+    if want is not None:
+        assert M.widths == want
+    wide = {"edges": (3, 3), "stairs": (4, 3), "hubs": (3, 2), "lap24": (26, 26), "sprand4000": (6, 6)}[name]
+    launches = {"edges": (7, 5), "stairs": (6, 5), "hubs": (3, 3), "lap24": (28, 28), "sprand4000": (7, 7)}[name]
+    for d in (0, 1):
+        plan = M.plans[d]
+        assert len(plan) == launches[d] and len(fx.wide_launches(plan)) == wide[d] >= 2
+        assert [p[0] for p in plan] == ["wide" if M.widths[d][p[1]] > 256 else "run" for p in plan]
+        assert all(p[2] == p[1] + 1 and p[4] - p[3] == M.widths[d][p[1]] > 256 for p in fx.wide_launches(plan))
+        assert plan[0][3] == 0 and plan[-1][4] == M.n and all(a[4] == b[3] and a[2] == b[1] for a, b in zip(plan, plan[1:]))
+    if name == "lap24":
+        assert max(M.widths[0]) == 432 and len(M.widths[0]) == 70
+    if name == "sprand4000":
+        assert max(M.widths[0]) > 900 and len(M.widths[0]) <= 20
+    if name == "hubs":                                                   # the long rows sit inside a wide level, in either direction
+        lens = np.bincount(M.rv, minlength=M.n)
+        assert all(lens[r] > fx.LONG_ROW for r in M.longs[0] + M.longs[1])
+        assert fx.launch_plan(M.widths[0])[2][0] == "wide" and fx.launch_plan(M.widths[1])[2][0] == "wide"
+
+
+def test_width_lists_cover_every_case_between_them():
+    lists = [w for pair in (fx.EDGES, fx.STAIRS, fx.HUBS) for w in pair]
+    plans = [fx.launch_plan(w) for w in lists]
+    adjacent = lambda w, a, b: any({x, y} == {a, b} for x, y in zip(w, w[1:]))
+    assert any(adjacent(w, 255, 256) and adjacent(w, 256, 257) for w in lists)                      # 255 | 256 | 257 next to one another
+    assert any(adjacent(w, 255, 256) for w in lists) and any(adjacent(w, 255, 257) for w in lists)
+    assert any(512 in w for w in lists) and any(513 in w for w in lists)                           # 256 q and 256 q + 1
+    assert any(p[0] == "wide" and p[3] % 256 for plan in plans for p in plan)                      # a wide launch whose p0 is no multiple of 256
+    assert sum(1 for plan in plans for p in plan if p[0] == "wide" and p[3] % 256) >= 8
+    triples = [(a, b, c) for plan in plans for a, b, c in zip(plan, plan[1:], plan[2:])]
+    assert any(a[0] == c[0] == "wide" and b[0] == "run" and b[2] - b[1] >= 3 for a, b, c in triples)    # wide -> a run of >= 3 levels -> wide
+    assert any(a[0] == c[0] == "wide" and b[0] == "run" and b[4] - b[3] == 1 for a, b, c in triples)    # a one-row level between two wide ones
+    assert any(plan[0][0] == "wide" for plan in plans) and any(plan[-1][0] == "wide" for plan in plans)
+    assert any(plan[0][0] == "run" for plan in plans) and any(plan[-1][0] == "run" for plan in plans)
+    assert any(plan[0][0] == "run" and plan[0][2] - plan[0][1] >= 2 for plan in plans)
+    for lo, up in (fx.EDGES, fx.STAIRS, fx.HUBS):                                                   # forward and backward plans differ
+        assert fx.kinds(fx.launch_plan(lo)) != fx.kinds(fx.launch_plan(up)) and sum(lo) == sum(up)
+    assert sorted(sum(lo) - 2048 for lo, _ in (fx.EDGES, fx.STAIRS, fx.HUBS)) == [-1, 0, 1]         # n on both sides of a multiple of 256
+
+
+@pytest.mark.parametrize("dtype,omega", OMEGAS)
+@pytest.mark.parametrize("name", list(fx.FIXTURES))
+def test_row_view_restatement_agrees_on_the_level_fixtures(ref, name, dtype, omega):
+    """the checker checked at the shapes the device is held to in tests/test_gpu_stationary_paths.py: the C column loops against the
+    numpy row-view restatement, bit for bit, four methods and the four substitutions alone, omega as Float64, Float32 and Int"""
+    M = fx.fixture(name, dtype)
+    R = RowView(sp.csc_matrix((M.nz, M.rv, M.cp), shape=(M.n, M.n)), dtype)
+    rng = np.random.default_rng(23)
+    b = rng.standard_normal(M.n).astype(dtype)
+    x0 = rng.standard_normal(M.n).astype(dtype)
+    S = np.float32 if sh.omega32(omega, dtype) else np.float64
+    k = 2
+    assert np.array_equal(ref.jacobi(M, b, x0, k)[0], _np_method(R, "jacobi", b, x0, omega, k, None))
+    assert np.array_equal(ref.gauss_seidel(M, b, x0, k)[0], _np_method(R, "gs", b, x0, omega, k, None))
+    assert np.array_equal(ref.sor(M, b, x0, omega, k)[1], _np_method(R, "sor", b, x0, omega, k, S))
+    x = ref.ssor(M, b, x0, omega, k)[0]
+    assert np.array_equal(x, _np_method(R, "ssor", b, x0, omega, k, S)) and np.all(np.isfinite(x))
+    ref.diag(M)
+    a, be = S(omega), S(S(1) - S(omega))
+    for upper in (False, True):
+        assert np.array_equal(ref.sub(M, upper, b), np.array(R.sub(upper, b), dtype))
+        assert np.array_equal(ref.sub(M, upper, b, omega, x0), np.array(R.sub(upper, b, S, a, be, x0), dtype))
 
 
 def test_float32_with_float64_omega_rounds_once(ref):
