@@ -361,21 +361,6 @@ extern "C" int mik_idrs_create(mik_ctx *ctx, const mik_csr *A, int s, void *x, v
 
 namespace {
 
-template <typename T> static int idrs_multidot(mik_ctx *ctx, int64_t n, int k, const T *V, int64_t ldv, const T *w, T *out_dev, int nt = 0)
-{
-    const int64_t nseg = mik_nseg<T>(n);
-    if (k <= 0) return MIK_OK;
-    if (nseg == 0) { MIK_HIP(ctx, hipMemsetAsync(out_dev, 0, sizeof(T) * k, ctx->stream)); return MIK_OK; }
-    const int grid = (int)std::min<int64_t>(nseg, mik_max_grid(ctx));
-    const bool vec = mik_aligned16(V) && mik_aligned16(w) && (ldv % VT<T>::W == 0);
-    if (vec) hipLaunchKernelGGL((k_multidot<T, true>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, V, ldv, w, (T *)ctx->partials, nt);
-    else hipLaunchKernelGGL((k_multidot<T, false>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, V, ldv, w, (T *)ctx->partials, 0);
-    MIK_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL((k_finalize_store<T>), dim3(k), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)ctx->partials, nseg, nseg, out_dev, (const int *)nullptr);
-    MIK_LAUNCH_CHECK(ctx);
-    return MIK_OK;
-}
-
 // level 2 of a norm's segment sums into dev[0] (norm; NaN outside the safe range) and dev[1]
 template <typename T> static int idrs_fin_norm(mik_ctx *ctx, int64_t nseg, const T *part, T *dev)
 {
@@ -426,7 +411,7 @@ template <typename T> static int idrs_step_impl(mik_idrs *it, int step, T *normR
     if (step <= s) {
         const int k = step - 1, cnt = s - k;
         if (k == 0) {                                                                               // f = P' R  :178-182
-            MIK_TRY(idrs_multidot<T>(ctx, n, s, P, it->ldp, r, dev + IDRS_SLOT_VEC, (nt >> 1) & 1));
+            MIK_TRY(launch_multidot<T>(ctx, n, s, P, it->ldp, r, dev + IDRS_SLOT_VEC, (nt >> 1) & 1));
             MIK_TRY(mik_read_scalars<T>(ctx, dev + IDRS_SLOT_VEC, s, h->f.data()));
         }
         IdrsCoef<T> c;                                                                              // c = LowerTriangular(M[k:s,k:s]) \ f[k:s]  :187
@@ -463,7 +448,7 @@ template <typename T> static int idrs_step_impl(mik_idrs *it, int step, T *normR
                 T *t = cur; cur = nxt; nxt = t;
             }
         }
-        MIK_TRY(idrs_multidot<T>(ctx, n, cnt, P + (int64_t)k * it->ldp, it->ldp, gk, dev + IDRS_SLOT_VEC, (nt >> 1) & 1));   // M[k..s, k]  :215-217
+        MIK_TRY(launch_multidot<T>(ctx, n, cnt, P + (int64_t)k * it->ldp, it->ldp, gk, dev + IDRS_SLOT_VEC, (nt >> 1) & 1));   // M[k..s, k]  :215-217
         {
             OpIdrsUpdate<T> op{r, gk, x, uk, Quot<T>{nullptr, h->f[(size_t)k], dev + IDRS_SLOT_VEC}};          // :221-225
             const bool vec = vecb && mik_aligned16(r) && mik_aligned16(x);

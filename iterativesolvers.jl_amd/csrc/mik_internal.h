@@ -245,6 +245,22 @@ template <typename T> static inline int64_t mik_nseg(int64_t n)
     return (n + seg - 1) / seg;
 }
 
+// Cache hint of a sweep over k basis columns of n elements: stream them past the caches when they cannot stay resident anyway (they
+// exceed what the 256 MB Infinity Cache holds next to the vector being orthogonalised), so that the vector does.
+template <typename T> static inline int mik_basis_nt(int64_t n, int k) { return (double)n * (double)k * sizeof(T) > 192.0e6 ? 1 : 0; }
+
+// Bytes from the first element of an n x cols block with leading dimension ld to its last (0: the block is empty), and whether two such
+// extents share a byte -- the aliasing refusals of the block entries.
+static inline size_t mik_block_bytes(size_t es, int64_t n, int cols, int64_t ld)
+{
+    return (n > 0 && cols > 0) ? es * ((size_t)(cols - 1) * (size_t)ld + (size_t)n) : 0;
+}
+static inline bool mik_overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
 // ---------------------------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------------------------
@@ -474,6 +490,26 @@ template <typename T> static inline int mik_read_scalars(mik_ctx *ctx, const T *
 #endif
     }
     memcpy(host_out, ctx->pub, sizeof(T) * count);
+    return MIK_OK;
+}
+
+// A small host matrix (rows x cols, leading dimension ldm), packed to leading dimension `rows`, at the head of ctx->partials.  Through the
+// context's pinned staging area when it fits, else straight from a packed copy with a wait: either way the caller's array (pageable or
+// pinned) has been read when this returns.
+template <typename T> static inline int mik_stage_small(mik_ctx *ctx, const T *M, int rows, int cols, int64_t ldm, T **dev_out)
+{
+    const size_t bytes = sizeof(T) * (size_t)rows * (size_t)cols;
+    MIK_TRY(mik_ensure_partials(ctx, bytes));
+    T *Md = (T *)ctx->partials;
+    std::vector<T> pk;
+    T *st = (T *)ctx->coef_host;
+    const bool pinned = bytes <= mik_ctx::COEF_BYTES;
+    if (pinned) MIK_HIP(ctx, mik_wait(ctx));                // staging buffer must be idle
+    else { pk.resize((size_t)rows * (size_t)cols); st = pk.data(); }
+    for (int j = 0; j < cols; ++j) memcpy(st + (size_t)j * rows, M + (size_t)j * ldm, sizeof(T) * (size_t)rows);
+    MIK_HIP(ctx, hipMemcpyAsync(Md, st, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (!pinned) MIK_HIP(ctx, mik_wait(ctx));
+    *dev_out = Md;
     return MIK_OK;
 }
 

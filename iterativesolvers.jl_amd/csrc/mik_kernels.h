@@ -296,6 +296,130 @@ template <typename T> __device__ __forceinline__ void vstore_nt(T *p, typename V
     __builtin_nontemporal_store(o, reinterpret_cast<NV *>(p));
 }
 
+// ---- a thread's share of one segment of a column, held in registers -------------------------------------------------------------
+// What the sweeps over the Krylov basis and the Gram kernels are written in (k_multidot, k_gemv_n, k_gram, k_block_gram): register
+// q = l * W + e holds element base + l * 256 * W + e of the column, base = s * SEG + W * t.  A 16-byte access when VEC and all W
+// elements lie inside n, else a guarded scalar tail.  Sums run l ascending, then e ascending, over the elements inside n, every
+// product rounded before it is added -- the order of OpDot in k_map, so that a dot formed here has the bits of mik_dot.
+template <typename T> constexpr int SEG_REGS = MIK_RED_L * VT<T>::W;
+
+// r = the thread's elements of col (elements at or past n: 0); nt: the 16-byte loads are non-temporal
+template <typename T, bool VEC>
+__device__ __forceinline__ void seg_load(const T *__restrict__ col, int64_t base, int64_t n, int nt, T (&r)[SEG_REGS<T>])
+{
+    constexpr int W = VT<T>::W;
+#pragma unroll
+    for (int l = 0; l < MIK_RED_L; ++l) {
+        const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
+        if (VEC && i + W <= n) {
+            auto cv = nt ? vload_nt(col + i) : vload(col + i);
+#pragma unroll
+            for (int e = 0; e < W; ++e) r[l * W + e] = el<T>(cv, e);
+        } else {
+#pragma unroll
+            for (int e = 0; e < W; ++e) r[l * W + e] = (i + e < n) ? col[i + e] : T(0);
+        }
+    }
+}
+
+// the thread's elements of col = r; nothing at or past n is written
+template <typename T, bool VEC>
+__device__ __forceinline__ void seg_store(T *__restrict__ col, int64_t base, int64_t n, const T (&r)[SEG_REGS<T>])
+{
+    constexpr int W = VT<T>::W;
+#pragma unroll
+    for (int l = 0; l < MIK_RED_L; ++l) {
+        const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
+        if (VEC && i + W <= n) {
+            typename VT<T>::vec cv;
+#pragma unroll
+            for (int e = 0; e < W; ++e) el<T>(cv, e) = r[l * W + e];
+            vstore(col + i, cv);
+        } else {
+#pragma unroll
+            for (int e = 0; e < W; ++e)
+                if (i + e < n) col[i + e] = r[l * W + e];
+        }
+    }
+}
+
+// the thread's sum of a .* b
+template <typename T, bool VEC>
+__device__ __forceinline__ T seg_dot(const T (&a)[SEG_REGS<T>], const T (&b)[SEG_REGS<T>], int64_t base, int64_t n)
+{
+    constexpr int W = VT<T>::W;
+    T acc = T(0);
+#pragma unroll
+    for (int l = 0; l < MIK_RED_L; ++l) {
+        const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
+        if (VEC && i + W <= n) {
+#pragma unroll
+            for (int e = 0; e < W; ++e) { T p = a[l * W + e] * b[l * W + e]; acc = acc + p; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < W; ++e)
+                if (i + e < n) { T p = a[l * W + e] * b[l * W + e]; acc = acc + p; }
+        }
+    }
+    return acc;
+}
+
+// The two sweeps over a column that is read once (k_multidot, k_gemv_n): the thread's sum of col .* w, and y += temp * col, in the order
+// and with the roundings of seg_dot.  The column does not pass through a register set of its own: a 16-byte group is consumed before the
+// next one is requested -- with both groups in flight these HBM-bound sweeps measured 3 - 5 % slower at 2^24 elements (profiles/README.md).
+template <typename T, bool VEC>
+__device__ __forceinline__ T seg_dot_col(const T *__restrict__ col, int64_t base, int64_t n, int nt, const T (&w)[SEG_REGS<T>])
+{
+    constexpr int W = VT<T>::W;
+    T acc = T(0);
+#pragma unroll
+    for (int l = 0; l < MIK_RED_L; ++l) {
+        const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
+        if (VEC && i + W <= n) {
+            auto cv = nt ? vload_nt(col + i) : vload(col + i);
+#pragma unroll
+            for (int e = 0; e < W; ++e) { T p = el<T>(cv, e) * w[l * W + e]; acc = acc + p; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < W; ++e)
+                if (i + e < n) { T p = col[i + e] * w[l * W + e]; acc = acc + p; }
+        }
+    }
+    return acc;
+}
+template <typename T, bool VEC>
+__device__ __forceinline__ void seg_axpy_col(T temp, const T *__restrict__ col, int64_t base, int64_t n, int nt, T (&y)[SEG_REGS<T>])
+{
+    constexpr int W = VT<T>::W;
+#pragma unroll
+    for (int l = 0; l < MIK_RED_L; ++l) {
+        const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
+        if (VEC && i + W <= n) {
+            auto cv = nt ? vload_nt(col + i) : vload(col + i);
+#pragma unroll
+            for (int e = 0; e < W; ++e) { T p = temp * el<T>(cv, e); y[l * W + e] = y[l * W + e] + p; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < W; ++e)
+                if (i + e < n) { T p = temp * col[i + e]; y[l * W + e] = y[l * W + e] + p; }
+        }
+    }
+}
+
+// Several sums of one segment at a time (k_gram, k_block_gram): every thread hands in its sum of a pair -- wave tree, lane 0 of wave w
+// writes slot[w] -- and, after a __syncthreads(), one thread per pair adds the 4 wave sums left to right: the shape of block_tree_256.
+template <typename T> __device__ __forceinline__ void pair_put(T acc, T (&slot)[4])
+{
+    acc = wave_tree(acc);
+    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = acc;
+}
+template <typename T> __device__ __forceinline__ T pair_total(const T (&slot)[4])
+{
+    T tot = slot[0];
+    tot = tot + slot[1]; tot = tot + slot[2]; tot = tot + slot[3];
+    return tot;
+}
+
 // Helper macro: define apply_vec in terms of a per-element lambda over loaded vectors is not
 // possible generically, so each op spells out its loads (all issued before the arithmetic).
 
@@ -1499,48 +1623,26 @@ __global__ __launch_bounds__(MIK_FIN_THREADS) void k_finalize_nrm_inv(const T *_
 
 // partial sums of V[:, j] .* w for j = 0..k-1, one segment per workgroup; w is read once.
 //   -- mul!(h, adjoint(V), w): src/orthogonalize.jl:15,27,43
-template <typename T, bool VEC>
+// SQ: one more reduced column, the segment sums of w .* w at seg_out[k] -- the bits mik_nrm2 squares
+//   -- src/svdl.jl:569-570 (oldqnorm and Q'q from one read of q)
+template <typename T, bool VEC, bool SQ = false>
 __global__ __launch_bounds__(MIK_BLOCK) void k_multidot(int64_t n, int64_t nseg, int k, const T *__restrict__ V,
                                                         int64_t ldv, const T *__restrict__ w,
-                                                        T *__restrict__ seg_out /* [k][nseg] */, int nt)
+                                                        T *__restrict__ seg_out /* [k + SQ][nseg] */, int nt)
 {
-    constexpr int W = VT<T>::W;
-    constexpr int L = MIK_RED_L;
-    constexpr int64_t SEG = (int64_t)MIK_BLOCK * W * L;
+    constexpr int64_t SEG = (int64_t)MIK_BLOCK * SEG_REGS<T>;
     __shared__ T lds4[4];
     for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const int64_t base = s * SEG + (int64_t)W * threadIdx.x;
-        T wr[L * W];
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-            if (VEC && i + W <= n) {
-                auto wv = vload(w + i);
-#pragma unroll
-                for (int e = 0; e < W; ++e) wr[l * W + e] = el<T>(wv, e);
-            } else {
-#pragma unroll
-                for (int e = 0; e < W; ++e) wr[l * W + e] = (i + e < n) ? w[i + e] : T(0);
-            }
-        }
+        const int64_t base = s * SEG + (int64_t)VT<T>::W * threadIdx.x;
+        T wr[SEG_REGS<T>];
+        seg_load<T, VEC>(w, base, n, 0, wr);
         for (int j = 0; j < k; ++j) {
-            const T *__restrict__ col = V + (int64_t)j * ldv;
-            T acc = T(0);
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-                if (VEC && i + W <= n) {
-                    auto cv = nt ? vload_nt(col + i) : vload(col + i);
-#pragma unroll
-                    for (int e = 0; e < W; ++e) { T p = el<T>(cv, e) * wr[l * W + e]; acc = acc + p; }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < W; ++e)
-                        if (i + e < n) { T p = col[i + e] * wr[l * W + e]; acc = acc + p; }
-                }
-            }
-            T tot = block_tree_256(acc, lds4);
+            T tot = block_tree_256(seg_dot_col<T, VEC>(V + (int64_t)j * ldv, base, n, nt, wr), lds4);
             if (threadIdx.x == 0) seg_out[(int64_t)j * nseg + s] = tot;
+        }
+        if (SQ) {
+            T tot = block_tree_256(seg_dot<T, VEC>(wr, wr, base, n), lds4);
+            if (threadIdx.x == 0) seg_out[(int64_t)k * nseg + s] = tot;
         }
     }
 }
@@ -1553,52 +1655,21 @@ template <typename T, bool VEC, int K>
 __global__ __launch_bounds__(MIK_BLOCK) void k_gram(int64_t n, int64_t nseg, const T *__restrict__ V, int64_t ldv,
                                                     T *__restrict__ seg_out)
 {
-    constexpr int W = VT<T>::W;
-    constexpr int L = MIK_RED_L;
     constexpr int NP = K * (K + 1) / 2;
-    constexpr int64_t SEG = (int64_t)MIK_BLOCK * W * L;
+    constexpr int64_t SEG = (int64_t)MIK_BLOCK * SEG_REGS<T>;
     __shared__ T lds[NP][4];
     for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const int64_t base = s * SEG + (int64_t)W * threadIdx.x;
-        T cr[K][L * W];
+        const int64_t base = s * SEG + (int64_t)VT<T>::W * threadIdx.x;
+        T cr[K][SEG_REGS<T>];
 #pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const T *__restrict__ col = V + (int64_t)j * ldv;
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-                if (VEC && i + W <= n) {
-                    auto cv = vload(col + i);
-#pragma unroll
-                    for (int e = 0; e < W; ++e) cr[j][l * W + e] = el<T>(cv, e);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < W; ++e) cr[j][l * W + e] = (i + e < n) ? col[i + e] : T(0);
-                }
-            }
-        }
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        for (int j = 0; j < K; ++j) seg_load<T, VEC>(V + (int64_t)j * ldv, base, n, 0, cr[j]);
         int p = 0;
 #pragma unroll
         for (int r = 0; r < K; ++r)
 #pragma unroll
-            for (int c = r; c < K; ++c) {
-                T acc = T(0);
-#pragma unroll
-                for (int q = 0; q < L * W; ++q) {
-                    const int64_t i = base + (int64_t)(q / W) * MIK_BLOCK * W + (q % W);
-                    if (i < n) { T pr = cr[r][q] * cr[c][q]; acc = acc + pr; }
-                }
-                acc = wave_tree(acc);
-                if (lane == 0) lds[p][w] = acc;
-                ++p;
-            }
+            for (int c = r; c < K; ++c) pair_put(seg_dot<T, VEC>(cr[r], cr[c], base, n), lds[p++]);
         __syncthreads();
-        if (threadIdx.x < NP) {
-            T tot = lds[threadIdx.x][0];
-            tot = tot + lds[threadIdx.x][1]; tot = tot + lds[threadIdx.x][2]; tot = tot + lds[threadIdx.x][3];
-            seg_out[(int64_t)threadIdx.x * nseg + s] = tot;
-        }
+        if (threadIdx.x < NP) seg_out[(int64_t)threadIdx.x * nseg + s] = pair_total(lds[threadIdx.x]);
         __syncthreads();
     }
 }
@@ -1714,60 +1785,89 @@ __global__ __launch_bounds__(MIK_BLOCK) void k_bicg_mr(int64_t n, int64_t nseg, 
 
 // y += sum_j (alpha * c[j]) * V[:, j], columns ascending (reference-BLAS dgemv 'N' order)
 //   -- mul!(y, V, c, alpha, 1): src/orthogonalize.jl:16,30,44; src/gmres.jl:275
-template <typename T, bool VEC>
+// SQ: also the segment sums of the updated y .* y at seg_out[s] -- the bits mik_nrm2 squares
+//   -- src/svdl.jl:570-571 (q -= Q h and norm(q) from one sweep)
+template <typename T, bool VEC, bool SQ = false>
 __global__ __launch_bounds__(MIK_BLOCK) void k_gemv_n(int64_t n, int64_t nseg, int k, const T *__restrict__ V,
                                                       int64_t ldv, const T *__restrict__ cf, T alpha,
-                                                      T *__restrict__ y, int nt)
+                                                      T *__restrict__ y, T *__restrict__ seg_out /* SQ only */, int nt)
 {
-    constexpr int W = VT<T>::W;
-    constexpr int L = MIK_RED_L;
-    constexpr int64_t SEG = (int64_t)MIK_BLOCK * W * L;
+    constexpr int64_t SEG = (int64_t)MIK_BLOCK * SEG_REGS<T>;
+    __shared__ T lds4[4];
     for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const int64_t base = s * SEG + (int64_t)W * threadIdx.x;
-        T yr[L * W];
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-            if (VEC && i + W <= n) {
-                auto yv = vload<T>(y + i);
-#pragma unroll
-                for (int e = 0; e < W; ++e) yr[l * W + e] = el<T>(yv, e);
-            } else {
-#pragma unroll
-                for (int e = 0; e < W; ++e) yr[l * W + e] = (i + e < n) ? y[i + e] : T(0);
-            }
-        }
+        const int64_t base = s * SEG + (int64_t)VT<T>::W * threadIdx.x;
+        T yr[SEG_REGS<T>];
+        seg_load<T, VEC>(y, base, n, 0, yr);
         for (int j = 0; j < k; ++j) {
-            const T *__restrict__ col = V + (int64_t)j * ldv;
-            const T temp = alpha * cf[j];
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-                if (VEC && i + W <= n) {
-                    auto cv = nt ? vload_nt(col + i) : vload(col + i);
-#pragma unroll
-                    for (int e = 0; e < W; ++e) { T p = temp * el<T>(cv, e); yr[l * W + e] = yr[l * W + e] + p; }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < W; ++e)
-                        if (i + e < n) { T p = temp * col[i + e]; yr[l * W + e] = yr[l * W + e] + p; }
-                }
-            }
+            seg_axpy_col<T, VEC>(alpha * cf[j], V + (int64_t)j * ldv, base, n, nt, yr);
         }
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-            if (VEC && i + W <= n) {
-                typename VT<T>::vec yv;
-#pragma unroll
-                for (int e = 0; e < W; ++e) el<T>(yv, e) = yr[l * W + e];
-                vstore(y + i, yv);
-            } else {
-#pragma unroll
-                for (int e = 0; e < W; ++e)
-                    if (i + e < n) y[i + e] = yr[l * W + e];
-            }
+        seg_store<T, VEC>(y, base, n, yr);
+        if (SQ) {
+            T tot = block_tree_256(seg_dot<T, VEC>(yr, yr, base, n), lds4);
+            if (threadIdx.x == 0) seg_out[s] = tot;
         }
+    }
+}
+
+// ---- host-side launchers of the basis sweeps (the style of launch_map); segment sums go to ctx->partials, which the caller has sized ----
+// nt: stream the columns of V past the caches (a hint of the caller's: results never depend on it).
+
+// out_dev[j] = dot(V[:, j], w), j < k (SQ: and out_dev[k] = the sum of w .* w): k_multidot ((k + SQ) * nseg sums), then the level-2 finaliser
+template <typename T, bool SQ = false>
+static inline int launch_multidot(mik_ctx *ctx, int64_t n, int k, const T *V, int64_t ldv, const T *w, T *out_dev, int nt)
+{
+    const int cols = k + (SQ ? 1 : 0);
+    const int64_t nseg = mik_nseg<T>(n);
+    if (cols <= 0) return MIK_OK;
+    if (nseg == 0) {   // empty vectors: every dot is +0
+        MIK_HIP(ctx, hipMemsetAsync(out_dev, 0, sizeof(T) * cols, ctx->stream));
+        return MIK_OK;
+    }
+    const int grid = (int)std::min<int64_t>(nseg, mik_max_grid(ctx));
+    const bool vec = mik_aligned16(w) && (k == 0 || (mik_aligned16(V) && ldv % VT<T>::W == 0));
+    T *part = (T *)ctx->partials;
+    if (vec) hipLaunchKernelGGL((k_multidot<T, true, SQ>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, V, ldv, w, part, nt);
+    else hipLaunchKernelGGL((k_multidot<T, false, SQ>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, V, ldv, w, part, 0);
+    MIK_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL((k_finalize_store<T>), dim3(cols), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)part, nseg, nseg, out_dev, (const int *)nullptr);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
+// y += sum_j (alpha * cf_dev[j]) * V[:, j] (SQ: and the nseg segment sums of the new y .* y): k_gemv_n
+template <typename T, bool SQ = false>
+static inline int launch_gemv_n(mik_ctx *ctx, int64_t n, int k, const T *V, int64_t ldv, const T *cf_dev, T alpha, T *y, int nt)
+{
+    const int64_t nseg = mik_nseg<T>(n);
+    if (nseg == 0 || (k == 0 && !SQ)) return MIK_OK;
+    const int grid = (int)std::min<int64_t>(nseg, mik_max_grid(ctx));
+    const bool vec = mik_aligned16(y) && (k == 0 || (mik_aligned16(V) && ldv % VT<T>::W == 0));
+    T *part = SQ ? (T *)ctx->partials : nullptr;
+    if (vec) hipLaunchKernelGGL((k_gemv_n<T, true, SQ>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, V, ldv, cf_dev, alpha, y, part, nt);
+    else hipLaunchKernelGGL((k_gemv_n<T, false, SQ>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, V, ldv, cf_dev, alpha, y, part, 0);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
+// segment sums of all pairs of the k <= 5 columns of V, n > 0: k_gram (k * (k + 1) / 2 * nseg sums, pair-major)
+template <typename T, int K> static inline int launch_gram_k(mik_ctx *ctx, int64_t n, const T *V, int64_t ldv)
+{
+    const int64_t nseg = mik_nseg<T>(n);
+    const int grid = (int)std::min<int64_t>(nseg, mik_max_grid(ctx));
+    const bool vec = mik_aligned16(V) && (ldv % VT<T>::W == 0);
+    if (vec) hipLaunchKernelGGL((k_gram<T, true, K>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, V, ldv, (T *)ctx->partials);
+    else hipLaunchKernelGGL((k_gram<T, false, K>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, V, ldv, (T *)ctx->partials);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+template <typename T> static inline int launch_gram(mik_ctx *ctx, int64_t n, int k, const T *V, int64_t ldv)
+{
+    switch (k) {
+    case 1: return launch_gram_k<T, 1>(ctx, n, V, ldv);
+    case 2: return launch_gram_k<T, 2>(ctx, n, V, ldv);
+    case 3: return launch_gram_k<T, 3>(ctx, n, V, ldv);
+    case 4: return launch_gram_k<T, 4>(ctx, n, V, ldv);
+    default: return launch_gram_k<T, 5>(ctx, n, V, ldv);
     }
 }
 

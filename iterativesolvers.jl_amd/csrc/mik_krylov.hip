@@ -97,12 +97,6 @@ extern "C" int mik_hessenberg_ldiv(int dtype, void *H, int64_t ldh, int width, v
 // =============================================================================================
 // gemv-N and orthogonalisation
 // =============================================================================================
-// Stream the Krylov basis past the caches when it cannot stay resident anyway (k columns exceed the 256 MB
-// Infinity Cache), so that the vector being orthogonalised does.  
-template <typename T> static inline int mik_basis_nt(const mik_ctx *ctx, int64_t n, int k, int bit)
-{
-    return (double)n * (double)k * sizeof(T) > 192.0e6 ? 1 : 0;
-}
 // Cache hints of a pass of the multi-launch Modified Gram-Schmidt chain (OpMgsPass::nt: 1 = v, 2 = z, 4 = w load, 8 = w store non-temporal).
 // The column that is subtracted in this pass and not needed again is streamed; when three vectors cannot share the 256 MB Infinity Cache
 // anyway, w is streamed too (load and store), so that the column projected on in this pass -- the one the NEXT pass subtracts -- is what
@@ -117,14 +111,7 @@ static inline int mik_mgs_pass_hints(const mik_ctx *ctx, int64_t n, size_t es)
 template <typename T>
 static int gemv_n_dev(mik_ctx *ctx, int64_t n, int k, const T *V, int64_t ldv, const T *cf_dev, T alpha, T *y)
 {
-    const int64_t nseg = mik_nseg<T>(n);
-    if (nseg == 0 || k == 0) return MIK_OK;
-    const int grid = (int)std::min<int64_t>(nseg, mik_max_grid(ctx));
-    const bool vec = mik_aligned16(V) && mik_aligned16(y) && (ldv % VT<T>::W == 0);
-    if (vec) hipLaunchKernelGGL((k_gemv_n<T, true>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, V, ldv, cf_dev, alpha, y, mik_basis_nt<T>(ctx, n, k, 2));
-    else hipLaunchKernelGGL((k_gemv_n<T, false>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, V, ldv, cf_dev, alpha, y, 0);
-    MIK_LAUNCH_CHECK(ctx);
-    return MIK_OK;
+    return launch_gemv_n<T>(ctx, n, k, V, ldv, cf_dev, alpha, y, mik_basis_nt<T>(n, k));
 }
 
 // Copy k host scalars into the coefficient area of the context (device), at element `slot`.
@@ -177,18 +164,7 @@ template <typename T> static int finalize_nrm_inv(mik_ctx *ctx, int64_t nseg, T 
 template <typename T>
 static int multidot(mik_ctx *ctx, int64_t n, int k, const T *V, int64_t ldv, const T *w, T *out_dev)
 {
-    const int64_t nseg = mik_nseg<T>(n);
-    if (k <= 0) return MIK_OK;
-    if (nseg == 0) {   // empty vectors: every dot is +0
-        MIK_HIP(ctx, hipMemsetAsync(out_dev, 0, sizeof(T) * k, ctx->stream));
-        return MIK_OK;
-    }
-    const int grid = (int)std::min<int64_t>(nseg, mik_max_grid(ctx));
-    const bool vec = mik_aligned16(V) && mik_aligned16(w) && (ldv % VT<T>::W == 0);
-    if (vec) hipLaunchKernelGGL((k_multidot<T, true>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, V, ldv, w, (T *)ctx->partials, mik_basis_nt<T>(ctx, n, k, 4));
-    else hipLaunchKernelGGL((k_multidot<T, false>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, V, ldv, w, (T *)ctx->partials, 0);
-    MIK_LAUNCH_CHECK(ctx);
-    return finalize_store<T>(ctx, nseg, k, out_dev);
+    return launch_multidot<T>(ctx, n, k, V, ldv, w, out_dev, mik_basis_nt<T>(n, k));
 }
 
 // orthogonalize_and_normalize!(V[:, 1:k], w, h, method) -> nrm   -- src/orthogonalize.jl:13-79
@@ -2238,17 +2214,6 @@ extern "C" int mik_gemv_t(mik_ctx *ctx, int dtype, int64_t n, int k, const void 
 }
 
 // M = V' * V for k <= 5 columns in one pass over V -- src/bicgstabl.jl:120 (M = rs' * rs)
-template <typename T, int K> static int gram_launch(mik_ctx *ctx, int64_t n, const T *V, int64_t ldv)
-{
-    const int64_t nseg = mik_nseg<T>(n);
-    const int grid = (int)std::min<int64_t>(nseg, mik_max_grid(ctx));
-    const bool vec = mik_aligned16(V) && (ldv % VT<T>::W == 0);
-    if (vec) hipLaunchKernelGGL((k_gram<T, true, K>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, V, ldv, (T *)ctx->partials);
-    else hipLaunchKernelGGL((k_gram<T, false, K>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, V, ldv, (T *)ctx->partials);
-    MIK_LAUNCH_CHECK(ctx);
-    return MIK_OK;
-}
-
 template <typename T> static int gram_impl(mik_ctx *ctx, int64_t n, int k, const T *V, int64_t ldv, T *M)
 {
     const int np = k * (k + 1) / 2;
@@ -2259,13 +2224,7 @@ template <typename T> static int gram_impl(mik_ctx *ctx, int64_t n, int k, const
         return MIK_OK;
     }
     MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * (size_t)nseg * (size_t)np));
-    switch (k) {
-    case 1: MIK_TRY((gram_launch<T, 1>(ctx, n, V, ldv))); break;
-    case 2: MIK_TRY((gram_launch<T, 2>(ctx, n, V, ldv))); break;
-    case 3: MIK_TRY((gram_launch<T, 3>(ctx, n, V, ldv))); break;
-    case 4: MIK_TRY((gram_launch<T, 4>(ctx, n, V, ldv))); break;
-    default: MIK_TRY((gram_launch<T, 5>(ctx, n, V, ldv))); break;
-    }
+    MIK_TRY(launch_gram<T>(ctx, n, k, V, ldv));
     MIK_TRY(finalize_store<T>(ctx, nseg, np, hd));
     std::vector<T> out((size_t)np);
     MIK_TRY(coef_download<T>(ctx, 0, out.data(), np));

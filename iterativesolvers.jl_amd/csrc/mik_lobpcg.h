@@ -5,7 +5,8 @@
 //       walks ITS row and, for every entry, gathers X[column, j0 .. j0 + CB) -- per column the same products in the same ascending
 //       column order from +0 as k_spmv_rowgather, so the bits are mik_spmv's.  Operators without split-off long rows only.
 //   k_block_gram       segment sums of X[:, i] .* Y[:, j] for a TP x TQ tile of pairs  -- mul!(G, adjoint(X), Y), :262-270, :217, :375
-//       The thread / segment / wave-tree / 4-wave-sum shape of OpDot in k_map, so every pair has the bits of mik_dot after the finaliser.
+//       Written in the segment helpers of csrc/mik_kernels.h (seg_load, seg_dot, pair_put / pair_total) that k_multidot and k_gram use: the
+//       thread / segment / wave-tree / 4-wave-sum shape of OpDot in k_map, so every pair has the bits of mik_dot after the finaliser.
 //   k_block_rdiv       X <- X * inv(R), R upper triangular                       -- rdiv!, :345-355
 //   k_block_update     Pout = R * Vr (+ P * Vp); Xout = X * Vx (+ Pout)           -- update_X_P!, :629-690
 //       One lane per row: a row's values stay in registers, every product and every sum rounded on its own, columns ascending, the
@@ -108,63 +109,29 @@ __global__ __launch_bounds__(MIK_BLOCK) void k_spmm_rowgather(int n, int b, cons
 // seg_out[(j * p + i) * nseg + s] = segment sum s of X[:, i] .* Y[:, j]; blockIdx.y = tile of TP x TQ pairs
 // ---------------------------------------------------------------------------------------------
 template <typename T, bool VEC>
-__device__ __forceinline__ void gram_load(const T *__restrict__ c, int64_t base, int64_t n, T (&v)[MIK_RED_L * VT<T>::W])
-{
-    constexpr int W = VT<T>::W;
-#pragma unroll
-    for (int l = 0; l < MIK_RED_L; ++l) {
-        const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-        if (VEC && i + W <= n) {
-            auto cv = vload(c + i);
-#pragma unroll
-            for (int e = 0; e < W; ++e) v[l * W + e] = el<T>(cv, e);
-        } else {
-#pragma unroll
-            for (int e = 0; e < W; ++e) v[l * W + e] = (i + e < n) ? c[i + e] : T(0);
-        }
-    }
-}
-
-template <typename T, bool VEC>
 __global__ __launch_bounds__(MIK_BLOCK) void k_block_gram(int64_t n, int64_t nseg, int p, int q, const T *__restrict__ X, int64_t ldx,
                                                            const T *__restrict__ Y, int64_t ldy, T *__restrict__ seg_out)
 {
-    constexpr int W = VT<T>::W;
-    constexpr int L = MIK_RED_L;
     constexpr int TP = MIK_GRAM_TP, TQ = MIK_GRAM_TQ;
-    constexpr int64_t SEG = (int64_t)MIK_BLOCK * W * L;
+    constexpr int64_t SEG = (int64_t)MIK_BLOCK * SEG_REGS<T>;
     __shared__ T lds[TP * TQ][4];
     const int tiles_p = (p + TP - 1) / TP;
     const int i0 = ((int)blockIdx.y % tiles_p) * TP, j0 = ((int)blockIdx.y / tiles_p) * TQ;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const int64_t base = s * SEG + (int64_t)W * threadIdx.x;
-        T xr[TP][L * W], yr[TQ][L * W];
+        const int64_t base = s * SEG + (int64_t)VT<T>::W * threadIdx.x;
+        T xr[TP][SEG_REGS<T>], yr[TQ][SEG_REGS<T>];
 #pragma unroll
-        for (int a = 0; a < TP; ++a) gram_load<T, VEC>(X + (int64_t)min(i0 + a, p - 1) * ldx, base, n, xr[a]);
+        for (int a = 0; a < TP; ++a) seg_load<T, VEC>(X + (int64_t)min(i0 + a, p - 1) * ldx, base, n, 0, xr[a]);   // columns past the block: the last one again
 #pragma unroll
-        for (int c = 0; c < TQ; ++c) gram_load<T, VEC>(Y + (int64_t)min(j0 + c, q - 1) * ldy, base, n, yr[c]);
+        for (int c = 0; c < TQ; ++c) seg_load<T, VEC>(Y + (int64_t)min(j0 + c, q - 1) * ldy, base, n, 0, yr[c]);
 #pragma unroll
         for (int c = 0; c < TQ; ++c)
 #pragma unroll
-            for (int a = 0; a < TP; ++a) {
-                T acc = T(0);
-#pragma unroll
-                for (int e = 0; e < L * W; ++e) {
-                    const int64_t i = base + (int64_t)(e / W) * MIK_BLOCK * W + (e % W);
-                    if (i < n) { const T pr = xr[a][e] * yr[c][e]; acc = acc + pr; }
-                }
-                acc = wave_tree(acc);
-                if (lane == 0) lds[c * TP + a][w] = acc;
-            }
+            for (int a = 0; a < TP; ++a) pair_put(seg_dot<T, VEC>(xr[a], yr[c], base, n), lds[c * TP + a]);
         __syncthreads();
         if (threadIdx.x < TP * TQ) {
             const int a = (int)threadIdx.x % TP, c = (int)threadIdx.x / TP;
-            if (i0 + a < p && j0 + c < q) {
-                T tot = lds[threadIdx.x][0];
-                tot = tot + lds[threadIdx.x][1]; tot = tot + lds[threadIdx.x][2]; tot = tot + lds[threadIdx.x][3];
-                seg_out[((int64_t)(j0 + c) * p + (i0 + a)) * nseg + s] = tot;
-            }
+            if (i0 + a < p && j0 + c < q) seg_out[((int64_t)(j0 + c) * p + (i0 + a)) * nseg + s] = pair_total(lds[threadIdx.x]);
         }
         __syncthreads();
     }

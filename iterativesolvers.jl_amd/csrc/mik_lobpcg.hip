@@ -3,48 +3,13 @@
 //   mik_block_gram     G = X' * Y, every entry with the bits of mik_dot
 //   mik_block_rdiv     X <- X * inv(R), R upper triangular (CholQR)
 //   mik_block_update   the Ritz update of one block triple in one pass
-// Kernels: csrc/mik_lobpcg.h.  Nothing an existing entry launches is touched.
+// Kernels: csrc/mik_lobpcg.h; k_block_gram is written in the segment helpers of csrc/mik_kernels.h that k_multidot / k_gram use.
 #include <algorithm>
 #include <vector>
 
 #include "mik_lobpcg.h"
 
 namespace {
-
-bool blk_overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
-size_t blk_bytes(size_t es, int64_t n, int cols, int64_t ld)
-{
-    return (n > 0 && cols > 0) ? es * ((size_t)(cols - 1) * (size_t)ld + (size_t)n) : 0;
-}
-
-// A small host matrix (rows x cols, leading dimension ldm), packed to leading dimension `rows`, at the head of ctx->partials.  Through the
-// context's pinned staging area when it fits, else straight from a packed copy with a wait: either way the caller's array has been read
-// when this returns.
-template <typename T>
-int blk_stage(mik_ctx *ctx, const T *M, int rows, int cols, int64_t ldm, T **dev_out)
-{
-    const size_t bytes = sizeof(T) * (size_t)rows * (size_t)cols;
-    MIK_TRY(mik_ensure_partials(ctx, bytes));
-    T *Md = (T *)ctx->partials;
-    if (bytes <= mik_ctx::COEF_BYTES) {
-        MIK_HIP(ctx, mik_wait(ctx));                        // staging buffer must be idle
-        T *st = (T *)ctx->coef_host;
-        for (int j = 0; j < cols; ++j) memcpy(st + (size_t)j * rows, M + (size_t)j * ldm, sizeof(T) * (size_t)rows);
-        MIK_HIP(ctx, hipMemcpyAsync(Md, st, bytes, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        std::vector<T> pk((size_t)rows * (size_t)cols);
-        for (int j = 0; j < cols; ++j) memcpy(pk.data() + (size_t)j * rows, M + (size_t)j * ldm, sizeof(T) * (size_t)rows);
-        MIK_HIP(ctx, hipMemcpyAsync(Md, pk.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-        MIK_HIP(ctx, mik_wait(ctx));
-    }
-    *dev_out = Md;
-    return MIK_OK;
-}
 
 unsigned row_grid(mik_ctx *ctx, int64_t n)
 {
@@ -118,7 +83,7 @@ template <typename T>
 int rdiv_impl(mik_ctx *ctx, int64_t n, int s, const T *R, int64_t ldr, T *X, int64_t ldx)
 {
     T *Rd = nullptr;
-    MIK_TRY(blk_stage<T>(ctx, R, s, s, ldr, &Rd));
+    MIK_TRY(mik_stage_small<T>(ctx, R, s, s, ldr, &Rd));
     if (s <= 4) return rdiv_launch<T, 4>(ctx, n, s, Rd, X, ldx);
     if (s <= 8) return rdiv_launch<T, 8>(ctx, n, s, Rd, X, ldx);
     if (s <= 16) return rdiv_launch<T, 16>(ctx, n, s, Rd, X, ldx);
@@ -141,7 +106,7 @@ int update_impl(mik_ctx *ctx, int64_t n, int sx, int b1, int b2, const T *X, int
                 const T *V, int64_t ldv, T *Xout, int64_t ldxo, T *Pout, int64_t ldpo)
 {
     T *Vd = nullptr;
-    MIK_TRY(blk_stage<T>(ctx, V, sx + b1 + b2, sx, ldv, &Vd));
+    MIK_TRY(mik_stage_small<T>(ctx, V, sx + b1 + b2, sx, ldv, &Vd));
     if (sx <= 4) return update_launch<T, 4>(ctx, n, sx, b1, b2, X, ldx, R, ldr, P, ldp, Vd, Xout, ldxo, Pout, ldpo);
     if (sx <= 8) return update_launch<T, 8>(ctx, n, sx, b1, b2, X, ldx, R, ldr, P, ldp, Vd, Xout, ldxo, Pout, ldpo);
     if (sx <= 16) return update_launch<T, 16>(ctx, n, sx, b1, b2, X, ldx, R, ldr, P, ldp, Vd, Xout, ldxo, Pout, ldpo);
@@ -157,7 +122,7 @@ extern "C" int mik_spmm(mik_ctx *ctx, const mik_csr *A, int b, const void *X, in
     if (b == 0) return MIK_OK;
     if (!X || !Y || ldx < A->n_cols || ldy < A->n_rows) return mik_fail(ctx, MIK_ERR_INVALID, "mik_spmm: null pointer or leading dimension too small");
     const size_t es = mik_dtype_size(A->dtype);
-    if (blk_overlap(X, blk_bytes(es, A->n_cols, b, ldx), Y, blk_bytes(es, A->n_rows, b, ldy)))
+    if (mik_overlap(X, mik_block_bytes(es, A->n_cols, b, ldx), Y, mik_block_bytes(es, A->n_rows, b, ldy)))
         return mik_fail(ctx, MIK_ERR_INVALID, "mik_spmm: Y overlaps X");
     if (A->dtype == MIK_F64) return spmm_impl<double>(ctx, A, b, (const double *)X, ldx, (double *)Y, ldy);
     return spmm_impl<float>(ctx, A, b, (const float *)X, ldx, (float *)Y, ldy);
@@ -196,12 +161,12 @@ extern "C" int mik_block_update(mik_ctx *ctx, int dtype, int64_t n, int sx, int 
     if (n == 0) return MIK_OK;
     const size_t es = mik_dtype_size(dtype);
     const void *in[3] = {X, R, P};
-    const size_t inb[3] = {blk_bytes(es, n, sx, ldx), blk_bytes(es, n, b1, ldr), blk_bytes(es, n, b2, ldp)};
-    const size_t xob = blk_bytes(es, n, sx, ldxo), pob = blk_bytes(es, n, b1 ? sx : 0, ldpo);
+    const size_t inb[3] = {mik_block_bytes(es, n, sx, ldx), mik_block_bytes(es, n, b1, ldr), mik_block_bytes(es, n, b2, ldp)};
+    const size_t xob = mik_block_bytes(es, n, sx, ldxo), pob = mik_block_bytes(es, n, b1 ? sx : 0, ldpo);
     for (int i = 0; i < 3; ++i)
-        if (blk_overlap(in[i], inb[i], Xout, xob) || blk_overlap(in[i], inb[i], Pout, pob))
+        if (mik_overlap(in[i], inb[i], Xout, xob) || mik_overlap(in[i], inb[i], Pout, pob))
             return mik_fail(ctx, MIK_ERR_INVALID, "mik_block_update: an output overlaps an input");
-    if (blk_overlap(Xout, xob, Pout, pob)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_block_update: Xout overlaps Pout");
+    if (mik_overlap(Xout, xob, Pout, pob)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_block_update: Xout overlaps Pout");
     if (dtype == MIK_F64)
         return update_impl<double>(ctx, n, sx, b1, b2, (const double *)X, ldx, (const double *)R, ldr, (const double *)P, ldp, (const double *)V, ldv,
                                    (double *)Xout, ldxo, (double *)Pout, ldpo);

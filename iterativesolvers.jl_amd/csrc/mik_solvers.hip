@@ -184,17 +184,6 @@ __global__ __launch_bounds__(MIK_FIN_THREADS) void k_bicg_fin_norm(const T *__re
     }
 }
 
-template <typename T, int K> int gram_partials(mik_ctx *ctx, int64_t n, const T *V, int64_t ldv)
-{
-    const int64_t nseg = mik_nseg<T>(n);
-    const int grid = (int)std::min<int64_t>(nseg, mik_max_grid(ctx));
-    const bool vec = mik_aligned16(V) && (ldv % VT<T>::W == 0);
-    if (vec) hipLaunchKernelGGL((k_gram<T, true, K>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, V, ldv, (T *)ctx->partials);
-    else hipLaunchKernelGGL((k_gram<T, false, K>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, V, ldv, (T *)ctx->partials);
-    MIK_LAUNCH_CHECK(ctx);
-    return MIK_OK;
-}
-
 }  // namespace
 
 struct mik_bicgstab {
@@ -354,12 +343,7 @@ template <typename T> static int bicg_step_impl(mik_bicgstab *it, T *residual)
         }
     }
     // MR part: M = rs' * rs (:120) in one pass, gamma (:123-125), the three updates and the norm (:127-132) in one sweep
-    switch (l + 1) {
-    case 2: MIK_TRY((gram_partials<T, 2>(ctx, n, rs, it->ldr))); break;
-    case 3: MIK_TRY((gram_partials<T, 3>(ctx, n, rs, it->ldr))); break;
-    case 4: MIK_TRY((gram_partials<T, 4>(ctx, n, rs, it->ldr))); break;
-    default: MIK_TRY((gram_partials<T, 5>(ctx, n, rs, it->ldr))); break;
-    }
+    MIK_TRY(launch_gram<T>(ctx, n, l + 1, (const T *)rs, it->ldr));
     if (lean) {
         hipLaunchKernelGGL((k_bicg_gram_gamma<T>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)ctx->partials, nseg, np, l, d, it->mirror);
         MIK_LAUNCH_CHECK(ctx);

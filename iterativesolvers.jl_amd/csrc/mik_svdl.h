@@ -1,5 +1,5 @@
-// mik_svdl.h -- kernels behind svdl (src/svdl.jl): the basis rotation of the thick restart and the two sweeps of one classical
-// Gram-Schmidt pass with the squared norm of the vector riding on each of them.
+// mik_svdl.h -- the kernel of svdl (src/svdl.jl) that is its own: the basis rotation of the thick restart.  (The two sweeps of a classical
+// Gram-Schmidt pass with the squared norm riding on them are the SQ instances of k_multidot / k_gemv_n, csrc/mik_kernels.h.)
 //
 //   k_basis_rotate   Y[:, 0:l] = V[:, 0:k] * F[0:k, 0:l]            -- src/svdl.jl:384, :392, :470, :471, :231, :237
 //       A lane owns W = 16 B / sizeof(T) consecutive rows and LB output columns: W * LB accumulators in registers.  It walks the k
@@ -7,9 +7,6 @@
 //       workgroup staged in LDS (every lane reads the same address: a broadcast, no bank conflict).  Every product and every sum is
 //       rounded on its own, columns ascending, the first product opening the sum -- an output element depends on its own row only, so
 //       the bits do not depend on the launch shape.  blockIdx.y selects the block of LB output columns (l > 32 reads V twice).
-//   k_multidot_sq    k_multidot (h = Q' q) + the segment sums of q .* q   -- src/svdl.jl:569-570 (oldqnorm and Q'q from one read of q)
-//   k_gemv_n_sq      k_gemv_n (q += alpha * Q h) + the segment sums of the new q .* q   -- :570-571 (q -= Q h and norm(q) from one sweep)
-//       Both keep the thread / segment / tree shape of OpDot in k_map, so each squared norm has the bits mik_nrm2 would give.
 #pragma once
 #include "mik_kernels.h"
 
@@ -99,123 +96,6 @@ __global__ __launch_bounds__(MIK_BLOCK) void k_basis_rotate(int64_t n, int k, in
                 }
             }
         }
-    }
-}
-
-// k_multidot with one more reduced column: seg_out[j][s] = segment sum of Q[:, j] .* q for j < k, seg_out[k][s] = that of q .* q.
-template <typename T, bool VEC>
-__global__ __launch_bounds__(MIK_BLOCK) void k_multidot_sq(int64_t n, int64_t nseg, int k, const T *__restrict__ Q, int64_t ldq,
-                                                            const T *__restrict__ q, T *__restrict__ seg_out /* [k + 1][nseg] */, int nt)
-{
-    constexpr int W = VT<T>::W;
-    constexpr int L = MIK_RED_L;
-    constexpr int64_t SEG = (int64_t)MIK_BLOCK * W * L;
-    __shared__ T lds4[4];
-    for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const int64_t base = s * SEG + (int64_t)W * threadIdx.x;
-        T wr[L * W];
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-            if (VEC && i + W <= n) {
-                auto wv = vload(q + i);
-#pragma unroll
-                for (int e = 0; e < W; ++e) wr[l * W + e] = el<T>(wv, e);
-            } else {
-#pragma unroll
-                for (int e = 0; e < W; ++e) wr[l * W + e] = (i + e < n) ? q[i + e] : T(0);
-            }
-        }
-        for (int j = 0; j < k; ++j) {
-            const T *__restrict__ col = Q + (int64_t)j * ldq;
-            T acc = T(0);
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-                if (VEC && i + W <= n) {
-                    auto cv = nt ? vload_nt(col + i) : vload(col + i);
-#pragma unroll
-                    for (int e = 0; e < W; ++e) { T p = el<T>(cv, e) * wr[l * W + e]; acc = acc + p; }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < W; ++e)
-                        if (i + e < n) { T p = col[i + e] * wr[l * W + e]; acc = acc + p; }
-                }
-            }
-            T tot = block_tree_256(acc, lds4);
-            if (threadIdx.x == 0) seg_out[(int64_t)j * nseg + s] = tot;
-        }
-        T acc = T(0);
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-#pragma unroll
-            for (int e = 0; e < W; ++e)
-                if (i + e < n) { T p = wr[l * W + e] * wr[l * W + e]; acc = acc + p; }
-        }
-        T tot = block_tree_256(acc, lds4);
-        if (threadIdx.x == 0) seg_out[(int64_t)k * nseg + s] = tot;
-    }
-}
-
-// k_gemv_n with the segment sums of the updated y .* y: seg_out[s].
-template <typename T, bool VEC>
-__global__ __launch_bounds__(MIK_BLOCK) void k_gemv_n_sq(int64_t n, int64_t nseg, int k, const T *__restrict__ V, int64_t ldv,
-                                                          const T *__restrict__ cf, T alpha, T *__restrict__ y, T *__restrict__ seg_out, int nt)
-{
-    constexpr int W = VT<T>::W;
-    constexpr int L = MIK_RED_L;
-    constexpr int64_t SEG = (int64_t)MIK_BLOCK * W * L;
-    __shared__ T lds4[4];
-    for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const int64_t base = s * SEG + (int64_t)W * threadIdx.x;
-        T yr[L * W];
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-            if (VEC && i + W <= n) {
-                auto yv = vload<T>(y + i);
-#pragma unroll
-                for (int e = 0; e < W; ++e) yr[l * W + e] = el<T>(yv, e);
-            } else {
-#pragma unroll
-                for (int e = 0; e < W; ++e) yr[l * W + e] = (i + e < n) ? y[i + e] : T(0);
-            }
-        }
-        for (int j = 0; j < k; ++j) {
-            const T *__restrict__ col = V + (int64_t)j * ldv;
-            const T temp = alpha * cf[j];
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-                if (VEC && i + W <= n) {
-                    auto cv = nt ? vload_nt(col + i) : vload(col + i);
-#pragma unroll
-                    for (int e = 0; e < W; ++e) { T p = temp * el<T>(cv, e); yr[l * W + e] = yr[l * W + e] + p; }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < W; ++e)
-                        if (i + e < n) { T p = temp * col[i + e]; yr[l * W + e] = yr[l * W + e] + p; }
-                }
-            }
-        }
-        T acc = T(0);
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-            if (VEC && i + W <= n) {
-                typename VT<T>::vec yv;
-#pragma unroll
-                for (int e = 0; e < W; ++e) { el<T>(yv, e) = yr[l * W + e]; T p = yr[l * W + e] * yr[l * W + e]; acc = acc + p; }
-                vstore(y + i, yv);
-            } else {
-#pragma unroll
-                for (int e = 0; e < W; ++e)
-                    if (i + e < n) { y[i + e] = yr[l * W + e]; T p = yr[l * W + e] * yr[l * W + e]; acc = acc + p; }
-            }
-        }
-        T tot = block_tree_256(acc, lds4);
-        if (threadIdx.x == 0) seg_out[s] = tot;
     }
 }
 

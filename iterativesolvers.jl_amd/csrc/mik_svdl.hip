@@ -1,10 +1,10 @@
 // mik_svdl.hip -- the two device entries svdl (src/svdl.jl) needs beyond the Krylov helpers of mik_krylov.hip:
 //   mik_basis_rotate   Y = V[:, 1:k] * F[:, 1:l], the basis rotation of thickrestart! / harmonicrestart! and the singular vectors
 //   mik_svdl_reorth    the double classical Gram-Schmidt of extend! with its norm test, and the normalisation that follows it
-// Kernels: csrc/mik_svdl.h.  Nothing an existing iterable launches is touched.
+// Kernels: k_basis_rotate (csrc/mik_svdl.h); the two sweeps of mik_svdl_reorth are k_multidot / k_gemv_n themselves (csrc/mik_kernels.h,
+// SQ = true: the squared norm rides on the sweep), launched as mik_gemv_t / mik_gemv_n launch them.
 #include <algorithm>
 #include <cmath>
-#include <vector>
 
 #include "mik_svdl.h"
 
@@ -27,22 +27,8 @@ int rotate_launch(mik_ctx *ctx, int64_t n, int k, int l, const T *V, int64_t ldv
 template <typename T>
 int rotate_impl(mik_ctx *ctx, int64_t n, int k, int l, const T *V, int64_t ldv, const T *F, int64_t ldf, T *Y, int64_t ldy)
 {
-    // F, packed to leading dimension k, goes to the device through the context's pinned staging area when it fits (the caller's array
-    // may be pageable or pinned: either way it has been read when the call returns), else straight from the caller's memory with a wait.
-    const size_t bytes = sizeof(T) * (size_t)k * (size_t)l;
-    MIK_TRY(mik_ensure_partials(ctx, bytes));
-    T *Fd = (T *)ctx->partials;
-    if (bytes <= mik_ctx::COEF_BYTES) {
-        MIK_HIP(ctx, mik_wait(ctx));                        // staging buffer must be idle
-        T *st = (T *)ctx->coef_host;
-        for (int j = 0; j < l; ++j) memcpy(st + (size_t)j * k, F + (size_t)j * ldf, sizeof(T) * (size_t)k);
-        MIK_HIP(ctx, hipMemcpyAsync(Fd, st, bytes, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        std::vector<T> pk((size_t)k * (size_t)l);
-        for (int j = 0; j < l; ++j) memcpy(pk.data() + (size_t)j * k, F + (size_t)j * ldf, sizeof(T) * (size_t)k);
-        MIK_HIP(ctx, hipMemcpyAsync(Fd, pk.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-        MIK_HIP(ctx, mik_wait(ctx));
-    }
+    T *Fd = nullptr;
+    MIK_TRY(mik_stage_small<T>(ctx, F, k, l, ldf, &Fd));
     if (l <= 8) return rotate_launch<T, 8>(ctx, n, k, l, V, ldv, Fd, Y, ldy);
     if (l <= 16) return rotate_launch<T, 16>(ctx, n, k, l, V, ldv, Fd, Y, ldy);
     return rotate_launch<T, 32>(ctx, n, k, l, V, ldv, Fd, Y, ldy);
@@ -64,9 +50,7 @@ int reorth_impl(mik_ctx *ctx, int64_t n, int k, const T *Q, int64_t ldq, T *q, T
     *passes_out = 1;
     if (n == 0) { *beta_out = T(0); return MIK_OK; }
     const int64_t nseg = mik_nseg<T>(n);
-    const int grid = (int)std::min<int64_t>(nseg, mik_max_grid(ctx));
-    const bool vec = mik_aligned16(q) && (k == 0 || (mik_aligned16(Q) && ldq % VT<T>::W == 0));
-    const int nt = (double)n * (double)k * sizeof(T) > 192.0e6 ? 1 : 0;      // the basis cannot stay in the Infinity Cache: stream it (as mik_gemv_t / mik_gemv_n do)
+    const int nt = mik_basis_nt<T>(n, k);
     T *hd = (T *)ctx->coef;
     T old = T(0), nw = T(0);
     int passes = 0;
@@ -74,21 +58,13 @@ int reorth_impl(mik_ctx *ctx, int64_t n, int k, const T *Q, int64_t ldq, T *q, T
         ++passes;
         // sweep 1: h = Q' q, and on the first pass oldqnorm from the same read of q   -- src/svdl.jl:569-570 (:572)
         MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * (size_t)nseg * (size_t)(k + 1)));
-        T *part = (T *)ctx->partials;
-        if (vec) hipLaunchKernelGGL((k_multidot_sq<T, true>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, Q, ldq, (const T *)q, part, nt);
-        else hipLaunchKernelGGL((k_multidot_sq<T, false>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, Q, ldq, (const T *)q, part, 0);
-        MIK_LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL((k_finalize_store<T>), dim3(k + 1), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)part, nseg, nseg, hd, (const int *)nullptr);
-        MIK_LAUNCH_CHECK(ctx);
+        MIK_TRY((launch_multidot<T, true>(ctx, n, k, Q, ldq, q, hd, nt)));
         if (passes == 1) MIK_TRY(sumsq_to_norm<T>(ctx, n, q, hd + k, &old));       // q is still the old vector if the scaled recomputation is needed
         if (k == 0) { nw = old; break; }
         // sweep 2: q -= Q h, and norm(q) from the same sweep   -- :570-571 (:572, :576)
         MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * (size_t)nseg));
-        part = (T *)ctx->partials;
-        if (vec) hipLaunchKernelGGL((k_gemv_n_sq<T, true>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, Q, ldq, (const T *)hd, T(-1), q, part, nt);
-        else hipLaunchKernelGGL((k_gemv_n_sq<T, false>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, k, Q, ldq, (const T *)hd, T(-1), q, part, 0);
-        MIK_LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL((k_finalize_store<T>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)part, nseg, (int64_t)0, hd + k + 1, (const int *)nullptr);
+        MIK_TRY((launch_gemv_n<T, true>(ctx, n, k, Q, ldq, hd, T(-1), q, nt)));
+        hipLaunchKernelGGL((k_finalize_store<T>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)ctx->partials, nseg, (int64_t)0, hd + k + 1, (const int *)nullptr);
         MIK_LAUNCH_CHECK(ctx);
         MIK_TRY(sumsq_to_norm<T>(ctx, n, q, hd + k + 1, &nw));
         if (passes == 2 || !(nw <= alpha * old)) break;                             // :571
@@ -99,12 +75,6 @@ int reorth_impl(mik_ctx *ctx, int64_t n, int k, const T *Q, int64_t ldq, T *q, T
     if (nw == T(0)) return MIK_OK;                          // the caller decides (the reference would fill q with Inf / NaN)
     OpScal<T> sc{q, coef_val<T>(T(1) / nw)};               // :577
     return launch_map<T>(ctx, n, sc, mik_aligned16(q), (T *)nullptr, nullptr);
-}
-
-bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
 }
 
 }  // namespace
@@ -118,7 +88,7 @@ extern "C" int mik_basis_rotate(mik_ctx *ctx, int dtype, int64_t n, int k, int l
     if (!F || ldf < k || ldv < n || ldy < n || (n && (!V || !Y))) return mik_fail(ctx, MIK_ERR_INVALID, "mik_basis_rotate: null pointer or leading dimension too small");
     if (n == 0) return MIK_OK;
     const size_t es = mik_dtype_size(dtype);
-    if (ranges_overlap(V, es * ((size_t)(k - 1) * (size_t)ldv + (size_t)n), Y, es * ((size_t)(l - 1) * (size_t)ldy + (size_t)n)))
+    if (mik_overlap(V, mik_block_bytes(es, n, k, ldv), Y, mik_block_bytes(es, n, l, ldy)))
         return mik_fail(ctx, MIK_ERR_INVALID, "mik_basis_rotate: Y overlaps V");
     if (dtype == MIK_F64) return rotate_impl<double>(ctx, n, k, l, (const double *)V, ldv, (const double *)F, ldf, (double *)Y, ldy);
     return rotate_impl<float>(ctx, n, k, l, (const float *)V, ldv, (const float *)F, ldf, (float *)Y, ldy);

@@ -32,7 +32,7 @@ The case that launches each template instance (both element types each):
 
 blk_rot_row's unrolled-by-4 loop starts at column 1, so k columns leave (k - 1) % 4 for its tail: the shapes of test_update_every_width give
 k = 2, 5, 6, 7, 9, 12, 16, 17, 18, 19, 30, 31 and 1 -- every remainder, with and without a trip of the unrolled loop.  The host staging
-(blk_stage) switches at 8192 bytes: in Float64 (18, 18, 18) stages 54 x 18 x 8 = 7776 bytes through the pinned area, (19, 19, 19) 8664
+(mik_stage_small) switches at 8192 bytes: in Float64 (18, 18, 18) stages 54 x 18 x 8 = 7776 bytes through the pinned area, (19, 19, 19) 8664
 bytes from a packed copy; s = 31 / 32 of rdiv sit below / at the switch.  Both are also called with leading dimensions larger than the
 matrix, the padding NaN."""
 import ctypes as C
