@@ -649,6 +649,50 @@ int mik_forward_sub(mik_stationary *S, const void *alpha, void *x, const void *b
 /* backward_sub!(F, x) -- :109-124; backward_sub!(alpha, F, x, beta, y) -- :126-142.  As mik_forward_sub. */
 int mik_backward_sub(mik_stationary *S, const void *alpha, void *x, const void *beta, const void *y, int scalar_dtype);
 
+/* ---- dense stationary methods: jacobi / gauss_seidel / sor / ssor on an AbstractMatrix (src/stationary.jl:31-263) ----------------
+ * One entry per whole iteration of the four dense iterables (added without a version bump, additive); real MIK_F64 / MIK_F32.  A is a
+ * DEVICE n x n column-major matrix with leading dimension ld >= n, read at every step (the handle keeps no copy of it; A must outlive
+ * the handle).  The reference's column loops give every row one serial order of subtractions; with d = A[r,r] and every
+ * `acc = acc - (A[r,c] * x[c])` rounded twice (no FMA) they are, row by row:
+ *   jacobi        next[r] = b[r] - sum over c != r ascending (old x);  x[r] = next[r] / d                                 -- :48-72
+ *   gauss_seidel  t = b[r] - sum over c > r ascending (old x) - sum over c < r ascending (new x);  x[r] = t / d          -- :108-129
+ *   sor           tmp[r] = that t;  x[r] = x[r] + omega * (tmp[r] / d - x[r])                                            -- :167-188
+ *   ssor          the sor sweep, giving x'; then tmp[r] = b[r] - sum over c < r DESCENDING - sum over c > r DESCENDING, every product
+ *                 with x' (:254-260 subtracts column col before it updates x[col]);  x[r] = x'[r] + omega * (tmp[r] / d - x'[r])  -- :227-263
+ * A lane owns a row and walks its columns in that order; a row's chain is never split, so a sweep is n-fold parallel and no more.
+ * The strict-lower phase is a blocked forward substitution in the PANEL form: ceil(n / W) launches following each other on the
+ * stream, launch K subtracting panel K - 1's W columns from the rows at or below panel K and then solving panel K's diagonal block
+ * (W serial steps: divide or relax, broadcast, subtract below) in the one workgroup that owns it.  No workgroup waits for another.
+ * omega is a HOST scalar of scalar_dtype, as for mik_forward_sub: Float32 data with a MIK_F64 omega evaluates the inner difference in
+ * Float32, the product and the sum in Float64, and rounds once at the store; an Int omega is passed in the element type.
+ * x, next / tmp and b are DEVICE n-vectors that must not overlap (MIK_ERR_INVALID).  The steps are asynchronous on the ctx stream;
+ * the handle owns the copy of the old x and the Gauss-Seidel accumulators, nothing is allocated per step. */
+typedef struct mik_dense_stationary mik_dense_stationary;
+enum { MIK_DENSE_AUTO = 0, MIK_DENSE_PANEL = 1, MIK_DENSE_CHAINED = 2 };
+typedef struct mik_dense_plan {
+    int form;         /* MIK_DENSE_AUTO (= the panel form) / MIK_DENSE_PANEL / MIK_DENSE_CHAINED (a single-launch forward substitution whose
+                       * workgroups hand x on to each other: not built, MIK_ERR_NOTIMPL) */
+    int spin_limit;   /* bound of a chained launch's waits, 0 = default; unused by the panel form */
+} mik_dense_plan;
+/* check_diag(A) (:6-12) on the device + the handle's two n-vectors.  plan may be NULL (= MIK_DENSE_AUTO).  MIK_ERR_SINGULAR with
+ * *singular_col = the first 1-based i with iszero(A[i,i]) (-0.0 included); MIK_ERR_MISMATCH for ld < n or n < 1.  Synchronises. */
+int mik_dense_stationary_create(mik_ctx *ctx, const void *A, int64_t n, int64_t ld, int dtype, const mik_dense_plan *plan,
+                                int64_t *singular_col, mik_dense_stationary **out);
+int mik_dense_stationary_destroy(mik_dense_stationary *S);
+/* panel_w: W; rows_per_workgroup: rows a workgroup of the row-owned sweep and of a panel launch owns; launches_forward: launches of one
+ * forward substitution; form: the form in use (MIK_DENSE_PANEL); gave_up: 1 once a chained launch gave up (always 0: there is none);
+ * bytes: device memory held.  Any pointer may be NULL. */
+int mik_dense_stationary_info(const mik_dense_stationary *S, int64_t *panel_w, int64_t *rows_per_workgroup, int64_t *launches_forward,
+                              int *form, int *gave_up, int64_t *bytes);
+/* One iteration of DenseJacobiIterable -- :48-72.  next keeps the undivided values. */
+int mik_dense_jacobi_step(mik_dense_stationary *S, void *x, void *next, const void *b);
+/* One iteration of DenseGaussSeidelIterable -- :108-129, in place in x. */
+int mik_dense_gs_step(mik_dense_stationary *S, void *x, const void *b);
+/* One iteration of DenseSORIterable -- :167-188.  tmp keeps the accumulators the divisions read. */
+int mik_dense_sor_step(mik_dense_stationary *S, void *x, void *tmp, const void *b, const void *omega, int scalar_dtype);
+/* One iteration of DenseSSORIterable -- :227-263.  tmp keeps the accumulators of the backward half. */
+int mik_dense_ssor_step(mik_dense_stationary *S, void *x, void *tmp, const void *b, const void *omega, int scalar_dtype);
+
 /* ---- svdl: Golub-Kahan-Lanczos bidiagonalisation with thick restart (src/svdl.jl) ------------------------------------------
  * The Lanczos loop of extend! (:542-609) runs on mik_spmv (A and its adjoint as two operators), mik_gemv_t / mik_gemv_n and the fused
  * sweeps above; the k x k SVD of a restart stays on the host.  Two things no entry above does in one pass (added without a version bump,

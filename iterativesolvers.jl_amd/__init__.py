@@ -6,7 +6,8 @@ The directory name (``iterativesolvers.jl_amd``) is not a Python identifier; loa
   csrc/      hand-written HIP kernels (gfx950) + the C ABI of include/mik.h  -> libmik.so
   _lib.py    ctypes binding of that ABI (fails loudly when the library is missing)
   api.py     host-side mirror of the reference interface (cg, cg_, gmres, gmres_, iterables ...): SURVEY section 8 rows only
-  stationary.py  jacobi / gauss_seidel / sor / ssor and their iterables (src/stationary_sparse.jl)
+  stationary.py  jacobi / gauss_seidel / sor / ssor and their iterables on a HipCSR (src/stationary_sparse.jl)
+  stationary_dense.py  the same four on a dense HipMatrix (src/stationary.jl), and the public names that dispatch between the two
   svdl.py    svdl: Golub-Kahan-Lanczos SVD with thick restart (src/svdl.jl) on a HipCSR uploaded with its adjoint
   lobpcg.py  lobpcg: block eigensolver (src/lobpcg.jl) on HipCSR operators, every sweep on a block of columns
   extras.py  solvers outside the scope contract (IDR(s), LSQR, LSMR, QMR, power method); kept apart, unjudged
@@ -26,8 +27,10 @@ from .api import (CGIterable, CGStateVariables, ClassicalGramSchmidt, Convergenc
                   gemv_t_, lu_solve_, ChebyshevIterable, chebyshev, chebyshev_, chebyshev_iterable_, MINRESIterable, minres, minres_,
                   minres_iterable_, givens_algorithm, axpy_dot_, axpy2_nrm2_, gram_, LinearOperator)
 from .stationary import (GaussSeidelIterable, JacobiIterable, SingularException, SORIterable, SSORIterable,   # noqa: F401
-                         StationaryOperator, gauss_seidel, gauss_seidel_, gauss_seidel_iterable, jacobi, jacobi_,
-                         jacobi_iterable, sor, sor_, sor_iterable, ssor, ssor_, ssor_iterable)
+                         StationaryOperator)
+from .stationary_dense import (DenseGaussSeidelIterable, DenseJacobiIterable, DenseSORIterable, DenseSSORIterable,   # noqa: F401
+                               DenseStationaryOperator, gauss_seidel, gauss_seidel_, gauss_seidel_iterable, jacobi, jacobi_,
+                               jacobi_iterable, sor, sor_, sor_iterable, ssor, ssor_, ssor_iterable)   # dispatch: HipCSR -> stationary.py
 from .svdl import (BrokenArrowBidiagonal, PartialFactorization, svdl, svdl_method_, isconverged, build, thickrestart_,   # noqa: F401
                    harmonicrestart_, extend_, ArgumentError, BoundsError, SvdlBreakdown, SVD)
 from .lobpcg import (LOBPCGIterator, LOBPCGResults, LOBPCGState, LobpcgCholeskyError, LobpcgRefusal, lobpcg, lobpcg_)   # noqa: F401

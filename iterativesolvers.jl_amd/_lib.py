@@ -66,6 +66,14 @@ class MikPartition(C.Structure):
                 ("halo", HALO_FN), ("reduce", REDUCE_FN), ("user", C.c_void_p), ("link", C.c_void_p)]
 
 
+class MikDensePlan(C.Structure):
+    """include/mik.h mik_dense_plan"""
+    _fields_ = [("form", C.c_int), ("spin_limit", C.c_int)]
+
+
+MIK_DENSE_AUTO, MIK_DENSE_PANEL, MIK_DENSE_CHAINED = 0, 1, 2
+
+
 # name -> (restype, argtypes); mirrors include/mik.h one to one
 SIGNATURES = {
     "mik_abi_version": (C.c_int, []),
@@ -205,6 +213,13 @@ SIGNATURES = {
     "mik_gs_multiply": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mik_forward_sub": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
     "mik_backward_sub": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "mik_dense_stationary_create": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.POINTER(MikDensePlan), _i64p, C.POINTER(_vp)]),
+    "mik_dense_stationary_destroy": (C.c_int, [_vp]),
+    "mik_dense_stationary_info": (C.c_int, [_vp, _i64p, _i64p, _i64p, _ip, _ip, _i64p]),
+    "mik_dense_jacobi_step": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "mik_dense_gs_step": (C.c_int, [_vp, _vp, _vp]),
+    "mik_dense_sor_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "mik_dense_ssor_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
     "mik_basis_rotate": (C.c_int, [_vp, C.c_int, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64]),
     "mik_svdl_reorth": (C.c_int, [_vp, C.c_int, _i64, C.c_int, _vp, _i64, _vp, _vp, _vp, C.POINTER(C.c_int)]),
     "mik_spmm": (C.c_int, [_vp, _vp, C.c_int, _vp, _i64, _vp, _i64]),

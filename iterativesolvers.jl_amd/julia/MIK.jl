@@ -1125,4 +1125,150 @@ IterativeSolvers.gauss_seidel(A::HipCSR{T}, b::HipVector{T}; kwargs...) where {T
 IterativeSolvers.sor(A::HipCSR{T}, b::HipVector{T}, ω::Real; kwargs...) where {T} = IterativeSolvers.sor!(IterativeSolvers.zerox(A, b), A, b, ω; kwargs...)
 IterativeSolvers.ssor(A::HipCSR{T}, b::HipVector{T}, ω::Real; kwargs...) where {T} = IterativeSolvers.ssor!(IterativeSolvers.zerox(A, b), A, b, ω; kwargs...)
 
+# ---- dense stationary methods: jacobi / gauss_seidel / sor / ssor on a dense device matrix (src/stationary.jl) --------------------
+# A device n x cols column-major matrix (leading dimension padded to a multiple of 64 elements), uploaded from a Matrix.
+mutable struct HipDenseMatrix{T<:MikFloat}
+    ptr::Ptr{Cvoid}
+    n::Int
+    cols::Int
+    ld::Int
+    ctx::Context
+end
+function HipDenseMatrix(a::Matrix{T}, ctx::Context = context()) where {T<:MikFloat}
+    n, cols = size(a)
+    ld = max(64, cld(n, 64) * 64)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mik_malloc, libmik), Cint, (Ptr{Cvoid}, Csize_t, Ref{Ptr{Cvoid}}), ctx.handle, ld * max(cols, 1) * sizeof(T), p), "mik_malloc", ctx.handle)
+    m = HipDenseMatrix{T}(p[], n, cols, ld, ctx)
+    finalizer(x -> alive(x.ctx) && ccall((:mik_free, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), x.ctx.handle, x.ptr), m)
+    padded = zeros(T, ld, cols)
+    padded[1:n, :] .= a
+    GC.@preserve padded check(ccall((:mik_memcpy_h2d, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t),
+                                    ctx.handle, m.ptr, pointer(padded), sizeof(padded)), "mik_memcpy_h2d", ctx.handle)
+    m
+end
+Base.size(m::HipDenseMatrix) = (m.n, m.cols)
+Base.size(m::HipDenseMatrix, d::Integer) = d == 1 ? m.n : (d == 2 ? m.cols : 1)
+Base.eltype(::HipDenseMatrix{T}) where {T} = T
+IterativeSolvers.zerox(A::HipDenseMatrix{T}, b::HipVector{T}) where {T} = fill!(HipVector{T}(undef, size(A, 2), b.ctx), zero(T))
+
+struct DensePlan                     # same field order and types as the C struct mik_dense_plan
+    form::Cint                       # 0 auto, 1 panel, 2 chained (not built: refused)
+    spin_limit::Cint
+end
+# check_diag (src/stationary.jl:6-12) + the work vectors of the four iterations (mik_dense_stationary_create); one C call per iteration
+mutable struct HipDenseStationary{T}
+    handle::Ptr{Cvoid}
+    A::HipDenseMatrix{T}             # read at every step; kept alive with the handle
+    ctx::Context
+end
+function HipDenseStationary(A::HipDenseMatrix{T}; form::Integer = 0, spin_limit::Integer = 0) where {T}
+    size(A, 1) == size(A, 2) || throw(DimensionMismatch("the matrix is $(size(A, 1)) x $(size(A, 2)), not square"))
+    h = Ref{Ptr{Cvoid}}(C_NULL); col = Ref{Int64}(0)
+    code = ccall((:mik_dense_stationary_create, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Ref{DensePlan}, Ref{Int64}, Ref{Ptr{Cvoid}}),
+                 A.ctx.handle, A.ptr, A.n, A.ld, dtype_code(T), DensePlan(form, spin_limit), col, h)
+    code == 8 && throw(LinearAlgebra.SingularException(Int(col[])))             # check_diag, src/stationary.jl:9
+    check(code, "mik_dense_stationary_create", A.ctx.handle)
+    S = HipDenseStationary{T}(h[], A, A.ctx)
+    finalizer(o -> alive(o.ctx) && ccall((:mik_dense_stationary_destroy, libmik), Cint, (Ptr{Cvoid},), o.handle), S)
+    S
+end
+"panel width, rows per workgroup, launches of one forward substitution, form in use, whether a chained launch gave up, device bytes"
+function dense_stationary_info(S::HipDenseStationary)
+    w = Ref{Int64}(0); r = Ref{Int64}(0); la = Ref{Int64}(0); form = Ref{Cint}(0); gave_up = Ref{Cint}(0); b = Ref{Int64}(0)
+    check(ccall((:mik_dense_stationary_info, libmik), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Cint}, Ref{Cint}, Ref{Int64}),
+                S.handle, w, r, la, form, gave_up, b), "mik_dense_stationary_info", S.ctx.handle)
+    (W = w[], R = r[], launches_forward = la[], form = Int(form[]), gave_up = gave_up[] != 0, bytes = b[])
+end
+# ω in Julia's promotion: Float32 data with a Float64 ω evaluate x + ω * (tmp / d - x) in Float64 (scalar dtype MIK_F64); an Int ω stays in T
+function dense_omega(::Type{T}, ω::Real) where {T}
+    R = promote_type(T, typeof(ω))
+    R <: MikFloat || throw(ArgumentError("ω of type $(typeof(ω)) on $(T) data: the device computes in Float32 / Float64"))
+    convert(R, ω)
+end
+
+mutable struct HipDenseJacobiIterable{T}                 # DenseJacobiIterable  :38-44
+    A::HipDenseStationary{T}
+    x::HipVector{T}
+    next::HipVector{T}
+    b::HipVector{T}
+    maxiter::Int
+end
+mutable struct HipDenseGaussSeidelIterable{T}            # DenseGaussSeidelIterable  :98-103
+    A::HipDenseStationary{T}
+    x::HipVector{T}
+    b::HipVector{T}
+    maxiter::Int
+end
+mutable struct HipDenseSORIterable{T, numT<:Real}        # DenseSORIterable  :156-163
+    A::HipDenseStationary{T}
+    x::HipVector{T}
+    tmp::HipVector{T}
+    b::HipVector{T}
+    ω::numT
+    maxiter::Int
+end
+mutable struct HipDenseSSORIterable{T, numT<:Real}       # DenseSSORIterable  :216-223
+    A::HipDenseStationary{T}
+    x::HipVector{T}
+    tmp::HipVector{T}
+    b::HipVector{T}
+    ω::numT
+    maxiter::Int
+end
+const HipDenseStationaryIterable = Union{HipDenseJacobiIterable, HipDenseGaussSeidelIterable, HipDenseSORIterable, HipDenseSSORIterable}
+
+function Base.iterate(j::HipDenseJacobiIterable{T}, iteration::Int = 1) where {T}                         # :48-72
+    iteration > j.maxiter && return nothing
+    check(ccall((:mik_dense_jacobi_step, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), j.A.handle, j.x.ptr, j.next.ptr, j.b.ptr),
+          "mik_dense_jacobi_step", j.A.ctx.handle)
+    nothing, iteration + 1
+end
+function Base.iterate(s::HipDenseGaussSeidelIterable{T}, iteration::Int = 1) where {T}                    # :108-129
+    iteration > s.maxiter && return nothing
+    check(ccall((:mik_dense_gs_step, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), s.A.handle, s.x.ptr, s.b.ptr), "mik_dense_gs_step", s.A.ctx.handle)
+    nothing, iteration + 1
+end
+function Base.iterate(s::HipDenseSORIterable{T}, iteration::Int = 1) where {T}                            # :167-188
+    iteration > s.maxiter && return nothing
+    ω = dense_omega(T, s.ω); R = typeof(ω)
+    check(ccall((:mik_dense_sor_step, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{R}, Cint),
+                s.A.handle, s.x.ptr, s.tmp.ptr, s.b.ptr, ω, dtype_code(R)), "mik_dense_sor_step", s.A.ctx.handle)
+    nothing, iteration + 1
+end
+function Base.iterate(s::HipDenseSSORIterable{T}, iteration::Int = 1) where {T}                           # :227-263
+    iteration > s.maxiter && return nothing
+    ω = dense_omega(T, s.ω); R = typeof(ω)
+    check(ccall((:mik_dense_ssor_step, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{R}, Cint),
+                s.A.handle, s.x.ptr, s.tmp.ptr, s.b.ptr, ω, dtype_code(R)), "mik_dense_ssor_step", s.A.ctx.handle)
+    nothing, iteration + 1
+end
+Base.length(it::HipDenseStationaryIterable) = it.maxiter
+
+# jacobi! / gauss_seidel! / sor! / ssor! (:31-36, :91-96, :149-154, :209-214): check_diag once, exactly maxiter iterations, x in place
+function IterativeSolvers.jacobi!(x::HipVector{T}, A::HipDenseMatrix{T}, b::HipVector{T}; maxiter::Int = 10) where {T}
+    iterable = HipDenseJacobiIterable{T}(HipDenseStationary(A), x, similar(x), b, maxiter)
+    for item = iterable end
+    x
+end
+function IterativeSolvers.gauss_seidel!(x::HipVector{T}, A::HipDenseMatrix{T}, b::HipVector{T}; maxiter::Int = 10) where {T}
+    iterable = HipDenseGaussSeidelIterable{T}(HipDenseStationary(A), x, b, maxiter)
+    for item = iterable end
+    x
+end
+function IterativeSolvers.sor!(x::HipVector{T}, A::HipDenseMatrix{T}, b::HipVector{T}, ω::Real; maxiter::Int = 10) where {T}
+    iterable = HipDenseSORIterable{T, typeof(ω)}(HipDenseStationary(A), x, similar(x), b, ω, maxiter)
+    for item = iterable end
+    x
+end
+function IterativeSolvers.ssor!(x::HipVector{T}, A::HipDenseMatrix{T}, b::HipVector{T}, ω::Real; maxiter::Int = 10) where {T}
+    iterable = HipDenseSSORIterable{T, typeof(ω)}(HipDenseStationary(A), x, similar(x), b, ω, maxiter)
+    for item = iterable end
+    x
+end
+IterativeSolvers.jacobi(A::HipDenseMatrix{T}, b::HipVector{T}; kwargs...) where {T} = IterativeSolvers.jacobi!(IterativeSolvers.zerox(A, b), A, b; kwargs...)
+IterativeSolvers.gauss_seidel(A::HipDenseMatrix{T}, b::HipVector{T}; kwargs...) where {T} = IterativeSolvers.gauss_seidel!(IterativeSolvers.zerox(A, b), A, b; kwargs...)
+IterativeSolvers.sor(A::HipDenseMatrix{T}, b::HipVector{T}, ω::Real; kwargs...) where {T} = IterativeSolvers.sor!(IterativeSolvers.zerox(A, b), A, b, ω; kwargs...)
+IterativeSolvers.ssor(A::HipDenseMatrix{T}, b::HipVector{T}, ω::Real; kwargs...) where {T} = IterativeSolvers.ssor!(IterativeSolvers.zerox(A, b), A, b, ω; kwargs...)
+
 end # module
