@@ -753,6 +753,41 @@ int mik_block_rdiv(mik_ctx *ctx, int dtype, int64_t n, int s, const void *R, int
 int mik_block_update(mik_ctx *ctx, int dtype, int64_t n, int sx, int b1, int b2, const void *X, int64_t ldx, const void *R, int64_t ldr,
                      const void *P, int64_t ldp, const void *V, int64_t ldv, void *Xout, int64_t ldxo, void *Pout, int64_t ldpo);
 
+/* ---- dense operator: mul!(y, A, x) and mul!(y, adjoint(A), x) for A::Matrix ---------------------------------------------------
+ * The first operator of every solver testset of the reference (test/cg.jl:24-29, test/gmres.jl:16-17, ...).  Added without a version
+ * bump (additive); real MIK_F64 / MIK_F32.  A is a DEVICE m x n column-major matrix with leading dimension lda >= m, read at every
+ * product (the handle keeps no copy of it; A must outlive the handle).  No FMA, no matrix cores, no floating-point atomics: every
+ * product and every sum is rounded on its own.
+ *   y = A x    The columns are cut into chunks of C consecutive columns (mik_dense_mul_shape).  For row i and chunk c, p_c[i] is the
+ *              serial sum from +0, over the chunk's columns ascending, of A[i,j] * x[j]; then y[i] = ((p_0[i] + p_1[i]) + p_2[i]) + ...,
+ *              left to right.  With n <= C this is exactly the order of Julia's generic column-oriented mul!; with
+ *              n <= min(C, mik_spmv_long_row()) it is also the order of mik_spmv on the same matrix stored fully.  The result depends on
+ *              (m, n, dtype, C) only -- never on the machine, the launch shape, lda or pointer alignment.  n = 0 gives y = +0 (a row of
+ *              -0.0 products therefore gives +0.0); NaN and Inf propagate as IEEE has them.
+ *   y = A' x   y[j] equals mik_dot(A[:, j], x) bit for bit: the fixed two-level tree of mik_reduce_shape over m elements ("Reduction
+ *              semantics"), through the same finaliser.  The scaled-norm machinery is not involved.
+ * N form: rows across lanes (a lane owns 2 fp64 / 4 fp32 consecutive rows per 16-byte load; a scalar-load variant with identical
+ * results when a column start is not 16-byte aligned), x[j] broadcast through a scalar load, chunks of the same rows in different
+ * workgroups, the chunk partials combined in chunk order by a second small kernel.  T form: one sweep that reads every column once and
+ * x once per workgroup pass, the segment sums through the segment toolkit and k_finalize_store.  No workgroup waits for another.
+ * The handle owns the workspace of the chunk partials / segment sums (allocated once in create; nothing is allocated per call) and never
+ * touches the context's reduction workspace, so the callbacks below may run in the middle of a fused CG / GMRES step. */
+typedef struct mik_dense mik_dense;     /* opaque: (ctx, dtype, m, n, A, lda) + its own workspace */
+/* C (one compile-time constant for both dtypes, a power of two in [32, 256]) and the rows a workgroup of the N form owns. */
+int mik_dense_mul_shape(int *chunk, int *rows_per_workgroup);
+/* MIK_ERR_MISMATCH for lda < m; MIK_ERR_INVALID for a NULL argument; m = 0 or n = 0 is MIK_OK. */
+int mik_dense_create(mik_ctx *ctx, int dtype, int64_t m, int64_t n, const void *A, int64_t lda, mik_dense **out);
+int mik_dense_destroy(mik_dense *D);
+/* adjoint = 0: mul!(y, A, x) -- LinearAlgebra's generic mul! for a Matrix, called at src/cg.jl:54,137; src/gmres.jl:245,287.
+ * adjoint = 1: mul!(y, adjoint(A), x) -- src/lsqr.jl:132,172; src/lsmr.jl:118,172; src/qmr.jl:76; src/svdl.jl:565.
+ * x, y: DEVICE vectors of n and m (adjoint: m and n) elements.  MIK_ERR_INVALID when x and y overlap or y overlaps A.
+ * Asynchronous on the ctx stream. */
+int mik_dense_mul(mik_dense *D, int adjoint, const void *x, void *y);
+/* The same as mik_mul_fn callbacks (user = the mik_dense handle): a host fills mik_operator{dtype, n, NULL, mik_dense_mul_fn, handle} and
+ * calls mik_cg_create_op / mik_gmres_create_op -- the whole solve then runs inside the library, no host-language frame per product. */
+int mik_dense_mul_fn(void *user, const void *x, void *y);         /* y = A x  -- src/cg.jl:54,137; src/gmres.jl:245,287 */
+int mik_dense_mul_adj_fn(void *user, const void *x, void *y);     /* y = A' x -- src/lsqr.jl:132,172; src/lsmr.jl:118,172; src/qmr.jl:76; src/svdl.jl:565 */
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Time `reps` back-to-back launches of the SpMV (optionally with the fused dot epilogue used by
  * the CG step) with HIP events on the ctx stream; returns average milliseconds per launch. */

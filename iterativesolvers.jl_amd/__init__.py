@@ -5,10 +5,11 @@ The directory name (``iterativesolvers.jl_amd``) is not a Python identifier; loa
 
   csrc/      hand-written HIP kernels (gfx950) + the C ABI of include/mik.h  -> libmik.so
   _lib.py    ctypes binding of that ABI (fails loudly when the library is missing)
-  api.py     host-side mirror of the reference interface (cg, cg_, gmres, gmres_, iterables ...): SURVEY section 8 rows only
+  api.py     host-side mirror of the reference interface (cg, cg_, gmres, gmres_, iterables ...): SURVEY section 8 rows only;
+             a HipMatrix is an operator too (mul!(y, A::Matrix, x) and adjoint(A): csrc/mik_dense_mul.hip)
   stationary.py  jacobi / gauss_seidel / sor / ssor and their iterables on a HipCSR (src/stationary_sparse.jl)
   stationary_dense.py  the same four on a dense HipMatrix (src/stationary.jl), and the public names that dispatch between the two
-  svdl.py    svdl: Golub-Kahan-Lanczos SVD with thick restart (src/svdl.jl) on a HipCSR uploaded with its adjoint
+  svdl.py    svdl: Golub-Kahan-Lanczos SVD with thick restart (src/svdl.jl) on a HipCSR uploaded with its adjoint, or on a HipMatrix
   lobpcg.py  lobpcg: block eigensolver (src/lobpcg.jl) on HipCSR operators, every sweep on a block of columns
   extras.py  solvers outside the scope contract (IDR(s), LSQR, LSMR, QMR, power method); kept apart, unjudged
   dist.py    row-partitioned multi-GPU CG / GMRES (one process per GPU; RCCL, peer-mapped mailboxes, in-process group)
@@ -20,7 +21,7 @@ The directory name (``iterativesolvers.jl_amd``) is not a Python identifier; loa
 from . import _lib, fixtures                                    # noqa: F401
 from ._lib import MikError, lib                                  # noqa: F401
 from .api import (CGIterable, CGStateVariables, ClassicalGramSchmidt, ConvergenceHistory, DGKS,   # noqa: F401
-                  GenericCGIterable, GMRESIterable, HipContext, HipCSR, HipMatrix, HipVector, Identity,
+                  GenericCGIterable, GMRESIterable, HipContext, HipCSR, HipMatrix, HipMatrixAdjoint, HipVector, Identity,
                   JacobiPrec, ModifiedGramSchmidt, PCGIterable, cg, cg_, cg_iterator_, default_context,
                   dot, gemv_n_, gmres, gmres_, gmres_iterable_, hessenberg_ldiv_, mul_, niters, norm, nprods,
                   nrests, orthogonalize_and_normalize_, zerox, BiCGStabIterable, bicgstabl, bicgstabl_, bicgstabl_iterator_,

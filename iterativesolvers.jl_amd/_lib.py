@@ -220,6 +220,12 @@ SIGNATURES = {
     "mik_dense_gs_step": (C.c_int, [_vp, _vp, _vp]),
     "mik_dense_sor_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
     "mik_dense_ssor_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "mik_dense_mul_shape": (C.c_int, [_ip, _ip]),
+    "mik_dense_create": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _i64, C.POINTER(_vp)]),
+    "mik_dense_destroy": (C.c_int, [_vp]),
+    "mik_dense_mul": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "mik_dense_mul_fn": (C.c_int, [_vp, _vp, _vp]),
+    "mik_dense_mul_adj_fn": (C.c_int, [_vp, _vp, _vp]),
     "mik_basis_rotate": (C.c_int, [_vp, C.c_int, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64]),
     "mik_svdl_reorth": (C.c_int, [_vp, C.c_int, _i64, C.c_int, _vp, _i64, _vp, _vp, _vp, C.POINTER(C.c_int)]),
     "mik_spmm": (C.c_int, [_vp, _vp, C.c_int, _vp, _i64, _vp, _i64]),

@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import weakref
 from typing import Optional
 
 import numpy as np
@@ -290,6 +291,72 @@ class HipMatrix:
     def to_numpy(self) -> np.ndarray:
         return np.stack([self.col(j).to_numpy() for j in range(self.cols)], axis=1)
 
+    # ---- the matrix as an operator: mul!(y, A::Matrix, x) and adjoint(A) (test/cg.jl:24-29, test/gmres.jl:16-17) ----
+    @property
+    def n_rows(self) -> int:
+        return self.n
+
+    @property
+    def n_cols(self) -> int:
+        return self.cols
+
+    def size(self, d: Optional[int] = None):
+        return (self.n, self.cols) if d is None else (self.n, self.cols)[d - 1]
+
+    def eltype(self):
+        return self.dtype
+
+    @property
+    def dense(self):
+        """The ``mik_dense`` handle of this matrix, created at the first product (it owns the workspace of the chunk partials and
+        segment sums; the matrix itself is not copied)."""
+        h = self.__dict__.get("_dense")
+        if h is None:
+            h = _vp()
+            check(lib().mik_dense_create(self.ctx.handle, dtype_code(self.dtype), self.n, self.cols, _vp(self.buf.ptr), self.ld, C.byref(h)),
+                  "mik_dense_create", self.ctx.handle)
+            self._dense = h
+        return h
+
+    @property
+    def adj(self) -> "HipMatrixAdjoint":
+        """``adjoint(A)``: a view, no copy; ``A.adj.adj is A``."""
+        ref = self.__dict__.get("_adj")                                  # a weak reference: the view holds the matrix, not the matrix the view
+        a = ref() if ref is not None else None
+        if a is None:
+            a = HipMatrixAdjoint(self)
+            self._adj = weakref.ref(a)
+        return a
+
+    def __matmul__(self, x: HipVector) -> HipVector:                     # A * v
+        return mul_(HipVector(self.n, self.dtype, self.ctx), self, x)
+
+    def __del__(self):
+        try:
+            if self.__dict__.get("_dense") and self.ctx.handle:
+                lib().mik_dense_destroy(self._dense)
+                self._dense = None
+        except Exception:
+            pass
+
+
+class HipMatrixAdjoint:
+    """``adjoint(A)`` of a ``HipMatrix``: the same device matrix read column by column (``mik_dense_mul`` with adjoint = 1)."""
+
+    def __init__(self, parent: HipMatrix):
+        self.adj = parent
+        self.ctx, self.dtype = parent.ctx, parent.dtype
+        self.n_rows, self.n_cols = parent.cols, parent.n
+
+    def size(self, d: Optional[int] = None):
+        return (self.n_rows, self.n_cols) if d is None else (self.n_rows, self.n_cols)[d - 1]
+
+    def eltype(self):
+        return self.dtype
+
+    def __matmul__(self, x: HipVector) -> HipVector:
+        return mul_(HipVector(self.n_rows, self.dtype, self.ctx), self, x)
+
 
 class HipCSR:
     """The operator ``A``: a SparseMatrixCSC uploaded as device CSR (``mik_csr``).
@@ -419,6 +486,10 @@ def mul_(y: HipVector, A, x: HipVector) -> HipVector:
     if isinstance(A, LinearOperator):
         A.mul(y, x)
         return y
+    if isinstance(A, (HipMatrix, HipMatrixAdjoint)):                     # mul!(y, A::Matrix, x) / mul!(y, adjoint(A), x)
+        M, adjoint = (A.adj, 1) if isinstance(A, HipMatrixAdjoint) else (A, 0)
+        check(lib().mik_dense_mul(M.dense, adjoint, _vp(x.ptr), _vp(y.ptr)), "mik_dense_mul", A.ctx.handle)
+        return y
     check(lib().mik_spmv(A.ctx.handle, A.handle, _vp(x.ptr), _vp(y.ptr)), "mik_spmv", A.ctx.handle)
     return y
 
@@ -459,6 +530,13 @@ class _Bound:
     def operator(self, A) -> "_lib.MikOperator":
         if isinstance(A, HipCSR):
             return _lib.MikOperator(A.code, A.n_rows, A.handle, _lib.MUL_FN(), None)
+        if isinstance(A, (HipMatrix, HipMatrixAdjoint)):                 # the library's own callback: no Python frame per product
+            if A.n_rows != A.n_cols or A.n_rows != self.n or A.dtype != self.dtype:      # the callback never sees the vector lengths
+                raise ValueError(f"DimensionMismatch: a {A.n_rows} x {A.n_cols} {A.dtype} matrix as the operator of {self.n}-vectors of {self.dtype}")
+            M, name = (A.adj, "mik_dense_mul_adj_fn") if isinstance(A, HipMatrixAdjoint) else (A, "mik_dense_mul_fn")
+            fn = C.cast(getattr(lib(), name), _lib.MUL_FN)
+            self.keep.append(A)
+            return _lib.MikOperator(dtype_code(self.dtype), self.n, None, fn, M.dense)
 
         def cb(_user, x, y):
             try:

@@ -1,0 +1,144 @@
+// mik_dense_mul.hip -- the dense operator: mul!(y, A, x) and mul!(y, adjoint(A), x) on a column-major device matrix, and the
+// mik_mul_fn callbacks that put it under the fused iterables (mik_cg_create_op / mik_gmres_create_op) with no host-language frame
+// per product.
+//
+// The handle owns its workspace -- the chunk partials of the N form and the segment sums of the T form share one allocation made in
+// create -- and never touches ctx->partials / ctx->coef: the callback runs in the middle of a fused CG / GMRES step that may hold
+// state there.  Nothing is allocated per call; every call is asynchronous on the ctx stream; no workgroup waits for another.
+#include "mik_internal.h"
+#include "mik_dense_mul.h"
+
+#include <new>
+
+struct mik_dense {
+    mik_ctx *ctx = nullptr;
+    int dtype = MIK_F64;
+    int64_t m = 0, n = 0, lda = 0;
+    const void *A = nullptr;
+    void *work = nullptr;            // N: [chunks][m_pad] partials;  T: [n][segments of m] segment sums
+    int64_t m_pad = 0;               // m rounded up to whole workgroups of the N form (keeps every partial column 16-byte aligned)
+};
+
+namespace {
+
+inline int64_t dm_chunks(int64_t n) { return (n + MIK_DM_C - 1) / MIK_DM_C; }
+
+template <typename T>
+int dm_mul_n(mik_dense *D, const T *x, T *y)
+{
+    mik_ctx *ctx = D->ctx;
+    const int64_t m = D->m, n = D->n;
+    if (m == 0) return MIK_OK;
+    if (n == 0) {                                             // the empty sum: +0
+        MIK_HIP(ctx, hipMemsetAsync(y, 0, sizeof(T) * (size_t)m, ctx->stream));
+        return MIK_OK;
+    }
+    const int64_t nc = dm_chunks(n);
+    T *out = nc == 1 ? y : (T *)D->work;
+    const bool vec = mik_aligned16(D->A) && D->lda % VT<T>::W == 0 && mik_aligned16(out);
+    const int nt = (double)m * (double)n * sizeof(T) > 192.0e6 ? 1 : 0;       // a matrix the caches cannot keep is streamed past them
+    // at most 4 workgroups per compute unit, all resident at once: a workgroup walks its chunks c, c + grid.y, ... in turn (measured neutral
+    // against one workgroup per chunk, scripts/micro/dense_chunk.hip; it bounds the launch for very wide matrices)
+    const int64_t gx = (m + MIK_DM_R - 1) / MIK_DM_R;
+    const dim3 grid((unsigned)gx, (unsigned)std::min<int64_t>(nc, std::max<int64_t>(1, std::min<int64_t>(65535, 4 * (int64_t)mik_cus(ctx) / gx))));
+    if (vec && nt) hipLaunchKernelGGL((k_dense_n<T, true, true, MIK_DM_C>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const T *)D->A, D->lda, x, out, D->m_pad);
+    else if (vec) hipLaunchKernelGGL((k_dense_n<T, true, false, MIK_DM_C>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const T *)D->A, D->lda, x, out, D->m_pad);
+    else hipLaunchKernelGGL((k_dense_n<T, false, false, MIK_DM_C>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const T *)D->A, D->lda, x, out, D->m_pad);
+    MIK_LAUNCH_CHECK(ctx);
+    if (nc > 1) {
+        hipLaunchKernelGGL((k_dense_n_combine<T, MIK_DM_PF>), dim3((unsigned)((m + MIK_DM_CB - 1) / MIK_DM_CB)), dim3(MIK_DM_CB), 0, ctx->stream, m, nc, (const T *)out, D->m_pad, y);
+        MIK_LAUNCH_CHECK(ctx);
+    }
+    return MIK_OK;
+}
+
+template <typename T>
+int dm_mul_t(mik_dense *D, const T *x, T *y)
+{
+    mik_ctx *ctx = D->ctx;
+    const int64_t m = D->m, n = D->n;
+    if (n == 0) return MIK_OK;
+    const int64_t nseg = mik_nseg<T>(m);
+    if (nseg == 0) {                                          // empty columns: every dot is +0
+        MIK_HIP(ctx, hipMemsetAsync(y, 0, sizeof(T) * (size_t)n, ctx->stream));
+        return MIK_OK;
+    }
+    const bool vec = mik_aligned16(D->A) && D->lda % VT<T>::W == 0 && mik_aligned16(x);
+    const int nt = (double)m * (double)n * sizeof(T) > 192.0e6 ? 1 : 0;
+    const int64_t batches = (n + MIK_DM_TCOLS - 1) / MIK_DM_TCOLS;
+    const int64_t gx = std::min<int64_t>(nseg, mik_max_grid(ctx));
+    const int64_t gy = std::min<int64_t>(batches, std::max<int64_t>(1, std::min<int64_t>(65535, 4 * (int64_t)mik_cus(ctx) / gx)));      // as in the N form
+    T *part = (T *)D->work;
+    const dim3 grid((unsigned)gx, (unsigned)gy);
+    if (vec && nt) hipLaunchKernelGGL((k_dense_t<T, true, true>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, nseg, n, (const T *)D->A, D->lda, x, part);
+    else if (vec) hipLaunchKernelGGL((k_dense_t<T, true, false>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, nseg, n, (const T *)D->A, D->lda, x, part);
+    else hipLaunchKernelGGL((k_dense_t<T, false, false>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, nseg, n, (const T *)D->A, D->lda, x, part);
+    MIK_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL((k_finalize_store<T>), dim3((unsigned)n), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)part, nseg, nseg, y, (const int *)nullptr);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
+}  // namespace
+
+extern "C" int mik_dense_mul_shape(int *chunk, int *rows_per_workgroup)
+{
+    if (chunk) *chunk = MIK_DM_C;
+    if (rows_per_workgroup) *rows_per_workgroup = MIK_DM_R;
+    return MIK_OK;
+}
+
+extern "C" int mik_dense_create(mik_ctx *ctx, int dtype, int64_t m, int64_t n, const void *A, int64_t lda, mik_dense **out)
+{
+    if (!ctx || !out) return MIK_ERR_INVALID;
+    *out = nullptr;
+    if (dtype != MIK_F64 && dtype != MIK_F32) return mik_fail(ctx, MIK_ERR_INVALID, "mik_dense_create: dtype must be MIK_F64 or MIK_F32");
+    if (m < 0 || n < 0) return mik_fail(ctx, MIK_ERR_INVALID, "mik_dense_create: m = %lld, n = %lld", (long long)m, (long long)n);
+    if (lda < m) return mik_fail(ctx, MIK_ERR_MISMATCH, "mik_dense_create: lda = %lld < m = %lld", (long long)lda, (long long)m);
+    if (!A && m > 0 && n > 0) return MIK_ERR_INVALID;
+    if (m > (int64_t)std::numeric_limits<int>::max() - MIK_DM_R || n > (int64_t)std::numeric_limits<int>::max() - MIK_DM_C)
+        return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_dense_create: a dimension >= 2^31");
+    mik_dense *D = new (std::nothrow) mik_dense();
+    if (!D) return mik_fail(ctx, MIK_ERR_NOMEM, "mik_dense_create: host allocation failed");
+    D->ctx = ctx; D->dtype = dtype; D->m = m; D->n = n; D->lda = lda; D->A = A;
+    D->m_pad = (m + MIK_DM_R - 1) / MIK_DM_R * MIK_DM_R;
+    const size_t es = mik_dtype_size(dtype);
+    const int64_t nc = dm_chunks(n);
+    const int64_t nseg = dtype == MIK_F64 ? mik_nseg<double>(m) : mik_nseg<float>(m);
+    const size_t bytes = std::max<size_t>(16, es * std::max<size_t>(nc > 1 ? (size_t)nc * (size_t)D->m_pad : 0, (size_t)n * (size_t)nseg));
+    (void)hipSetDevice(ctx->device);
+    const hipError_t e = hipMalloc(&D->work, bytes);
+    if (e != hipSuccess) {
+        delete D;
+        return mik_fail(ctx, e == hipErrorOutOfMemory ? MIK_ERR_NOMEM : MIK_ERR_HIP, "mik_dense_create: hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    }
+    *out = D;
+    return MIK_OK;
+}
+
+extern "C" int mik_dense_destroy(mik_dense *D)
+{
+    if (!D) return MIK_OK;
+    if (D->ctx) { (void)hipSetDevice(D->ctx->device); (void)hipStreamSynchronize(D->ctx->stream); }
+    if (D->work) (void)hipFree(D->work);
+    delete D;
+    return MIK_OK;
+}
+
+extern "C" int mik_dense_mul(mik_dense *D, int adjoint, const void *x, void *y)
+{
+    if (!D) return MIK_ERR_INVALID;
+    const size_t es = mik_dtype_size(D->dtype);
+    const int64_t nx = adjoint ? D->m : D->n, ny = adjoint ? D->n : D->m;
+    if ((nx && !x) || (ny && !y)) return MIK_ERR_INVALID;
+    if (mik_overlap(x, es * (size_t)nx, y, es * (size_t)ny)) return mik_fail(D->ctx, MIK_ERR_INVALID, "mik_dense_mul: x and y must not overlap");
+    const size_t abytes = (D->m > 0 && D->n > 0) ? es * ((size_t)(D->n - 1) * (size_t)D->lda + (size_t)D->m) : 0;
+    if (mik_overlap(y, es * (size_t)ny, D->A, abytes)) return mik_fail(D->ctx, MIK_ERR_INVALID, "mik_dense_mul: y must not overlap A");
+    if (D->dtype == MIK_F64)
+        return adjoint ? dm_mul_t<double>(D, (const double *)x, (double *)y) : dm_mul_n<double>(D, (const double *)x, (double *)y);
+    return adjoint ? dm_mul_t<float>(D, (const float *)x, (float *)y) : dm_mul_n<float>(D, (const float *)x, (float *)y);
+}
+
+extern "C" int mik_dense_mul_fn(void *user, const void *x, void *y) { return mik_dense_mul((mik_dense *)user, 0, x, y); }
+
+extern "C" int mik_dense_mul_adj_fn(void *user, const void *x, void *y) { return mik_dense_mul((mik_dense *)user, 1, x, y); }

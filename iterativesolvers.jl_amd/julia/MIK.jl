@@ -409,6 +409,10 @@ function ldiv_trampoline(user::Ptr{Cvoid}, y::Ptr{Cvoid}, x::Ptr{Cvoid})::Cint
 end
 function operator_struct(A, ::Type{T}, n::Int, ctx::Context, keep::Vector{Any}) where {T}
     A isa HipCSR && return MikOperator(dtype_code(T), n, A.handle, C_NULL, C_NULL)
+    if A isa HipDenseMatrix || A isa HipDenseAdjoint             # the library's own callback: no Julia frame per product
+        push!(keep, A)
+        return dense_operator_struct(A, T, n)
+    end
     box = CallbackBox{T}(A, n, ctx); push!(keep, box)
     MikOperator(dtype_code(T), n, C_NULL, @cfunction(mul_trampoline, Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid})), pointer_from_objref(box))
 end
@@ -1270,5 +1274,65 @@ IterativeSolvers.jacobi(A::HipDenseMatrix{T}, b::HipVector{T}; kwargs...) where 
 IterativeSolvers.gauss_seidel(A::HipDenseMatrix{T}, b::HipVector{T}; kwargs...) where {T} = IterativeSolvers.gauss_seidel!(IterativeSolvers.zerox(A, b), A, b; kwargs...)
 IterativeSolvers.sor(A::HipDenseMatrix{T}, b::HipVector{T}, ω::Real; kwargs...) where {T} = IterativeSolvers.sor!(IterativeSolvers.zerox(A, b), A, b, ω; kwargs...)
 IterativeSolvers.ssor(A::HipDenseMatrix{T}, b::HipVector{T}, ω::Real; kwargs...) where {T} = IterativeSolvers.ssor!(IterativeSolvers.zerox(A, b), A, b, ω; kwargs...)
+
+# ---- dense operator: mul!(y, A, x) and mul!(y, adjoint(A), x) for a dense device matrix (csrc/mik_dense_mul.hip) -------------------
+# What LinearAlgebra's generic mul! is for a Matrix at src/cg.jl:54,137 and src/gmres.jl:245,287, and for adjoint(A) at src/lsqr.jl:132,172,
+# src/lsmr.jl:118,172, src/qmr.jl:76 and src/svdl.jl:565.  The mik_dense handle (opaque: it owns the workspace of the chunk partials and the
+# segment sums, no copy of the matrix) is created at the first product of a matrix and kept beside it, not inside HipDenseMatrix.
+mutable struct HipDenseOperator
+    handle::Ptr{Cvoid}
+    ctx::Context
+end
+const DENSE_OPERATORS = WeakKeyDict{Any, HipDenseOperator}()     # HipDenseMatrix -> its handle; the value holds no reference to the key
+function dense_operator(A::HipDenseMatrix{T}) where {T}
+    get!(DENSE_OPERATORS, A) do
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:mik_dense_create, libmik), Cint, (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}),
+                    A.ctx.handle, dtype_code(T), A.n, A.cols, A.ptr, A.ld, h), "mik_dense_create", A.ctx.handle)
+        op = HipDenseOperator(h[], A.ctx)
+        finalizer(o -> alive(o.ctx) && ccall((:mik_dense_destroy, libmik), Cint, (Ptr{Cvoid},), o.handle), op)
+        op
+    end
+end
+"(C, R): the columns per chunk of y = A x and the rows a workgroup owns (include/mik.h, dense operator)"
+function dense_mul_shape()
+    c = Ref{Cint}(0); r = Ref{Cint}(0)
+    check(ccall((:mik_dense_mul_shape, libmik), Cint, (Ref{Cint}, Ref{Cint}), c, r), "mik_dense_mul_shape", C_NULL)
+    (C = Int(c[]), R = Int(r[]))
+end
+"adjoint(A) of a HipDenseMatrix: a view, no copy; adjoint(adjoint(A)) === A"
+struct HipDenseAdjoint{T<:MikFloat}
+    parent::HipDenseMatrix{T}
+end
+LinearAlgebra.adjoint(A::HipDenseMatrix) = HipDenseAdjoint(A)
+LinearAlgebra.adjoint(A::HipDenseAdjoint) = A.parent
+Base.size(A::HipDenseAdjoint) = (A.parent.cols, A.parent.n)
+Base.size(A::HipDenseAdjoint, d::Integer) = d == 1 ? A.parent.cols : (d == 2 ? A.parent.n : 1)
+Base.eltype(::HipDenseAdjoint{T}) where {T} = T
+function dense_mul!(y::HipVector{T}, A::HipDenseMatrix{T}, adj::Bool, x::HipVector{T}) where {T}
+    (length(x), length(y)) == (adj ? (A.n, A.cols) : (A.cols, A.n)) || throw(DimensionMismatch("mul!(y, A, x)"))
+    check(ccall((:mik_dense_mul, libmik), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}), dense_operator(A).handle, adj ? 1 : 0, x.ptr, y.ptr),
+          "mik_dense_mul", A.ctx.handle)
+    y
+end
+function LinearAlgebra.mul!(y::HipVector{T}, A::HipDenseMatrix{T}, x::HipVector{T}) where {T}
+    dense_mul!(y, A, false, x)
+end
+function LinearAlgebra.mul!(y::HipVector{T}, A::HipDenseAdjoint{T}, x::HipVector{T}) where {T}
+    dense_mul!(y, A.parent, true, x)
+end
+Base.:*(A::HipDenseMatrix{T}, x::HipVector{T}) where {T} = mul!(HipVector{T}(undef, A.n, A.ctx), A, x)
+Base.:*(A::HipDenseAdjoint{T}, x::HipVector{T}) where {T} = mul!(HipVector{T}(undef, A.parent.cols, A.parent.ctx), A, x)
+# mik_operator{dtype, n, NULL, mik_dense_mul_fn, handle}: the fused iterables call the library's product themselves
+dense_square(A, ::Type{T}, n::Int) where {T} = (size(A, 1) == size(A, 2) == n && eltype(A) == T) ||
+    throw(DimensionMismatch("a $(size(A, 1)) x $(size(A, 2)) $(eltype(A)) matrix as the operator of $(n)-vectors of $(T)"))     # the callback never sees the vector lengths
+function dense_operator_struct(A::HipDenseMatrix, ::Type{T}, n::Int) where {T}
+    dense_square(A, T, n)
+    MikOperator(dtype_code(T), n, C_NULL, cglobal((:mik_dense_mul_fn, libmik)), dense_operator(A).handle)
+end
+function dense_operator_struct(A::HipDenseAdjoint, ::Type{T}, n::Int) where {T}
+    dense_square(A, T, n)
+    MikOperator(dtype_code(T), n, C_NULL, cglobal((:mik_dense_mul_adj_fn, libmik)), dense_operator(A.parent).handle)
+end
 
 end # module

@@ -12,7 +12,7 @@ and is then swapped in; the reference's ``[L.Q q]`` concatenations are a column 
 restart loop.
 
 Differences from the reference, all deliberate:
-  * the operator is a ``HipCSR`` uploaded with its adjoint (``extras.with_adjoint`` / ``with_adjoint_from_scipy``), rectangular allowed;
+  * the operator is a ``HipCSR`` uploaded with its adjoint (``extras.with_adjoint`` / ``with_adjoint_from_scipy``) or a ``HipMatrix`` (its ``.adj`` is a view), rectangular allowed;
     ``LinearOperator`` callbacks are not supported;
   * the default ``v0`` is a random unit vector from numpy's generator, not from Julia's stream; a caller's ``v0`` is copied (build scales
     ``q`` in place, :357: that happens on the copy the factorisation owns);
@@ -152,8 +152,8 @@ class DeviceOps:
     """Every statement of length m or n, on the device.  (tests/svdl_double.py implements the same methods in numpy.)"""
 
     def __init__(self, A):
-        if not isinstance(A, HipCSR):
-            raise TypeError("svdl needs a HipCSR operator (LinearOperator callbacks are not supported)")
+        if not isinstance(A, (HipCSR, HipMatrix)):
+            raise TypeError("svdl needs a HipCSR or a HipMatrix operator (LinearOperator callbacks are not supported)")
         if getattr(A, "adj", None) is None:
             raise MikError(5, "svdl", "this operator was uploaded without its adjoint: create it with extras.with_adjoint(...) / "
                                       "with_adjoint_from_scipy(m)")
