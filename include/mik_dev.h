@@ -56,6 +56,14 @@ int mik_ctx_set_tuning(mik_ctx *ctx, int key, int value);
  * kernel (0: the multi-launch chains), *segments_per_workgroup = its G (0: buffers never allocated -- too many segments for this machine),
  * *xcd_local_last = the column last enqueued used the XCD-local form, *timeouts = columns that came back timed out so far.  Any pointer may be NULL. */
 int mik_dev_gmres_form(const mik_gmres *it, int *single_launch, int *segments_per_workgroup, int *xcd_local_last, int *timeouts);
+/* The launch plan mik_dense_mul(D, adjoint, x, y) takes for these pointers on this context (csrc/mik_dense_mul.hip computes it for the launch and
+ * for this query through one helper): *vec = 1 the 16-byte-load variant (0: scalar loads -- a matrix, leading dimension, x of the adjoint or
+ * directly written y that is not 16-byte aligned), *streamed = 1 non-temporal loads (a matrix beyond what the caches keep), the grid of the product
+ * kernel, *chunks_or_batches = column chunks of y = A x / 32-column batches of y = A' x that grid y strides over, *segments = reduction segments
+ * of y = A' x that grid x strides over (0 for y = A x).  Variant, grid and chunks / batches are zero for a call that launches no product kernel
+ * (an empty dimension).  Nothing is launched or read on the device.  Any out pointer may be NULL. */
+int mik_dev_dense_plan(const mik_dense *D, int adjoint, const void *x, const void *y, int *vec, int *streamed, int64_t *grid_x, int64_t *grid_y,
+                       int64_t *chunks_or_batches, int64_t *segments);
 /* Shape of the resident-w Modified Gram-Schmidt kernel (csrc/mik_mgs_res.h): threads per workgroup (threads / 256 segments per round), rounds of a
  * workgroup's segments kept in registers and in LDS; the rest of w is streamed in every pass.  For byte accounting (bench.py). */
 int mik_dev_mgs_resident_shape(int *threads, int *register_rounds, int *lds_rounds);

@@ -82,6 +82,7 @@ SIGNATURES = {
     "mik_ctx_destroy": (C.c_int, [_vp]),
     "mik_ctx_info": (C.c_int, [_vp, C.POINTER(MikDeviceInfo)]),
     "mik_dev_gmres_form": (C.c_int, [_vp, _ip, _ip, _ip, _ip]),
+    "mik_dev_dense_plan": (C.c_int, [_vp, C.c_int, _vp, _vp, _ip, _ip, _i64p, _i64p, _i64p, _i64p]),
     "mik_dev_mgs_resident_shape": (C.c_int, [_ip, _ip, _ip]),
     "mik_ctx_set_stream": (C.c_int, [_vp, _vp]),
     "mik_ctx_synchronize": (C.c_int, [_vp]),

@@ -12,6 +12,7 @@
 #include "mik_kernels.h"
 
 constexpr int MIK_DM_C = 64;           // columns per chunk of the N form (one compile-time constant for both dtypes)
+constexpr double MIK_DM_STREAM_BYTES = 192.0e6;   // a matrix of more bytes is read with non-temporal loads: the caches cannot keep it between products
 constexpr int MIK_DM_R = 1024;         // rows per workgroup of the N form: 256 lanes x 16 bytes x (fp64: 2 passes, fp32: 1 pass)
 constexpr int MIK_DM_U = 8;            // columns whose loads a lane issues before it consumes the first: 8 x 16 B x passes in flight per lane
 constexpr int MIK_DM_TCOLS = 32;       // columns a workgroup of the T form sweeps per segment of x it holds in registers

@@ -23,6 +23,51 @@ namespace {
 
 inline int64_t dm_chunks(int64_t n) { return (n + MIK_DM_C - 1) / MIK_DM_C; }
 
+// The launch plan of one call: which kernel variant, which grid, how many chunks / column batches and segments its loops walk.  dm_mul_n /
+// dm_mul_t launch what it says and mik_dev_dense_plan (include/mik_dev.h) reports it: one computation, so the two cannot drift apart.
+// A call with an empty dimension launches no product kernel: its plan is all zero (the T form still reports its segments).
+struct dm_plan {
+    int vec = 0, streamed = 0;
+    int64_t gx = 0, gy = 0, cols = 0, nseg = 0;      // cols: chunks of the N form, column batches of the T form; nseg: segments of the T form
+};
+
+// a matrix the caches cannot keep is streamed past them
+template <typename T> inline int dm_streamed(int64_t m, int64_t n) { return (double)m * (double)n * sizeof(T) > MIK_DM_STREAM_BYTES ? 1 : 0; }
+
+template <typename T>
+dm_plan dm_plan_n(const mik_dense *D, const T *x, const T *y)
+{
+    (void)x;
+    dm_plan p;
+    const int64_t m = D->m, n = D->n;
+    if (m == 0 || n == 0) return p;
+    p.cols = dm_chunks(n);
+    const T *out = p.cols == 1 ? y : (const T *)D->work;
+    p.vec = mik_aligned16(D->A) && D->lda % VT<T>::W == 0 && mik_aligned16(out);
+    p.streamed = dm_streamed<T>(m, n);
+    // at most 4 workgroups per compute unit, all resident at once: a workgroup walks its chunks c, c + grid.y, ... in turn (measured neutral
+    // against one workgroup per chunk, scripts/micro/dense_chunk.hip; it bounds the launch for very wide matrices)
+    p.gx = (m + MIK_DM_R - 1) / MIK_DM_R;
+    p.gy = std::min<int64_t>(p.cols, std::max<int64_t>(1, std::min<int64_t>(65535, 4 * (int64_t)mik_cus(D->ctx) / p.gx)));
+    return p;
+}
+
+template <typename T>
+dm_plan dm_plan_t(const mik_dense *D, const T *x, const T *y)
+{
+    (void)y;
+    dm_plan p;
+    const int64_t m = D->m, n = D->n;
+    p.nseg = mik_nseg<T>(m);
+    if (n == 0 || p.nseg == 0) return p;
+    p.vec = mik_aligned16(D->A) && D->lda % VT<T>::W == 0 && mik_aligned16(x);
+    p.streamed = dm_streamed<T>(m, n);
+    p.cols = (n + MIK_DM_TCOLS - 1) / MIK_DM_TCOLS;
+    p.gx = std::min<int64_t>(p.nseg, mik_max_grid(D->ctx));
+    p.gy = std::min<int64_t>(p.cols, std::max<int64_t>(1, std::min<int64_t>(65535, 4 * (int64_t)mik_cus(D->ctx) / p.gx)));      // as in the N form
+    return p;
+}
+
 template <typename T>
 int dm_mul_n(mik_dense *D, const T *x, T *y)
 {
@@ -33,14 +78,12 @@ int dm_mul_n(mik_dense *D, const T *x, T *y)
         MIK_HIP(ctx, hipMemsetAsync(y, 0, sizeof(T) * (size_t)m, ctx->stream));
         return MIK_OK;
     }
-    const int64_t nc = dm_chunks(n);
+    const dm_plan p = dm_plan_n<T>(D, x, y);
+    const int64_t nc = p.cols;
     T *out = nc == 1 ? y : (T *)D->work;
-    const bool vec = mik_aligned16(D->A) && D->lda % VT<T>::W == 0 && mik_aligned16(out);
-    const int nt = (double)m * (double)n * sizeof(T) > 192.0e6 ? 1 : 0;       // a matrix the caches cannot keep is streamed past them
-    // at most 4 workgroups per compute unit, all resident at once: a workgroup walks its chunks c, c + grid.y, ... in turn (measured neutral
-    // against one workgroup per chunk, scripts/micro/dense_chunk.hip; it bounds the launch for very wide matrices)
-    const int64_t gx = (m + MIK_DM_R - 1) / MIK_DM_R;
-    const dim3 grid((unsigned)gx, (unsigned)std::min<int64_t>(nc, std::max<int64_t>(1, std::min<int64_t>(65535, 4 * (int64_t)mik_cus(ctx) / gx))));
+    const bool vec = p.vec != 0;
+    const int nt = p.streamed;
+    const dim3 grid((unsigned)p.gx, (unsigned)p.gy);
     if (vec && nt) hipLaunchKernelGGL((k_dense_n<T, true, true, MIK_DM_C>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const T *)D->A, D->lda, x, out, D->m_pad);
     else if (vec) hipLaunchKernelGGL((k_dense_n<T, true, false, MIK_DM_C>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const T *)D->A, D->lda, x, out, D->m_pad);
     else hipLaunchKernelGGL((k_dense_n<T, false, false, MIK_DM_C>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const T *)D->A, D->lda, x, out, D->m_pad);
@@ -58,18 +101,16 @@ int dm_mul_t(mik_dense *D, const T *x, T *y)
     mik_ctx *ctx = D->ctx;
     const int64_t m = D->m, n = D->n;
     if (n == 0) return MIK_OK;
-    const int64_t nseg = mik_nseg<T>(m);
+    const dm_plan p = dm_plan_t<T>(D, x, y);
+    const int64_t nseg = p.nseg;
     if (nseg == 0) {                                          // empty columns: every dot is +0
         MIK_HIP(ctx, hipMemsetAsync(y, 0, sizeof(T) * (size_t)n, ctx->stream));
         return MIK_OK;
     }
-    const bool vec = mik_aligned16(D->A) && D->lda % VT<T>::W == 0 && mik_aligned16(x);
-    const int nt = (double)m * (double)n * sizeof(T) > 192.0e6 ? 1 : 0;
-    const int64_t batches = (n + MIK_DM_TCOLS - 1) / MIK_DM_TCOLS;
-    const int64_t gx = std::min<int64_t>(nseg, mik_max_grid(ctx));
-    const int64_t gy = std::min<int64_t>(batches, std::max<int64_t>(1, std::min<int64_t>(65535, 4 * (int64_t)mik_cus(ctx) / gx)));      // as in the N form
+    const bool vec = p.vec != 0;
+    const int nt = p.streamed;
     T *part = (T *)D->work;
-    const dim3 grid((unsigned)gx, (unsigned)gy);
+    const dim3 grid((unsigned)p.gx, (unsigned)p.gy);
     if (vec && nt) hipLaunchKernelGGL((k_dense_t<T, true, true>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, nseg, n, (const T *)D->A, D->lda, x, part);
     else if (vec) hipLaunchKernelGGL((k_dense_t<T, true, false>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, nseg, n, (const T *)D->A, D->lda, x, part);
     else hipLaunchKernelGGL((k_dense_t<T, false, false>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, nseg, n, (const T *)D->A, D->lda, x, part);
@@ -137,6 +178,22 @@ extern "C" int mik_dense_mul(mik_dense *D, int adjoint, const void *x, void *y)
     if (D->dtype == MIK_F64)
         return adjoint ? dm_mul_t<double>(D, (const double *)x, (double *)y) : dm_mul_n<double>(D, (const double *)x, (double *)y);
     return adjoint ? dm_mul_t<float>(D, (const float *)x, (float *)y) : dm_mul_n<float>(D, (const float *)x, (float *)y);
+}
+
+extern "C" int mik_dev_dense_plan(const mik_dense *D, int adjoint, const void *x, const void *y, int *vec, int *streamed, int64_t *grid_x,
+                                  int64_t *grid_y, int64_t *chunks_or_batches, int64_t *segments)
+{
+    if (!D) return MIK_ERR_INVALID;
+    dm_plan p;
+    if (D->dtype == MIK_F64) p = adjoint ? dm_plan_t<double>(D, (const double *)x, (const double *)y) : dm_plan_n<double>(D, (const double *)x, (const double *)y);
+    else p = adjoint ? dm_plan_t<float>(D, (const float *)x, (const float *)y) : dm_plan_n<float>(D, (const float *)x, (const float *)y);
+    if (vec) *vec = p.vec;
+    if (streamed) *streamed = p.streamed;
+    if (grid_x) *grid_x = p.gx;
+    if (grid_y) *grid_y = p.gy;
+    if (chunks_or_batches) *chunks_or_batches = p.cols;
+    if (segments) *segments = p.nseg;
+    return MIK_OK;
 }
 
 extern "C" int mik_dense_mul_fn(void *user, const void *x, void *y) { return mik_dense_mul((mik_dense *)user, 0, x, y); }

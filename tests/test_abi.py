@@ -71,6 +71,21 @@ def test_ctypes_binding_covers_header(pkg):
     assert L.mik_abi_version() == 6
 
 
+def test_development_queries_are_declared_in_the_development_header_only_and_bound_with_their_argument_counts(pkg):
+    """mik_dev_* (mik_dev_gmres_form, mik_dev_dense_plan, ...): exported and bound, never part of the boundary header"""
+    boundary = open(HEADER).read()
+    dev = re.sub(r"/\*.*?\*/", "", open(DEV_HEADER).read(), flags=re.S)
+    names = sorted(n for n in pkg._lib.SIGNATURES if n.startswith("mik_dev_"))
+    assert "mik_dev_gmres_form" in names and "mik_dev_dense_plan" in names
+    for name in names:
+        assert name not in boundary, name
+        decl = re.search(rf"\bint {name}\(([^;]*)\);", dev)
+        assert decl, name
+        assert len(decl.group(1).split(",")) == len(pkg._lib.SIGNATURES[name][1]), name
+        assert callable(getattr(pkg.lib(), name))
+    assert "MIK_ABI_VERSION 6" in boundary                                       # additive: the boundary and its version are untouched
+
+
 def test_reduce_shape_is_exported_constant(pkg):
     L = pkg.lib()
     w, l = C.c_int(), C.c_int()

@@ -92,6 +92,23 @@ def test_header_binding_and_export_agree_on_the_entries(pkg):
     assert L.mik_dense_create(None, 0, 1, 1, None, 1, None) == 1 and L.mik_dense_destroy(None) == 0       # MIK_ERR_INVALID, no device needed
 
 
+def test_the_launch_plan_query_is_a_development_entry_and_fails_cleanly_without_a_handle(pkg):
+    dev = open(os.path.join(ROOT, "include", "mik_dev.h")).read()
+    assert "mik_dev_dense_plan" not in HEADER and re.search(r"\bint mik_dev_dense_plan\(const mik_dense \*D, int adjoint,", dev)
+    v, s = C.c_int(-1), C.c_int(-1)
+    g = [C.c_int64(-1) for _ in range(4)]
+    assert pkg.lib().mik_dev_dense_plan(None, 0, None, None, C.byref(v), C.byref(s), *[C.byref(q) for q in g]) == 1       # MIK_ERR_INVALID
+    assert (v.value, s.value) == (-1, -1) and all(q.value == -1 for q in g)                                              # nothing was written
+    src = open(os.path.join(ROOT, "iterativesolvers.jl_amd", "csrc", "mik_dense_mul.hip")).read()
+    hdr = open(os.path.join(ROOT, "iterativesolvers.jl_amd", "csrc", "mik_dense_mul.h")).read()
+    assert "192.0e6" not in src and hdr.count("192.0e6") == 1 and "MIK_DM_STREAM_BYTES" in src     # the streaming threshold has one home
+    for fn in ("dm_mul_n", "dm_mul_t"):                                                             # launch and query share the helper
+        body = src[src.index(f"int {fn}("):]
+        assert f"dm_plan_{fn[-1]}<T>(D, x, y)" in body[:body.index("return MIK_OK;\n}")]
+    q = src[src.index('extern "C" int mik_dev_dense_plan('):]
+    assert "dm_plan_n<double>" in q and "dm_plan_t<float>" in q[:q.index("\n}\n")]
+
+
 # ---- 3: the Python layer on the numpy double ------------------------------------------------------------------------------------
 @pytest.fixture
 def double(pkg, ref, monkeypatch):

@@ -13,55 +13,12 @@ import numpy as np
 import pytest
 
 import dense_operator_host as dh
+from dense_operator_host import Raw, V, ref, shape  # noqa: F401  (ref, shape: fixtures)
 from test_svdl_host import diag_case
 
 pytestmark = pytest.mark.gpu
 _vp = C.c_void_p
 DTYPES = [np.float64, np.float32]
-
-
-@pytest.fixture(scope="session")
-def ref(tmp_path_factory):
-    return dh.build(tmp_path_factory.mktemp("dense_mul_ref"))
-
-
-@pytest.fixture(scope="session")
-def shape(pkg):
-    c, r = C.c_int(), C.c_int()
-    assert pkg.lib().mik_dense_mul_shape(C.byref(c), C.byref(r)) == 0
-    assert c.value in (32, 64, 128, 256) and r.value >= 64
-    return c.value, r.value
-
-
-def V(pkg, ctx, a):
-    return pkg.HipVector.from_numpy(np.ascontiguousarray(a), ctx)
-
-
-class Raw:
-    """A matrix in a raw device buffer with its own mik_dense handle: leading dimension lda, the first element `off` elements into the
-    allocation (off = 1: no column start is 16-byte aligned for Float64, and with an odd lda none but every fourth for Float32 -- the
-    scalar-load variant).  The padding rows are NaN: they must never be read."""
-
-    def __init__(self, pkg, ctx, A, lda, off=1):
-        self.pkg, self.ctx, self.m, self.n, self.lda, self.off = pkg, ctx, A.shape[0], A.shape[1], int(lda), off
-        store = np.full((self.lda, max(self.n, 1)), np.nan, A.dtype, order="F")
-        store[:self.m, :self.n] = A
-        self.buf = pkg.HipVector(off + store.size, A.dtype, ctx)
-        self.buf.copy_from_host(np.concatenate([np.full(off, np.nan, A.dtype), store.reshape(-1, order="F")]))
-        self.h = _vp()
-        self.rc = pkg.lib().mik_dense_create(ctx.handle, pkg._lib.dtype_code(A.dtype), self.m, self.n, _vp(self.buf.ptr + off * A.dtype.itemsize),
-                                             self.lda, C.byref(self.h))
-
-    def col(self, j):
-        return self.buf.view(self.off + j * self.lda, self.m)
-
-    def mul(self, adjoint, x, y):
-        return self.pkg.lib().mik_dense_mul(self.h, int(adjoint), _vp(x.ptr), _vp(y.ptr))
-
-    def close(self):
-        if self.h:
-            self.pkg.lib().mik_dense_destroy(self.h)
-            self.h = None
 
 
 def full_csc(A):
