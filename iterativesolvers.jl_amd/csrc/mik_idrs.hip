@@ -136,19 +136,17 @@ template <typename T> struct OpIdrsBiorth {
     }
 };
 
-// alpha = dot(P[i], G[k]) / M[i, i] in front of the sweep that uses it (k_map_with)                                       -- :208
+// alpha = dot(P[i], G[k]) / M[i, i] (:208), once: stored by the finaliser launch (k_fin), or formed by every workgroup of the sweep
+// that uses it (k_map_with)
+template <typename T> __device__ __forceinline__ T idrs_alpha(T dot, T mii) { return dot / mii; }
+template <typename T> struct FinIdrsAlpha {
+    T mii; T *out;
+    __device__ __forceinline__ void operator()(T tot) const { out[0] = idrs_alpha(tot, mii); }
+};
 template <typename T> struct ProIdrsAlpha {
     T mii;
-    __device__ __forceinline__ void operator()(T tot, OpIdrsBiorth<T> &op, bool) const { op.alpha = Coef<T>{nullptr, tot / mii}; }
+    __device__ __forceinline__ void operator()(T tot, OpIdrsBiorth<T> &op, bool) const { op.alpha = Coef<T>{nullptr, idrs_alpha(tot, mii)}; }
 };
-
-template <typename T>
-__global__ __launch_bounds__(MIK_FIN_THREADS) void k_idrs_fin_alpha(const T *__restrict__ S, int64_t m, T mii, T *__restrict__ out)
-{
-    __shared__ T lds16[16];
-    const T tot = level2_sum(S, m, lds16);
-    if (threadIdx.x == 0) out[0] = tot / mii;
-}
 
 // beta = f[k] / M[k, k]; R -= beta G[k]; X += beta U[k]; partial sums of R.^2                                            -- :221-225
 template <typename T> struct OpIdrsUpdate {
@@ -299,16 +297,10 @@ struct mik_idrs {
     void *host = nullptr;                 // IdrsHost<T>
 };
 
-static void idrs_disown(mik_ctx *ctx, void *h)
-{
-    for (size_t i = 0; i < ctx->owned.size(); ++i)
-        if (ctx->owned[i].first == h) { ctx->owned.erase(ctx->owned.begin() + (long)i); return; }
-}
-
 extern "C" int mik_idrs_destroy(mik_idrs *it)
 {
     if (!it) return MIK_OK;
-    idrs_disown(it->ctx, it);
+    mik_ctx_disown(it->ctx, it);
     (void)hipSetDevice(it->ctx->device);
     (void)hipStreamSynchronize(it->ctx->stream);
     if (it->q) (void)hipFree(it->q);
@@ -441,8 +433,7 @@ template <typename T> static int idrs_step_impl(mik_idrs *it, int step, T *normR
                 if (lean) {
                     MIK_TRY((launch_map_with<T>(ctx, n, op, ProIdrsAlpha<T>{MM(i, i)}, vecp, (const T *)cur, (int)nseg, nxt)));
                 } else {
-                    hipLaunchKernelGGL((k_idrs_fin_alpha<T>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)cur, nseg, MM(i, i), dev + IDRS_SLOT_ALPHA);
-                    MIK_LAUNCH_CHECK(ctx);
+                    MIK_TRY(launch_fin<T>(ctx, (const T *)cur, nseg, FinIdrsAlpha<T>{MM(i, i), dev + IDRS_SLOT_ALPHA}));
                     MIK_TRY((launch_map<T>(ctx, n, op, vecp, nxt, nullptr)));
                 }
                 T *t = cur; cur = nxt; nxt = t;

@@ -61,6 +61,13 @@ struct mik_ctx {
     std::vector<std::pair<void *, int (*)(void *)>> owned;
 };
 
+// A whole-iteration handle that is being destroyed leaves its context's list
+static inline void mik_ctx_disown(mik_ctx *ctx, void *h)
+{
+    for (size_t i = 0; i < ctx->owned.size(); ++i)
+        if (ctx->owned[i].first == h) { ctx->owned.erase(ctx->owned.begin() + (long)i); return; }
+}
+
 // The machine shape the selection paths plan for: what the device reported, unless the development knob MIK_KNOB_MACHINE
 // (compute units | XCDs << 16) overrides it for a test.
 static inline int mik_cus(const mik_ctx *ctx) { const int v = ctx->tuning[MIK_KNOB_MACHINE] & 0xFFFF; return v > 0 ? v : std::max(1, ctx->cu_count); }
@@ -449,6 +456,29 @@ static inline hipError_t mik_wait(mik_ctx *ctx)
         if (rc_ != MIK_OK) return rc_; \
     } while (0)
 
+// Wait until the device has stored `want` in the host-mapped sequence word *seq -- the closing kernel of a step publishes it with system
+// scope (bounded spin; the per-iteration waits of the solvers: no event, no copy engine in the path).  Every ~1M polls: has the stream
+// died, or finished without publishing?  who / what / waiting_for word the refusal: "<who>: stream idle but <what> N was never
+// published", "<who>: <HIP error> while waiting for <waiting_for>" (nullptr: "<who>: <HIP error>").
+static inline int mik_wait_seq(mik_ctx *ctx, const unsigned long long *seq, unsigned long long want, const char *who, const char *what,
+                               const char *waiting_for)
+{
+    for (unsigned long long spins = 0;; ++spins) {
+        if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) == want) return MIK_OK;
+        if ((spins & 0xFFFFF) == 0xFFFFF) {
+            const hipError_t e = hipStreamQuery(ctx->stream);
+            if (e == hipSuccess) {
+                if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) == want) return MIK_OK;
+                return mik_fail(ctx, MIK_ERR_HIP, "%s: stream idle but %s %llu was never published", who, what, want);
+            }
+            if (e != hipErrorNotReady)
+                return mik_fail(ctx, MIK_ERR_HIP, "%s: %s%s%s", who, hipGetErrorString(e), waiting_for ? " while waiting for " : "", waiting_for ? waiting_for : "");
+        }
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+    }
+}
 
 // `count` values of the device array `dev`, as soon as everything enqueued before has run.  A one-wave kernel copies them into the
 // context's pinned mailbox and then stores a ticket (system scope); the host spins on the ticket -- no copy engine, no event in
@@ -475,20 +505,7 @@ template <typename T> static inline int mik_read_scalars(mik_ctx *ctx, const T *
     const unsigned long long want = ++ctx->pub_seq;
     hipLaunchKernelGGL((k_publish<T>), dim3(1), dim3(64), 0, ctx->stream, dev, count, (T *)ctx->pub, ticket, want);
     MIK_LAUNCH_CHECK(ctx);
-    for (unsigned long long spins = 0;; ++spins) {
-        if (__atomic_load_n(ticket, __ATOMIC_ACQUIRE) == want) break;
-        if ((spins & 0xFFFFF) == 0xFFFFF) {                  // every ~1M polls: has the stream died, or finished without publishing?
-            const hipError_t e = hipStreamQuery(ctx->stream);
-            if (e == hipSuccess) {
-                if (__atomic_load_n(ticket, __ATOMIC_ACQUIRE) == want) break;
-                return mik_fail(ctx, MIK_ERR_HIP, "scalar read: stream idle but ticket %llu was never published", want);
-            }
-            if (e != hipErrorNotReady) return mik_fail(ctx, MIK_ERR_HIP, "scalar read: %s", hipGetErrorString(e));
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
+    MIK_TRY(mik_wait_seq(ctx, ticket, want, "scalar read", "ticket", nullptr));
     memcpy(host_out, ctx->pub, sizeof(T) * count);
     return MIK_OK;
 }

@@ -114,6 +114,37 @@ template <typename T> __device__ __forceinline__ bool level2_sum_spread(const T 
     return last;
 }
 
+// A level-2 finaliser launch whose scalar statements are a functor, in the two shapes of the tree: one workgroup of MIK_FIN_THREADS
+// (level2_sum), or MIK_FIN_WGS single-wave workgroups and the FinScratch ticket (level2_sum_spread).  Either forms the total of the m
+// segment sums and hands it to fin(tot) on the one thread that holds it.
+template <typename T, typename Fin>
+__global__ __launch_bounds__(MIK_FIN_THREADS) void k_fin(const T *__restrict__ S, int64_t m, Fin fin)
+{
+    __shared__ T lds16[16];
+    const T tot = level2_sum(S, m, lds16);
+    if (threadIdx.x == 0) fin(tot);
+}
+template <typename T, typename Fin>
+__global__ __launch_bounds__(64) void k_fin_spread(const T *__restrict__ S, int64_t m, Fin fin, FinScratch<T> *fs)
+{
+    T tot;
+    if (level2_sum_spread(S, m, fs, tot)) fin(tot);
+}
+template <typename T, typename Fin> static inline int launch_fin(mik_ctx *ctx, const T *S, int64_t m, Fin fin)
+{
+    hipLaunchKernelGGL((k_fin<T, Fin>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, S, m, fin);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+// ... spread above 16,384 partials (one per 256-row block when an SpMV launch formed the sum), for a caller that has a FinScratch
+template <typename T, typename Fin> static inline int launch_fin(mik_ctx *ctx, const T *S, int64_t m, Fin fin, FinScratch<T> *fs)
+{
+    if (m <= 16384) return launch_fin<T>(ctx, S, m, fin);
+    hipLaunchKernelGGL((k_fin_spread<T, Fin>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, S, m, fin, fs);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
 // residual = norm(r) of a row-partitioned step from the rank-ordered total of |r|^2 (src/cg.jl:61-62), history, beta and the stopping test
 // of :36 for the next iterate() call; one thread.  A total outside the range of a safe sqrt(sum of squares) freezes the batch on every
 // rank alike (identical totals): x and r of the step are final, the hosts finish it with the scaled norm over the partition.

@@ -7,6 +7,7 @@
 // Julia broadcast (src/cg.jl:51,58-59) and SparseArrays' `y[i] += a * x` scatter.
 #pragma once
 #include <algorithm>
+#include <type_traits>
 
 #include "mik_internal.h"
 
@@ -24,34 +25,64 @@
 // Segment s = 256*W*L elements; thread t owns, for l = 0..L-1, the W elements starting at
 // s*SEG + l*256*W + W*t (coalesced 16-byte loads), accumulated in that order.
 
-template <typename T, bool VEC, typename Op>
-__global__ __launch_bounds__(MIK_BLOCK) void k_map(int64_t n, int64_t nseg, Op op, T *__restrict__ seg_out,
-                                                    const int *__restrict__ done)
+// The segment walk, written once.  map_segment: this thread's L 16-byte groups of segment s (a group that does not lie whole inside n, or
+// any group when !VEC, goes element by element); the accumulators are whatever Op::apply / apply_vec take (none used, one, or two: k_map2).
+template <typename T, bool VEC, typename Op, typename... Acc>
+__device__ __forceinline__ void map_segment(const Op &op, int64_t s, int64_t n, Acc &...acc)
 {
-    if (done && *done) return;
     constexpr int W = VT<T>::W;
     constexpr int L = MIK_RED_L;
     constexpr int64_t SEG = (int64_t)MIK_BLOCK * W * L;
-    __shared__ T lds4[4];
-    for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const int64_t base = s * SEG + (int64_t)W * threadIdx.x;
-        T acc = T(0);
+    const int64_t base = s * SEG + (int64_t)W * threadIdx.x;
 #pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-            if (VEC && i + W <= n) {
-                op.apply_vec(i, acc);
-            } else {
+    for (int l = 0; l < L; ++l) {
+        const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
+        if (VEC && i + W <= n) {
+            op.apply_vec(i, acc...);
+        } else {
 #pragma unroll
-                for (int e = 0; e < W; ++e)
-                    if (i + e < n) op.apply(i + e, acc);
-            }
+            for (int e = 0; e < W; ++e)
+                if (i + e < n) op.apply(i + e, acc...);
         }
+    }
+}
+
+// map_sweep: the grid-stride loop over the segments; a reducing Op leaves the level-1 sum of segment s in seg_out[s]
+template <typename T, bool VEC, typename Op>
+__device__ __forceinline__ void map_sweep(const Op &op, int64_t n, int64_t nseg, T *__restrict__ seg_out, T *lds4)
+{
+    for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
+        T acc = T(0);
+        map_segment<T, VEC>(op, s, n, acc);
         if (Op::REDUCE) {
             T tot = block_tree_256(acc, lds4);
             if (threadIdx.x == 0) seg_out[s] = tot;
         }
     }
+}
+
+// Host side of the four launchers: one workgroup per segment, capped grid (the kernels stride over the rest), at least min_grid
+// workgroups -- an empty vector launches nothing when min_grid is 0 -- and the 16-byte or the element-wise instance;
+// go(std::bool_constant<VEC>, grid, nseg) launches it.
+template <typename T, typename Go>
+static inline int launch_segments(mik_ctx *ctx, int64_t n, bool vec, int min_grid, Go go)
+{
+    const int64_t nseg = mik_nseg<T>(n);
+    const int grid = (int)std::max<int64_t>(min_grid, std::min<int64_t>(nseg, mik_max_grid(ctx)));
+    if (grid == 0) return MIK_OK;
+    if (vec) go(std::true_type(), grid, nseg);
+    else go(std::false_type(), grid, nseg);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
+template <typename T, bool VEC, typename Op>
+__global__ __launch_bounds__(MIK_BLOCK) void k_map(int64_t n, int64_t nseg, Op op, T *__restrict__ seg_out,
+                                                    const int *__restrict__ done)
+{
+    if (done && *done) return;
+    __shared__ T lds4[4];
+    map_sweep<T, VEC>(op, n, nseg, seg_out, lds4);
 }
 
 // k_map whose coefficient is the level-2 sum of a PRODUCER kernel's segment sums, finalised by every
@@ -77,6 +108,7 @@ __global__ __launch_bounds__(MIK_BLOCK) void k_map_pro(int64_t n, int64_t nseg, 
     __shared__ T lds4[4];
     // One segment per workgroup (n up to ~1M, the launch-bound regime): issue the vector loads BEFORE the
     // prologue, so their latency overlaps the prologue's load -> wave trees -> LDS chain instead of following it.
+    // (load_vec / compute_vec: another body than map_segment's, so this arm stays written out.)
     const bool ahead = nseg <= (int64_t)gridDim.x && (int64_t)blockIdx.x < nseg;
     typename Op::Regs rg[L];
     bool full[L];
@@ -122,53 +154,25 @@ __global__ __launch_bounds__(MIK_BLOCK) void k_map_pro(int64_t n, int64_t nseg, 
         }
         return;
     }
-    for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const int64_t base = s * SEG + (int64_t)W * threadIdx.x;
-        T acc = T(0);
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-            if (VEC && i + W <= n) {
-                op.apply_vec(i, acc);
-            } else {
-#pragma unroll
-                for (int e = 0; e < W; ++e)
-                    if (i + e < n) op.apply(i + e, acc);
-            }
-        }
-        if (Op::REDUCE) {
-            T tot = block_tree_256(acc, lds4);
-            if (threadIdx.x == 0) seg_out[s] = tot;
-        }
-    }
+    map_sweep<T, VEC>(op, n, nseg, seg_out, lds4);
 }
 
+// (a grid of at least 1 and no early return on an empty vector: workgroup 0 publishes the coefficient)
 template <typename T, int PRO, typename Op, typename X = NoExchange>
 static inline int launch_map_pro(mik_ctx *ctx, int64_t n, Op op, bool vec, T *seg_out, const T *prev_part, int prev_m, T *coef_out, X xch = X())
 {
-    const int64_t nseg = mik_nseg<T>(n);
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nseg, mik_max_grid(ctx)));   // >= 1: workgroup 0 publishes the coefficient
-    if (vec)
-        hipLaunchKernelGGL((k_map_pro<T, true, Op, PRO, X>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, op, seg_out, prev_part, prev_m, coef_out, xch);
-    else
-        hipLaunchKernelGGL((k_map_pro<T, false, Op, PRO, X>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, op, seg_out, prev_part, prev_m, coef_out, xch);
-    MIK_LAUNCH_CHECK(ctx);
-    return MIK_OK;
+    return launch_segments<T>(ctx, n, vec, 1, [&](auto v, int grid, int64_t nseg) {
+        hipLaunchKernelGGL((k_map_pro<T, decltype(v)::value, Op, PRO, X>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, op, seg_out, prev_part, prev_m, coef_out, xch);
+    });
 }
 
 // host-side launcher of k_map: one workgroup per segment, capped grid with a grid-stride loop
 template <typename T, typename Op>
 static inline int launch_map(mik_ctx *ctx, int64_t n, Op op, bool vec, T *seg_out, const int *done)
 {
-    const int64_t nseg = mik_nseg<T>(n);
-    if (nseg == 0) return MIK_OK;
-    const int grid = (int)std::min<int64_t>(nseg, mik_max_grid(ctx));
-    if (vec)
-        hipLaunchKernelGGL((k_map<T, true, Op>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, op, seg_out, done);
-    else
-        hipLaunchKernelGGL((k_map<T, false, Op>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, op, seg_out, done);
-    MIK_LAUNCH_CHECK(ctx);
-    return MIK_OK;
+    return launch_segments<T>(ctx, n, vec, 0, [&](auto v, int grid, int64_t nseg) {
+        hipLaunchKernelGGL((k_map<T, decltype(v)::value, Op>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, op, seg_out, done);
+    });
 }
 
 // k_map with TWO reductions over the same sweep (Op::apply / apply_vec take two accumulators): both keep the segment / thread /
@@ -178,24 +182,10 @@ __global__ __launch_bounds__(MIK_BLOCK) void k_map2(int64_t n, int64_t nseg, Op 
                                                      const int *__restrict__ done)
 {
     if (done && *done) return;
-    constexpr int W = VT<T>::W;
-    constexpr int L = MIK_RED_L;
-    constexpr int64_t SEG = (int64_t)MIK_BLOCK * W * L;
     __shared__ T lds4[4];
     for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const int64_t base = s * SEG + (int64_t)W * threadIdx.x;
         T a1 = T(0), a2 = T(0);
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-            if (VEC && i + W <= n) {
-                op.apply_vec(i, a1, a2);
-            } else {
-#pragma unroll
-                for (int e = 0; e < W; ++e)
-                    if (i + e < n) op.apply(i + e, a1, a2);
-            }
-        }
+        map_segment<T, VEC>(op, s, n, a1, a2);
         const T t1 = block_tree_256(a1, lds4);
         const T t2 = block_tree_256(a2, lds4);
         if (threadIdx.x == 0) { seg1[s] = t1; seg2[s] = t2; }
@@ -205,13 +195,9 @@ __global__ __launch_bounds__(MIK_BLOCK) void k_map2(int64_t n, int64_t nseg, Op 
 template <typename T, typename Op>
 static inline int launch_map2(mik_ctx *ctx, int64_t n, Op op, bool vec, T *seg1, T *seg2, const int *done)
 {
-    const int64_t nseg = mik_nseg<T>(n);
-    if (nseg == 0) return MIK_OK;
-    const int grid = (int)std::min<int64_t>(nseg, mik_max_grid(ctx));
-    if (vec) hipLaunchKernelGGL((k_map2<T, true, Op>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, op, seg1, seg2, done);
-    else hipLaunchKernelGGL((k_map2<T, false, Op>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, op, seg1, seg2, done);
-    MIK_LAUNCH_CHECK(ctx);
-    return MIK_OK;
+    return launch_segments<T>(ctx, n, vec, 0, [&](auto v, int grid, int64_t nseg) {
+        hipLaunchKernelGGL((k_map2<T, decltype(v)::value, Op>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, op, seg1, seg2, done);
+    });
 }
 
 // k_map whose coefficient comes from the level-2 sum of the PRODUCER's segment sums, formed by every workgroup itself (m <= 1024
@@ -221,44 +207,19 @@ static inline int launch_map2(mik_ctx *ctx, int64_t n, Op op, bool vec, T *seg1,
 template <typename T, bool VEC, typename Op, typename Pro>
 __global__ __launch_bounds__(MIK_BLOCK) void k_map_with(int64_t n, int64_t nseg, Op op, Pro pro, const T *__restrict__ part, int m, T *__restrict__ seg_out)
 {
-    constexpr int W = VT<T>::W;
-    constexpr int L = MIK_RED_L;
-    constexpr int64_t SEG = (int64_t)MIK_BLOCK * W * L;
     __shared__ T lds16[16];
     __shared__ T lds4[4];
     const T tot = block_level2_256(part, m, lds16);
     pro(tot, op, blockIdx.x == 0 && threadIdx.x == 0);
-    for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
-        const int64_t base = s * SEG + (int64_t)W * threadIdx.x;
-        T acc = T(0);
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int64_t i = base + (int64_t)l * MIK_BLOCK * W;
-            if (VEC && i + W <= n) {
-                op.apply_vec(i, acc);
-            } else {
-#pragma unroll
-                for (int e = 0; e < W; ++e)
-                    if (i + e < n) op.apply(i + e, acc);
-            }
-        }
-        if (Op::REDUCE) {
-            const T t2 = block_tree_256(acc, lds4);
-            if (threadIdx.x == 0) seg_out[s] = t2;
-        }
-    }
+    map_sweep<T, VEC>(op, n, nseg, seg_out, lds4);
 }
 
 template <typename T, typename Op, typename Pro>
 static inline int launch_map_with(mik_ctx *ctx, int64_t n, Op op, Pro pro, bool vec, const T *part, int m, T *seg_out)
 {
-    const int64_t nseg = mik_nseg<T>(n);
-    if (nseg == 0) return MIK_OK;
-    const int grid = (int)std::min<int64_t>(nseg, mik_max_grid(ctx));
-    if (vec) hipLaunchKernelGGL((k_map_with<T, true, Op, Pro>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, op, pro, part, m, seg_out);
-    else hipLaunchKernelGGL((k_map_with<T, false, Op, Pro>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, op, pro, part, m, seg_out);
-    MIK_LAUNCH_CHECK(ctx);
-    return MIK_OK;
+    return launch_segments<T>(ctx, n, vec, 0, [&](auto v, int grid, int64_t nseg) {
+        hipLaunchKernelGGL((k_map_with<T, decltype(v)::value, Op, Pro>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, n, nseg, op, pro, part, m, seg_out);
+    });
 }
 
 template <typename T> __device__ __forceinline__ typename VT<T>::vec vload(const T *p)
@@ -420,8 +381,10 @@ template <typename T> __device__ __forceinline__ T pair_total(const T (&slot)[4]
     return tot;
 }
 
-// Helper macro: define apply_vec in terms of a per-element lambda over loaded vectors is not
-// possible generically, so each op spells out its loads (all issued before the arithmetic).
+// What the Ops below share is the walk (map_segment / map_sweep above): which groups a thread owns, the full-group test, the element
+// tail, the level-1 tree.  What they do not share is the body: an apply_vec cannot be derived from apply by a per-element lambda over
+// loaded vectors -- which operands are loaded non-temporally, and that all loads are issued before the arithmetic, differ from Op to
+// Op -- so each Op spells out both.
 
 // y .= x .+ beta .* y            -- src/cg.jl:51  (u .= r .+ beta .* u), :86
 template <typename T> struct OpXpby {

@@ -862,22 +862,7 @@ template <typename T> static int cg_enqueue_tail(mik_cg *it, long long it_next, 
 // Wait until the device has published step `seq` in the host-mapped mirror (bounded spin).
 int cg_wait_mirror(mik_cg *it)
 {
-    volatile unsigned long long *p = &it->mirror->seq;
-    const unsigned long long want = it->seq;
-    for (unsigned long long spins = 0;; ++spins) {
-        if (__atomic_load_n((const unsigned long long *)p, __ATOMIC_ACQUIRE) == want) return MIK_OK;
-        if ((spins & 0xFFFFF) == 0xFFFFF) {   // every ~1M polls: has the stream died or finished without publishing?
-            hipError_t e = hipStreamQuery(it->ctx->stream);
-            if (e == hipSuccess) {
-                if (__atomic_load_n((const unsigned long long *)p, __ATOMIC_ACQUIRE) == want) return MIK_OK;
-                return mik_fail(it->ctx, MIK_ERR_HIP, "cg: stream idle but step %llu was never published", want);
-            }
-            if (e != hipErrorNotReady) return mik_fail(it->ctx, MIK_ERR_HIP, "cg: %s while waiting for a step", hipGetErrorString(e));
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
+    return mik_wait_seq(it->ctx, &it->mirror->seq, it->seq, "cg", "step", "a step");
 }
 
 template <typename T> static int cg_fetch_state(mik_cg *it, CgDev<T> *host)
@@ -1558,22 +1543,7 @@ template <typename T> static int gm_fused_wait(mik_gmres *g, int k, int slot, T 
 {
     mik_ctx *ctx = g->ctx;
     MgsMirror *mir = gm_mirror(g, slot);
-    const unsigned long long want = g->mgs_slot_seq[slot];
-    volatile unsigned long long *p = &mir->seq;
-    for (unsigned long long spins = 0;; ++spins) {
-        if (__atomic_load_n((const unsigned long long *)p, __ATOMIC_ACQUIRE) == want) break;
-        if ((spins & 0xFFFFF) == 0xFFFFF) {
-            hipError_t e = hipStreamQuery(ctx->stream);
-            if (e == hipSuccess) {
-                if (__atomic_load_n((const unsigned long long *)p, __ATOMIC_ACQUIRE) == want) break;
-                return mik_fail(ctx, MIK_ERR_HIP, "gmres: stream idle but the Gram-Schmidt step %llu was never published", want);
-            }
-            if (e != hipErrorNotReady) return mik_fail(ctx, MIK_ERR_HIP, "gmres: %s while waiting for the Gram-Schmidt step", hipGetErrorString(e));
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
+    MIK_TRY(mik_wait_seq(ctx, &mir->seq, g->mgs_slot_seq[slot], "gmres", "the Gram-Schmidt step", "the Gram-Schmidt step"));
     if (mir->err || ctx->tuning[MIK_KNOB_GS_TIMEOUT] == 1) return MIK_GS_TIMEOUT;        // (development knob MIK_KNOB_GS_TIMEOUT: pretend it happened)
     // a workgroup gave up waiting for a slot (GPU shared with other work?): the caller redoes the column
     const T *out = reinterpret_cast<const T *>(mir + 1);

@@ -34,82 +34,59 @@ struct BicgMirror {                 // pinned, written by the last kernel of a s
     unsigned long long seq;
 };
 
-// :89-90 in front of :93 -- what k_bicg_fin_rho does, per workgroup (reads sigma, omega; writes rho: no other workgroup reads it here)
+// The scalar statements between a reduction and the sweep that uses it, once each: a Fin* functor runs them on the one thread of a
+// finaliser launch (k_fin / k_fin_spread) and stores what later kernels read; the Pro* functor of the same statement runs them in
+// every workgroup of the sweep itself (k_map_with), for the sweep's own coefficient.
+//
+// :85, :90 -- beta = rho / sigma, in front of the first column sigma = -omega * sigma before
+template <typename T> __device__ __forceinline__ T bicg_beta(T rho, T &sigma, T omega, int first)
+{
+    if (first) { const T p = omega * sigma; sigma = -p; }
+    return rho / sigma;
+}
+// :101 -- alpha = rho / sigma
+template <typename T> __device__ __forceinline__ T bicg_alpha(T rho, T sigma) { return rho / sigma; }
+
+// rho = dot(r_shadow, rs[:, j]) (:89) in front of :93
+template <typename T> struct FinBicgRho {
+    BicgDev<T> *d; int first;
+    __device__ __forceinline__ void operator()(T tot) const
+    {
+        T sigma = d->sigma;
+        const T beta = bicg_beta(tot, sigma, d->omega, first);
+        if (first) d->sigma = sigma;
+        d->rho = tot;
+        d->neg_beta = -beta;
+    }
+};
+// ... per workgroup of that sweep: every workgroup reads sigma and omega while the launch runs, so only rho -- which no workgroup reads
+// here -- is stored
 template <typename T> struct ProBicgRho {
     BicgDev<T> *d; int first;
     __device__ __forceinline__ void operator()(T tot, OpBicgU<T> &op, bool publish) const
     {
         T sigma = d->sigma;
-        if (first) { const T p = d->omega * sigma; sigma = -p; }
-        const T beta = tot / sigma;
+        const T beta = bicg_beta(tot, sigma, d->omega, first);
         op.neg_beta = Coef<T>{nullptr, -beta};
         if (publish) d->rho = tot;
     }
 };
-// :100-101 in front of :103, :111 -- k_bicg_fin_sigma per workgroup (reads rho; writes sigma for the next column)
+// sigma = dot(r_shadow, us[:, j + 1]) (:100) in front of :103, :111 (reads rho; writes sigma for the next column)
+template <typename T> struct FinBicgSigma {
+    BicgDev<T> *d;
+    __device__ __forceinline__ void store(T sigma, T alpha) const { d->sigma = sigma; d->alpha = alpha; d->neg_alpha = -alpha; }
+    __device__ __forceinline__ void operator()(T tot) const { store(tot, bicg_alpha(d->rho, tot)); }
+};
 template <typename T> struct ProBicgSigma {
     BicgDev<T> *d;
     __device__ __forceinline__ void operator()(T tot, OpBicgR<T> &op, bool publish) const
     {
-        const T alpha = d->rho / tot;
+        const T alpha = bicg_alpha(d->rho, tot);
         op.neg_alpha = Coef<T>{nullptr, -alpha};
         op.alpha = Coef<T>{nullptr, alpha};
-        if (publish) { d->sigma = tot; d->alpha = alpha; d->neg_alpha = -alpha; }
+        if (publish) FinBicgSigma<T>{d}.store(tot, alpha);
     }
 };
-
-// rho = dot(r_shadow, rs[:, j]) (:89); beta = rho / sigma (:90); first: sigma = -omega * sigma before (:85)
-template <typename T>
-__global__ __launch_bounds__(MIK_FIN_THREADS) void k_bicg_fin_rho(const T *__restrict__ S, int64_t m, BicgDev<T> *d, int first)
-{
-    __shared__ T lds16[16];
-    const T tot = level2_sum(S, m, lds16);
-    if (threadIdx.x == 0) {
-        if (first) { const T p = d->omega * d->sigma; d->sigma = -p; }
-        d->rho = tot;
-        const T beta = tot / d->sigma;
-        d->neg_beta = -beta;
-    }
-}
-
-// sigma = dot(r_shadow, us[:, j + 1]) (:100); alpha = rho / sigma (:101)
-template <typename T>
-__global__ __launch_bounds__(MIK_FIN_THREADS) void k_bicg_fin_sigma(const T *__restrict__ S, int64_t m, BicgDev<T> *d)
-{
-    __shared__ T lds16[16];
-    const T tot = level2_sum(S, m, lds16);
-    if (threadIdx.x == 0) {
-        d->sigma = tot;
-        const T alpha = d->rho / tot;
-        d->alpha = alpha;
-        d->neg_alpha = -alpha;
-    }
-}
-
-// the same two over one partial per 256-row block (rho / sigma formed in the SpMV launch: 65,536 partials at 256^3): 16 single-wave
-// workgroups and a ticket, as k_cg_fin_alpha
-template <typename T>
-__global__ __launch_bounds__(64) void k_bicg_fin_rho_spread(const T *__restrict__ S, int64_t m, BicgDev<T> *d, int first, FinScratch<T> *fs)
-{
-    T tot;
-    if (level2_sum_spread(S, m, fs, tot)) {
-        if (first) { const T p = d->omega * d->sigma; d->sigma = -p; }
-        d->rho = tot;
-        const T beta = tot / d->sigma;
-        d->neg_beta = -beta;
-    }
-}
-template <typename T>
-__global__ __launch_bounds__(64) void k_bicg_fin_sigma_spread(const T *__restrict__ S, int64_t m, BicgDev<T> *d, FinScratch<T> *fs)
-{
-    T tot;
-    if (level2_sum_spread(S, m, fs, tot)) {
-        d->sigma = tot;
-        const T alpha = d->rho / tot;
-        d->alpha = alpha;
-        d->neg_alpha = -alpha;
-    }
-}
 
 // F = lu!(view(M, L, L)); ldiv!(gamma, F, view(M, L, 1)); omega = gamma[l]   (:123-125, :131) -- lu_solve of mik_krylov.hip, on
 // the packed upper triangle the Gram finaliser left (row r, columns r..k-1, r ascending)
@@ -203,16 +180,10 @@ struct mik_bicgstab {
     unsigned long long seq = 0;
 };
 
-static void ctx_disown(mik_ctx *ctx, void *h)
-{
-    for (size_t i = 0; i < ctx->owned.size(); ++i)
-        if (ctx->owned[i].first == h) { ctx->owned.erase(ctx->owned.begin() + (long)i); return; }
-}
-
 extern "C" int mik_bicgstab_destroy(mik_bicgstab *it)
 {
     if (!it) return MIK_OK;
-    ctx_disown(it->ctx, it);
+    mik_ctx_disown(it->ctx, it);
     (void)hipSetDevice(it->ctx->device);
     (void)hipStreamSynchronize(it->ctx->stream);
     if (it->dev) (void)hipFree(it->dev);
@@ -313,9 +284,7 @@ template <typename T> static int bicg_step_impl(mik_bicgstab *it, T *residual)
             OpBicgU<T> op{us, it->ldu, rs, it->ldr, j + 1, Coef<T>{nullptr, T(0)}, bnt};
             MIK_TRY((launch_map_with<T>(ctx, n, op, ProBicgRho<T>{d, j == 0 ? 1 : 0}, blockvec, rpart, (int)mr, (T *)nullptr)));
         } else {
-            if (mr > 16384) hipLaunchKernelGGL((k_bicg_fin_rho_spread<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, rpart, mr, d, j == 0 ? 1 : 0, (FinScratch<T> *)it->fin);
-            else hipLaunchKernelGGL((k_bicg_fin_rho<T>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, rpart, mr, d, j == 0 ? 1 : 0);
-            MIK_LAUNCH_CHECK(ctx);
+            MIK_TRY(launch_fin<T>(ctx, rpart, mr, FinBicgRho<T>{d, j == 0 ? 1 : 0}, (FinScratch<T> *)it->fin));
             OpBicgU<T> op{us, it->ldu, rs, it->ldr, j + 1, coef_ptr<T>(&d->neg_beta), bnt};
             MIK_TRY((launch_map<T>(ctx, n, op, blockvec, (T *)nullptr, nullptr)));
         }
@@ -330,9 +299,7 @@ template <typename T> static int bicg_step_impl(mik_bicgstab *it, T *residual)
             OpBicgR<T> op{us, it->ldu, rs, it->ldr, j + 1, x, Coef<T>{nullptr, T(0)}, Coef<T>{nullptr, T(0)}, bnt};
             MIK_TRY((launch_map_with<T>(ctx, n, op, ProBicgSigma<T>{d}, blockvec, (const T *)ctx->partials, (int)ms, (T *)nullptr)));
         } else {
-            if (ms > 16384) hipLaunchKernelGGL((k_bicg_fin_sigma_spread<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)ctx->partials, ms, d, (FinScratch<T> *)it->fin);
-            else hipLaunchKernelGGL((k_bicg_fin_sigma<T>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)ctx->partials, ms, d);
-            MIK_LAUNCH_CHECK(ctx);
+            MIK_TRY(launch_fin<T>(ctx, (const T *)ctx->partials, ms, FinBicgSigma<T>{d}, (FinScratch<T> *)it->fin));
             OpBicgR<T> op{us, it->ldu, rs, it->ldr, j + 1, x, coef_ptr<T>(&d->neg_alpha), coef_ptr<T>(&d->alpha), bnt};
             MIK_TRY((launch_map<T>(ctx, n, op, blockvec, (T *)nullptr, nullptr)));
         }
@@ -372,20 +339,7 @@ template <typename T> static int bicg_step_impl(mik_bicgstab *it, T *residual)
     hipLaunchKernelGGL((k_bicg_fin_norm<T>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)ctx->partials, nseg, it->mirror, it->seq);
     MIK_LAUNCH_CHECK(ctx);
     // the one host wait of the outer iteration
-    for (unsigned long long spins = 0;; ++spins) {
-        if (__atomic_load_n(&it->mirror->seq, __ATOMIC_ACQUIRE) == it->seq) break;
-        if ((spins & 0xFFFFF) == 0xFFFFF) {
-            const hipError_t e = hipStreamQuery(ctx->stream);
-            if (e == hipSuccess) {
-                if (__atomic_load_n(&it->mirror->seq, __ATOMIC_ACQUIRE) == it->seq) break;
-                return mik_fail(ctx, MIK_ERR_HIP, "bicgstabl: stream idle but step %llu was never published", it->seq);
-            }
-            if (e != hipErrorNotReady) return mik_fail(ctx, MIK_ERR_HIP, "bicgstabl: %s while waiting for a step", hipGetErrorString(e));
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
+    MIK_TRY(mik_wait_seq(ctx, &it->mirror->seq, it->seq, "bicgstabl", "step", "a step"));
     if (it->mirror->singular) {
         // the device state is not steppable any more (gamma = 0, omega stale): the handle stays failed, like the reference's iterable
         // after the SingularException of lu! (src/bicgstabl.jl:124)
@@ -416,7 +370,7 @@ extern "C" int mik_bicgstab_step(mik_bicgstab *it, void *residual)
 // ---- MINRES -----------------------------------------------------------------------------------------------------------------
 // iterate(::MINRESIterable) at src/minres.jl:95-159 with the sweeps of mik_axpy_dot (twice) and mik_minres_update: the Lanczos
 // coefficients, the two Givens rotations, the right-hand side of the least-squares problem and the coefficients of the tail
-// sweep stay on the device (k_minres_fin_proj, k_minres_fin_norm), so the host waits once per iteration -- for |rhs[2]|, the
+// sweep stay on the device (FinMinresProj, k_minres_fin_norm), so the host waits once per iteration -- for |rhs[2]|, the
 // residual norm it returns -- instead of twice in the middle of it.  Same sweeps, same tree, same scalar arithmetic in the
 // element type as the statement-by-statement path of the Python mirror (api.py, MINRESIterable.iterate).
 namespace {
@@ -489,33 +443,22 @@ __device__ void minres_scalars(MinresDev<T> *d, T h3, long long iteration, int s
     __hip_atomic_store(&mirror->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// :107 in front of :109 -- k_minres_fin_proj per workgroup of the orthogonalisation sweep (k_map_with)
+// proj = dot(v_curr, v_next) (:107): the coefficient of v_next -= proj v_curr (:109)
+template <typename T> __device__ __forceinline__ T minres_neg_proj(T proj) { return -proj; }
+// H[3] = proj (:107) and that coefficient, for the kernels behind the finaliser launch ...
+template <typename T> struct FinMinresProj {
+    MinresDev<T> *d;
+    __device__ __forceinline__ void operator()(T tot) const { d->H[2] = tot; d->neg_proj = minres_neg_proj(tot); }
+};
+// ... and per workgroup of the orthogonalisation sweep itself (k_map_with)
 template <typename T> struct ProMinresProj {
     MinresDev<T> *d;
     __device__ __forceinline__ void operator()(T tot, OpAxpyDot<T> &op, bool publish) const
     {
-        op.alpha = Coef<T>{nullptr, -tot};
-        if (publish) { d->H[2] = tot; d->neg_proj = -tot; }
+        op.alpha = Coef<T>{nullptr, minres_neg_proj(tot)};
+        if (publish) FinMinresProj<T>{d}(tot);
     }
 };
-
-// proj = dot(v_curr, v_next) (:107): H[3] = proj, the coefficient of :109
-template <typename T>
-__global__ __launch_bounds__(MIK_FIN_THREADS) void k_minres_fin_proj(const T *__restrict__ S, int64_t m, MinresDev<T> *d)
-{
-    __shared__ T lds16[16];
-    const T tot = level2_sum(S, m, lds16);
-    if (threadIdx.x == 0) { d->H[2] = tot; d->neg_proj = -tot; }
-}
-
-// the same over many partials (one per 256-row block when the SpMV forms proj): 16 single-wave workgroups and a ticket, as k_cg_fin_alpha --
-// a single 1024-thread workgroup pulls 65,536 partials through one CU (11 us at 256^3 instead of 5)
-template <typename T>
-__global__ __launch_bounds__(64) void k_minres_fin_proj_spread(const T *__restrict__ S, int64_t m, MinresDev<T> *d, FinScratch<T> *fs)
-{
-    T tot;
-    if (level2_sum_spread(S, m, fs, tot)) { d->H[2] = tot; d->neg_proj = -tot; }
-}
 
 // H[4] = norm(v_next) (:112), then the scalar part of the iteration
 template <typename T>
@@ -565,7 +508,7 @@ struct mik_minres {
 extern "C" int mik_minres_destroy(mik_minres *it)
 {
     if (!it) return MIK_OK;
-    ctx_disown(it->ctx, it);
+    mik_ctx_disown(it->ctx, it);
     (void)hipSetDevice(it->ctx->device);
     (void)hipStreamSynchronize(it->ctx->stream);
     if (it->dev) (void)hipFree(it->dev);
@@ -619,24 +562,6 @@ extern "C" int mik_minres_create(mik_ctx *ctx, const mik_csr *A, void *x, void *
     return MIK_OK;
 }
 
-template <typename T> static int minres_wait(mik_minres *it)
-{
-    for (unsigned long long spins = 0;; ++spins) {
-        if (__atomic_load_n(&it->mirror->seq, __ATOMIC_ACQUIRE) == it->seq) return MIK_OK;
-        if ((spins & 0xFFFFF) == 0xFFFFF) {
-            const hipError_t e = hipStreamQuery(it->ctx->stream);
-            if (e == hipSuccess) {
-                if (__atomic_load_n(&it->mirror->seq, __ATOMIC_ACQUIRE) == it->seq) return MIK_OK;
-                return mik_fail(it->ctx, MIK_ERR_HIP, "minres: stream idle but iteration %llu was never published", it->seq);
-            }
-            if (e != hipErrorNotReady) return mik_fail(it->ctx, MIK_ERR_HIP, "minres: %s while waiting for an iteration", hipGetErrorString(e));
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-}
-
 // Does this step's Lanczos update ride on the SpMV launch?  Asked per step, like bicg_fuses: the operator's layout and the development knobs
 // may change between steps (mik_csr_set_layout, mik_set_tuning) -- the step then falls back to the separate sweep instead of failing, and
 // mik_minres_proj_shape reports the shape of the NEXT step's projection.
@@ -671,11 +596,7 @@ template <typename T> static int minres_step_impl(mik_minres *it, int64_t iterat
         const bool vec = mik_aligned16(v_next) && (!xp || mik_aligned16(xp)) && mik_aligned16(v_curr);
         MIK_TRY((launch_map<T>(ctx, n, op, vec, part_a, nullptr)));
     }
-    if (!lean) {
-        if (na > 16384) hipLaunchKernelGGL((k_minres_fin_proj_spread<T>), dim3(MIK_FIN_WGS), dim3(64), 0, ctx->stream, (const T *)part_a, na, d, (FinScratch<T> *)it->fin);
-        else hipLaunchKernelGGL((k_minres_fin_proj<T>), dim3(1), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const T *)part_a, na, d);
-        MIK_LAUNCH_CHECK(ctx);
-    }
+    if (!lean) MIK_TRY(launch_fin<T>(ctx, (const T *)part_a, na, FinMinresProj<T>{d}, (FinScratch<T> *)it->fin));   // (65,536 partials at 256^3: 5 us spread, 11 us through one CU)
     it->seq += 1;
     {   // v_next -= proj v_curr; H[4] = norm(v_next)                                                          :109, :112
         OpAxpyDot<T> op{v_curr, v_next, nullptr, coef_ptr<T>(&d->neg_proj), 0};
@@ -695,7 +616,7 @@ template <typename T> static int minres_step_impl(mik_minres *it, int64_t iterat
         return launch_map<T>(ctx, n, op, vec, (T *)nullptr, (const int *)&d->range);     // held back while the norm is being rescaled
     };
     MIK_TRY(tail());
-    MIK_TRY(minres_wait<T>(it));
+    MIK_TRY(mik_wait_seq(ctx, &it->mirror->seq, it->seq, "minres", "iteration", "an iteration"));
     if (it->mirror->range) {       // |v_next|^2 outside the range of a safe sum of squares: the scaled norm, then the scalars and the tail
         T h3;
         MIK_TRY(mik_safe_norm_slow<T>(ctx, n, v_next, &h3));
@@ -703,7 +624,7 @@ template <typename T> static int minres_step_impl(mik_minres *it, int64_t iterat
         hipLaunchKernelGGL((k_minres_scalars<T>), dim3(1), dim3(1), 0, ctx->stream, d, h3, (long long)iteration, it->skew, it->mirror, it->seq);
         MIK_LAUNCH_CHECK(ctx);
         MIK_TRY(tail());
-        MIK_TRY(minres_wait<T>(it));
+        MIK_TRY(mik_wait_seq(ctx, &it->mirror->seq, it->seq, "minres", "iteration", "an iteration"));
     }
     *resnorm = (T)it->mirror->resnorm;
     void *t = it->v[0]; it->v[0] = it->v[1]; it->v[1] = it->v[2]; it->v[2] = t;              // :145
