@@ -787,6 +787,23 @@ int mik_dense_mul(mik_dense *D, int adjoint, const void *x, void *y);
  * calls mik_cg_create_op / mik_gmres_create_op -- the whole solve then runs inside the library, no host-language frame per product. */
 int mik_dense_mul_fn(void *user, const void *x, void *y);         /* y = A x  -- src/cg.jl:54,137; src/gmres.jl:245,287 */
 int mik_dense_mul_adj_fn(void *user, const void *x, void *y);     /* y = A' x -- src/lsqr.jl:132,172; src/lsmr.jl:118,172; src/qmr.jl:76; src/svdl.jl:565 */
+/* Block product: Y[:, j] = A * X[:, j] for j < b -- mul!(AX, A, X) of src/lobpcg.jl:124-139 for A::Matrix.  X: DEVICE n x b, column-major,
+ * ldx >= n; Y: DEVICE m x b, column-major, ldy >= m.  Column j of Y equals mik_dense_mul(D, 0, X[:, j], Y[:, j]) bit for bit: the chunked
+ * order above, no FMA, no matrix cores, no atomics; the result depends on (m, n, dtype, C) only -- never on b, the group width, ldx / ldy,
+ * alignment or the launch shape.  n = 0 gives +0 in every column.  The b columns run in groups of mik_dense_block_shape() columns, one
+ * after another on the stream: A is read once per group, every loaded element multiplied into the accumulators of all columns of the group;
+ * the chunk partials of ONE group go to the handle's block workspace, laid out [column of the group][chunk][m rounded up to whole
+ * workgroups], and one combine launch per group sums them in chunk order.  With n <= C the product kernel writes Y itself.  A last group
+ * narrower than the library's threshold runs column by column through the kernels of mik_dense_mul.
+ * MIK_ERR_INVALID for b < 0, a NULL block with a non-empty extent, Y overlapping X or A; MIK_ERR_NOTIMPL for b > 32; MIK_ERR_MISMATCH for
+ * ldx < n or ldy < m; b = 0 or m = 0 is MIK_OK and launches nothing.  Asynchronous on the ctx stream; no workgroup waits for another. */
+int mik_dense_mm(mik_dense *D, int b, const void *X, int64_t ldx, void *Y, int64_t ldy);
+/* Allocate the block workspace of mik_dense_mm (group width x chunks x padded rows elements; nothing when n <= C).  Idempotent.
+ * mik_dense_mm calls it on first use; a host calls it when it builds an iterator, so that nothing is allocated inside an iteration loop.
+ * A second allocation: it never replaces or frees the workspace of mik_dense_mul.  mik_dense_destroy frees it. */
+int mik_dense_block_reserve(mik_dense *D);
+/* The group width: the right-hand sides that share one read of A. */
+int mik_dense_block_shape(int *group_width);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Time `reps` back-to-back launches of the SpMV (optionally with the fused dot epilogue used by

@@ -64,6 +64,17 @@ int mik_dev_gmres_form(const mik_gmres *it, int *single_launch, int *segments_pe
  * (an empty dimension).  Nothing is launched or read on the device.  Any out pointer may be NULL. */
 int mik_dev_dense_plan(const mik_dense *D, int adjoint, const void *x, const void *y, int *vec, int *streamed, int64_t *grid_x, int64_t *grid_y,
                        int64_t *chunks_or_batches, int64_t *segments);
+/* The launch plan mik_dense_mm(D, b, X, ldx, Y, ldy) takes (computed by the helper the launch runs): *groups = launches of the block kernel,
+ * *last_width = columns of the last of them, *vector_cols = trailing columns that run one by one through the kernels of mik_dense_mul (a last group
+ * narrower than the threshold); *vec / *streamed / grid / *chunks describe the block kernel -- 16-byte loads need an aligned matrix and leading
+ * dimension and, when n <= C (the product kernel stores into Y itself), Y and ldy aligned too; X never matters -- or, with *groups = 0, the vector
+ * call of column 0.  *workspace_bytes = the block workspace the handle holds now (0 before mik_dense_block_reserve, or when n <= C).  All zero
+ * for an empty dimension or b <= 0.  Nothing is launched or read on the device.  Any out pointer may be NULL. */
+int mik_dev_dense_block_plan(const mik_dense *D, int b, const void *X, int64_t ldx, const void *Y, int64_t ldy, int *vec, int *streamed,
+                             int64_t *grid_x, int64_t *grid_y, int64_t *chunks, int *groups, int *last_width, int *vector_cols, int64_t *workspace_bytes);
+/* The narrowest last group this handle gives to the block kernel: 1 .. group width; 0 = the library's threshold.  For measurements and for
+ * tests that want the block kernel at every width; results never depend on it. */
+int mik_dev_dense_block_min_width(mik_dense *D, int width);
 /* Shape of the resident-w Modified Gram-Schmidt kernel (csrc/mik_mgs_res.h): threads per workgroup (threads / 256 segments per round), rounds of a
  * workgroup's segments kept in registers and in LDS; the rest of w is streamed in every pass.  For byte accounting (bench.py). */
 int mik_dev_mgs_resident_shape(int *threads, int *register_rounds, int *lds_rounds);

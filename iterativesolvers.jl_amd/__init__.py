@@ -10,7 +10,7 @@ The directory name (``iterativesolvers.jl_amd``) is not a Python identifier; loa
   stationary.py  jacobi / gauss_seidel / sor / ssor and their iterables on a HipCSR (src/stationary_sparse.jl)
   stationary_dense.py  the same four on a dense HipMatrix (src/stationary.jl), and the public names that dispatch between the two
   svdl.py    svdl: Golub-Kahan-Lanczos SVD with thick restart (src/svdl.jl) on a HipCSR uploaded with its adjoint, or on a HipMatrix
-  lobpcg.py  lobpcg: block eigensolver (src/lobpcg.jl) on HipCSR operators, every sweep on a block of columns
+  lobpcg.py  lobpcg: block eigensolver (src/lobpcg.jl) on HipCSR operators, with dense=True also on dense HipMatrix ones, every sweep on a block of columns
   extras.py  solvers outside the scope contract (IDR(s), LSQR, LSMR, QMR, power method); kept apart, unjudged
   dist.py    row-partitioned multi-GPU CG / GMRES (one process per GPU; RCCL, peer-mapped mailboxes, in-process group)
   bench_dist.py  measurement harness of bench.py --gpus N (self-test orchestration, group fall-back, the line) -- not product code

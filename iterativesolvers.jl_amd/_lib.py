@@ -83,6 +83,8 @@ SIGNATURES = {
     "mik_ctx_info": (C.c_int, [_vp, C.POINTER(MikDeviceInfo)]),
     "mik_dev_gmres_form": (C.c_int, [_vp, _ip, _ip, _ip, _ip]),
     "mik_dev_dense_plan": (C.c_int, [_vp, C.c_int, _vp, _vp, _ip, _ip, _i64p, _i64p, _i64p, _i64p]),
+    "mik_dev_dense_block_plan": (C.c_int, [_vp, C.c_int, _vp, _i64, _vp, _i64, _ip, _ip, _i64p, _i64p, _i64p, _ip, _ip, _ip, _i64p]),
+    "mik_dev_dense_block_min_width": (C.c_int, [_vp, C.c_int]),
     "mik_dev_mgs_resident_shape": (C.c_int, [_ip, _ip, _ip]),
     "mik_ctx_set_stream": (C.c_int, [_vp, _vp]),
     "mik_ctx_synchronize": (C.c_int, [_vp]),
@@ -225,6 +227,9 @@ SIGNATURES = {
     "mik_dense_create": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _i64, C.POINTER(_vp)]),
     "mik_dense_destroy": (C.c_int, [_vp]),
     "mik_dense_mul": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "mik_dense_mm": (C.c_int, [_vp, C.c_int, _vp, _i64, _vp, _i64]),
+    "mik_dense_block_reserve": (C.c_int, [_vp]),
+    "mik_dense_block_shape": (C.c_int, [_ip]),
     "mik_dense_mul_fn": (C.c_int, [_vp, _vp, _vp]),
     "mik_dense_mul_adj_fn": (C.c_int, [_vp, _vp, _vp]),
     "mik_basis_rotate": (C.c_int, [_vp, C.c_int, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _i64, _vp, _i64]),

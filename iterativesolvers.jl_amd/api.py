@@ -331,6 +331,21 @@ class HipMatrix:
     def __matmul__(self, x: HipVector) -> HipVector:                     # A * v
         return mul_(HipVector(self.n, self.dtype, self.ctx), self, x)
 
+    def mm_(self, Y: "HipMatrix", X: "HipMatrix", b: Optional[int] = None) -> "HipMatrix":
+        """``mul!(Y[:, 1:b], A, X[:, 1:b])`` (src/lobpcg.jl:124-139 for ``A::Matrix``): every column has the bits of ``mul_`` on that
+        column; the matrix is read once per group of columns (``mik_dense_mm``).  ``b`` defaults to the columns of ``X``; at most 32."""
+        b = X.cols if b is None else int(b)
+        if (X.n, Y.n) != (self.cols, self.n) or not 0 <= b <= min(X.cols, Y.cols) or not X.dtype == Y.dtype == self.dtype:
+            raise ValueError(f"DimensionMismatch: mul!(Y, A, X) with A {self.n} x {self.cols}, X {X.n} x {X.cols}, Y {Y.n} x {Y.cols}, b = {b}")
+        check(lib().mik_dense_mm(self.dense, b, _vp(X.buf.ptr), X.ld, _vp(Y.buf.ptr), Y.ld), "mik_dense_mm", self.ctx.handle)
+        return Y
+
+    def reserve_block_(self) -> "HipMatrix":
+        """Allocate the workspace of ``mm_`` now (``mik_dense_block_reserve``): an iterator calls it when it is built, so that its loop allocates
+        nothing."""
+        check(lib().mik_dense_block_reserve(self.dense), "mik_dense_block_reserve", self.ctx.handle)
+        return self
+
     def __del__(self):
         try:
             if self.__dict__.get("_dense") and self.ctx.handle:

@@ -3,7 +3,7 @@
 // per product.
 //
 // The handle owns its workspace -- the chunk partials of the N form and the segment sums of the T form share one allocation made in
-// create -- and never touches ctx->partials / ctx->coef: the callback runs in the middle of a fused CG / GMRES step that may hold
+// create; the partials of the block product Y = A X live in a second allocation made by mik_dense_block_reserve -- and never touches ctx->partials / ctx->coef: the callback runs in the middle of a fused CG / GMRES step that may hold
 // state there.  Nothing is allocated per call; every call is asynchronous on the ctx stream; no workgroup waits for another.
 #include "mik_internal.h"
 #include "mik_dense_mul.h"
@@ -17,6 +17,10 @@ struct mik_dense {
     const void *A = nullptr;
     void *work = nullptr;            // N: [chunks][m_pad] partials;  T: [n][segments of m] segment sums
     int64_t m_pad = 0;               // m rounded up to whole workgroups of the N form (keeps every partial column 16-byte aligned)
+    void *bwork = nullptr;           // block form: [right-hand side of the group][chunk][m_pad] partials of ONE group; never shared with `work`
+    size_t bwork_bytes = 0;
+    bool breserved = false;          // mik_dense_block_reserve has run (one chunk needs no workspace: bwork stays null)
+    int bmin = 0;                    // development override of MIK_DM_GW_MIN (mik_dev_dense_block_min_width); 0 = the default
 };
 
 namespace {
@@ -89,8 +93,103 @@ int dm_mul_n(mik_dense *D, const T *x, T *y)
     else hipLaunchKernelGGL((k_dense_n<T, false, false, MIK_DM_C>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const T *)D->A, D->lda, x, out, D->m_pad);
     MIK_LAUNCH_CHECK(ctx);
     if (nc > 1) {
-        hipLaunchKernelGGL((k_dense_n_combine<T, MIK_DM_PF>), dim3((unsigned)((m + MIK_DM_CB - 1) / MIK_DM_CB)), dim3(MIK_DM_CB), 0, ctx->stream, m, nc, (const T *)out, D->m_pad, y);
+        hipLaunchKernelGGL((k_dense_n_combine<T, MIK_DM_PF>), dim3((unsigned)((m + MIK_DM_CB - 1) / MIK_DM_CB)), dim3(MIK_DM_CB), 0, ctx->stream, m, nc, (const T *)out, D->m_pad, y, (int64_t)0, (int64_t)0);
         MIK_LAUNCH_CHECK(ctx);
+    }
+    return MIK_OK;
+}
+
+// ---- block form: Y[:, j] = A X[:, j], j < b ---------------------------------------------------------------------------------------------
+// b right-hand sides run as groups of MIK_DM_GW, one after another on the stream (which makes the reuse of the one-group workspace safe): A is
+// read once per group.  A last group narrower than MIK_DM_GW_MIN runs column by column through dm_mul_n instead -- the bits are the same by
+// construction (dm_rows is the one body of both kernels), the choice is one of time alone.
+constexpr int MIK_DM_GW_MIN = 2;
+
+struct dm_bplan {
+    int vec = 0, streamed = 0, groups = 0, last_w = 0, vector_cols = 0;     // groups: launches of the block kernel; vector_cols: columns left to dm_mul_n
+    int64_t gx = 0, gy = 0, chunks = 0;
+};
+
+template <typename T>
+dm_bplan dm_plan_nb(const mik_dense *D, int b, const T *X, int64_t ldx, const T *Y, int64_t ldy)
+{
+    dm_bplan p;
+    const int64_t m = D->m, n = D->n;
+    if (m == 0 || n == 0 || b <= 0) return p;
+    const int wmin = D->bmin > 0 ? D->bmin : MIK_DM_GW_MIN;
+    const int last = b % MIK_DM_GW ? b % MIK_DM_GW : MIK_DM_GW;
+    p.groups = (b + MIK_DM_GW - 1) / MIK_DM_GW;
+    p.last_w = last;
+    if (last < wmin) { p.vector_cols = last; p.groups -= 1; p.last_w = p.groups ? MIK_DM_GW : 0; }
+    if (p.groups == 0) {                                       // every column goes through the vector kernels: their plan, for column 0
+        const dm_plan v = dm_plan_n<T>(D, X, Y);
+        p.vec = v.vec; p.streamed = v.streamed; p.gx = v.gx; p.gy = v.gy; p.chunks = v.cols;
+        return p;
+    }
+    p.chunks = dm_chunks(n);
+    // one chunk: the product kernel stores into Y itself, so every column of Y has to start on a 16-byte boundary for the 16-byte variant
+    const bool out16 = p.chunks == 1 ? (mik_aligned16(Y) && ldy % VT<T>::W == 0) : true;
+    p.vec = mik_aligned16(D->A) && D->lda % VT<T>::W == 0 && out16;
+    p.streamed = dm_streamed<T>(m, n);
+    p.gx = (m + MIK_DM_R - 1) / MIK_DM_R;                       // the grid of the vector form
+    p.gy = std::min<int64_t>(p.chunks, std::max<int64_t>(1, std::min<int64_t>(65535, 4 * (int64_t)mik_cus(D->ctx) / p.gx)));
+    return p;
+}
+
+int dm_block_reserve(mik_dense *D)
+{
+    if (D->breserved) return MIK_OK;
+    const int64_t nc = dm_chunks(D->n);
+    if (nc > 1 && D->m > 0) {
+        const size_t bytes = mik_dtype_size(D->dtype) * (size_t)MIK_DM_GW * (size_t)nc * (size_t)D->m_pad;
+        (void)hipSetDevice(D->ctx->device);
+        const hipError_t e = hipMalloc(&D->bwork, bytes);
+        if (e != hipSuccess) {
+            D->bwork = nullptr;
+            return mik_fail(D->ctx, e == hipErrorOutOfMemory ? MIK_ERR_NOMEM : MIK_ERR_HIP, "mik_dense_block_reserve: hipMalloc of %zu bytes failed: %s", bytes,
+                            hipGetErrorString(e));
+        }
+        D->bwork_bytes = bytes;
+    }
+    D->breserved = true;
+    return MIK_OK;
+}
+
+template <typename T>
+int dm_mm(mik_dense *D, int b, const T *X, int64_t ldx, T *Y, int64_t ldy)
+{
+    mik_ctx *ctx = D->ctx;
+    const int64_t m = D->m, n = D->n;
+    if (n == 0) {                                             // the empty sum: +0 in every column
+        MIK_HIP(ctx, hipMemset2DAsync(Y, sizeof(T) * (size_t)ldy, 0, sizeof(T) * (size_t)m, (size_t)b, ctx->stream));
+        return MIK_OK;
+    }
+    const dm_bplan p = dm_plan_nb<T>(D, b, X, ldx, Y, ldy);
+    const int64_t nc = p.chunks;
+    if (p.groups > 0 && nc > 1) {
+        const int rc = dm_block_reserve(D);
+        if (rc != MIK_OK) return rc;
+    }
+    const dim3 grid((unsigned)p.gx, (unsigned)p.gy);
+    const dim3 cgrid((unsigned)((m + MIK_DM_CB - 1) / MIK_DM_CB));
+    for (int g = 0; g < p.groups; ++g) {
+        const int w = g + 1 < p.groups ? MIK_DM_GW : p.last_w;
+        const T *Xg = X + (int64_t)g * MIK_DM_GW * ldx;
+        T *Yg = Y + (int64_t)g * MIK_DM_GW * ldy;
+        T *out = nc == 1 ? Yg : (T *)D->bwork;
+        const int64_t col_stride = nc == 1 ? ldy : nc * D->m_pad;
+        if (p.vec && p.streamed) hipLaunchKernelGGL((k_dense_nb<T, true, true, MIK_DM_C, MIK_DM_GW>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const T *)D->A, D->lda, Xg, ldx, w, out, col_stride, D->m_pad);
+        else if (p.vec) hipLaunchKernelGGL((k_dense_nb<T, true, false, MIK_DM_C, MIK_DM_GW>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const T *)D->A, D->lda, Xg, ldx, w, out, col_stride, D->m_pad);
+        else hipLaunchKernelGGL((k_dense_nb<T, false, false, MIK_DM_C, MIK_DM_GW>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const T *)D->A, D->lda, Xg, ldx, w, out, col_stride, D->m_pad);
+        MIK_LAUNCH_CHECK(ctx);
+        if (nc > 1) {
+            hipLaunchKernelGGL((k_dense_n_combine<T, MIK_DM_PF>), dim3(cgrid.x, (unsigned)w), dim3(MIK_DM_CB), 0, ctx->stream, m, nc, (const T *)out, D->m_pad, Yg, col_stride, ldy);
+            MIK_LAUNCH_CHECK(ctx);
+        }
+    }
+    for (int j = b - p.vector_cols; j < b; ++j) {
+        const int rc = dm_mul_n<T>(D, X + (int64_t)j * ldx, Y + (int64_t)j * ldy);
+        if (rc != MIK_OK) return rc;
     }
     return MIK_OK;
 }
@@ -162,6 +261,7 @@ extern "C" int mik_dense_destroy(mik_dense *D)
     if (!D) return MIK_OK;
     if (D->ctx) { (void)hipSetDevice(D->ctx->device); (void)hipStreamSynchronize(D->ctx->stream); }
     if (D->work) (void)hipFree(D->work);
+    if (D->bwork) (void)hipFree(D->bwork);
     delete D;
     return MIK_OK;
 }
@@ -178,6 +278,62 @@ extern "C" int mik_dense_mul(mik_dense *D, int adjoint, const void *x, void *y)
     if (D->dtype == MIK_F64)
         return adjoint ? dm_mul_t<double>(D, (const double *)x, (double *)y) : dm_mul_n<double>(D, (const double *)x, (double *)y);
     return adjoint ? dm_mul_t<float>(D, (const float *)x, (float *)y) : dm_mul_n<float>(D, (const float *)x, (float *)y);
+}
+
+extern "C" int mik_dense_block_shape(int *group_width)
+{
+    if (group_width) *group_width = MIK_DM_GW;
+    return MIK_OK;
+}
+
+extern "C" int mik_dense_block_reserve(mik_dense *D)
+{
+    if (!D) return MIK_ERR_INVALID;
+    return dm_block_reserve(D);
+}
+
+extern "C" int mik_dense_mm(mik_dense *D, int b, const void *X, int64_t ldx, void *Y, int64_t ldy)
+{
+    if (!D || b < 0) return MIK_ERR_INVALID;
+    if (b > MIK_DM_BMAX) return mik_fail(D->ctx, MIK_ERR_NOTIMPL, "mik_dense_mm: b = %d (at most %d columns)", b, MIK_DM_BMAX);
+    if (b == 0) return MIK_OK;
+    if (ldx < D->n || ldy < D->m)
+        return mik_fail(D->ctx, MIK_ERR_MISMATCH, "mik_dense_mm: ldx = %lld < n = %lld or ldy = %lld < m = %lld", (long long)ldx, (long long)D->n, (long long)ldy, (long long)D->m);
+    if (D->m == 0) return MIK_OK;
+    if ((D->n && !X) || !Y) return MIK_ERR_INVALID;
+    const size_t es = mik_dtype_size(D->dtype);
+    const size_t xbytes = mik_block_bytes(es, D->n, b, ldx), ybytes = mik_block_bytes(es, D->m, b, ldy);
+    if (mik_overlap(X, xbytes, Y, ybytes)) return mik_fail(D->ctx, MIK_ERR_INVALID, "mik_dense_mm: Y overlaps X");
+    const size_t abytes = D->n > 0 ? es * ((size_t)(D->n - 1) * (size_t)D->lda + (size_t)D->m) : 0;
+    if (mik_overlap(Y, ybytes, D->A, abytes)) return mik_fail(D->ctx, MIK_ERR_INVALID, "mik_dense_mm: Y overlaps A");
+    if (D->dtype == MIK_F64) return dm_mm<double>(D, b, (const double *)X, ldx, (double *)Y, ldy);
+    return dm_mm<float>(D, b, (const float *)X, ldx, (float *)Y, ldy);
+}
+
+extern "C" int mik_dev_dense_block_plan(const mik_dense *D, int b, const void *X, int64_t ldx, const void *Y, int64_t ldy, int *vec, int *streamed,
+                                        int64_t *grid_x, int64_t *grid_y, int64_t *chunks, int *groups, int *last_width, int *vector_cols,
+                                        int64_t *workspace_bytes)
+{
+    if (!D) return MIK_ERR_INVALID;
+    const dm_bplan p = D->dtype == MIK_F64 ? dm_plan_nb<double>(D, b, (const double *)X, ldx, (const double *)Y, ldy)
+                                           : dm_plan_nb<float>(D, b, (const float *)X, ldx, (const float *)Y, ldy);
+    if (vec) *vec = p.vec;
+    if (streamed) *streamed = p.streamed;
+    if (grid_x) *grid_x = p.gx;
+    if (grid_y) *grid_y = p.gy;
+    if (chunks) *chunks = p.chunks;
+    if (groups) *groups = p.groups;
+    if (last_width) *last_width = p.last_w;
+    if (vector_cols) *vector_cols = p.vector_cols;
+    if (workspace_bytes) *workspace_bytes = (int64_t)D->bwork_bytes;
+    return MIK_OK;
+}
+
+extern "C" int mik_dev_dense_block_min_width(mik_dense *D, int width)
+{
+    if (!D || width < 0 || width > MIK_DM_GW) return MIK_ERR_INVALID;
+    D->bmin = width;
+    return MIK_OK;
 }
 
 extern "C" int mik_dev_dense_plan(const mik_dense *D, int adjoint, const void *x, const void *y, int *vec, int *streamed, int64_t *grid_x,

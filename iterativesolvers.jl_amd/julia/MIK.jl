@@ -1315,6 +1315,13 @@ function dense_mul!(y::HipVector{T}, A::HipDenseMatrix{T}, adj::Bool, x::HipVect
           "mik_dense_mul", A.ctx.handle)
     y
 end
+"Y[:, 1:b] = A * X[:, 1:b] (mik_dense_mm): every column has the bits of dense_mul! on that column; A is read once per group of columns"
+function dense_mm!(Y::HipDenseMatrix{T}, A::HipDenseMatrix{T}, X::HipDenseMatrix{T}, b::Integer = X.cols) where {T}
+    (X.n == A.cols && Y.n == A.n && 0 <= b <= min(X.cols, Y.cols)) || throw(DimensionMismatch("mul!(Y, A, X)"))
+    check(ccall((:mik_dense_mm, libmik), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64), dense_operator(A).handle, b, X.ptr, X.ld, Y.ptr, Y.ld),
+          "mik_dense_mm", A.ctx.handle)
+    Y
+end
 function LinearAlgebra.mul!(y::HipVector{T}, A::HipDenseMatrix{T}, x::HipVector{T}) where {T}
     dense_mul!(y, A, false, x)
 end

@@ -1,20 +1,23 @@
 """``lobpcg`` -- the Locally Optimal Block Preconditioned Conjugate Gradient method for the extreme eigenpairs of ``A x = lambda B x`` on
-device CSR operators (src/lobpcg.jl, v0.9.4), restated function by function; Julia's ``f!`` is spelled ``f_``.  Citations are file:line in
+device operators, sparse (``HipCSR``) or dense (``HipMatrix``) (src/lobpcg.jl, v0.9.4), restated function by function; Julia's ``f!`` is spelled ``f_``.  Citations are file:line in
 the reference checkout.
 
 What runs where
-  device   everything of length n, a block of columns at a time: ``A*X`` / ``B*X`` (``mik_spmm``), every cross product ``X'Y`` of the block
+  device   everything of length n, a block of columns at a time: ``A*X`` / ``B*X`` (``mik_spmm`` for a ``HipCSR``, ``mik_dense_mm`` for a
+           ``HipMatrix``), every cross product ``X'Y`` of the block
            Gram matrices, of CholQR and of the constraint (``mik_block_gram``), ``X * inv(R)`` of CholQR (``mik_block_rdiv``), the Ritz update
            of X, AX, BX and P, AP, BP (``mik_block_update``); column by column the residuals with their norms (``mik_copy`` +
            ``mik_axpy_dot``), the gather of the active columns (``mik_copy``), ``X -= Y*tmp`` of the constraint (``mik_gemv_n``) and the
            preconditioner (``mik_divide`` for ``JacobiPrec``, else ``ldiv_`` per column);
   host     in numpy, in the element type: the Cholesky factorisations, the triangular solves of the constraint, and the Rayleigh-Ritz
            problem of at most 96 x 96 (``eigh``; the generalised problem reduced by the Cholesky factor of ``gramB``; a stable argsort).
-Every block is allocated when the iterator is built; the update writes into a spare X triple that is then swapped in.  Nothing is allocated
+Every block, and the block workspace of a dense operator, is allocated when the iterator is built; the update writes into a spare X triple that is then swapped in.  Nothing is allocated
 on the device inside the iteration loop.
 
 Differences from the reference, all deliberate:
-  * ``A`` and ``B`` are ``HipCSR``; real float32 / float64; a block is at most 32 columns wide (the width of the device entries);
+  * ``A`` and ``B`` are ``HipCSR``, or -- with ``dense=True`` -- each a ``HipCSR`` or a square ``HipMatrix`` (the two may differ).  Without the
+    keyword a ``HipMatrix`` is refused as it always was: that refusal is behaviour callers and the suite rely on, so the dense route is asked for;
+    real float32 / float64; a block is at most 32 columns wide (the width of the device entries);
   * where the reference calls ``rand`` the functions take ``rng=`` (a ``numpy.random.Generator``), so that runs repeat;
   * ``results.X`` stays on the device (a ``HipMatrix``); ``X0`` and ``C`` are ``HipMatrix`` or numpy arrays and are copied;
   * a Cholesky factorisation that fails (a block that lost rank, a ``B`` that is not positive definite) raises ``LobpcgCholeskyError``,
@@ -37,7 +40,7 @@ from ._lib import MikError, check, dtype_code, lib
 from .api import HipCSR, HipMatrix, Identity, JacobiPrec
 
 _vp = C.c_void_p
-MAX_BLOCK = 32                                                           # widest block of mik_spmm / mik_block_gram / mik_block_rdiv / mik_block_update
+MAX_BLOCK = 32                                                           # widest block of mik_spmm / mik_dense_mm / mik_block_gram / mik_block_rdiv / mik_block_update
 
 
 class LobpcgRefusal(ValueError):
@@ -103,14 +106,21 @@ def _append(ops, r1, r2, n1, n2=None):
 class DeviceOps:
     """Every statement of length n, on the device.  (tests/lobpcg_double.py implements the same methods in numpy.)"""
 
-    def __init__(self, A, B=None):
+    def __init__(self, A, B=None, dense=False):
         for M, name in ((A, "A"), (B, "B")):
-            if not isinstance(M, HipCSR) and not (M is None and name == "B"):
-                raise TypeError(f"lobpcg needs HipCSR operators ({name} is {type(M).__name__}; callbacks are not supported)")
-        if A.n_rows != A.n_cols or (B is not None and (B.n_rows, B.n_cols, B.dtype) != (A.n_rows, A.n_cols, A.dtype)):
+            if M is None and name == "B":
+                continue
+            if isinstance(M, HipMatrix) and not dense:
+                raise TypeError(f"lobpcg needs HipCSR operators ({name} is a HipMatrix: pass dense=True to run it through mik_dense_mm)")
+            if not isinstance(M, (HipCSR, HipMatrix)):
+                raise TypeError(f"lobpcg needs HipCSR operators, or HipMatrix ones with dense=True ({name} is {type(M).__name__}; callbacks are not supported)")
+        if A.n_rows != A.n_cols or (B is not None and (B.n_rows, B.n_cols, np.dtype(B.dtype)) != (A.n_rows, A.n_cols, np.dtype(A.dtype))):
             raise ValueError("DimensionMismatch: lobpcg needs square A and B of one size and element type")
         self.ctx, self.dtype, self.n = A.ctx, np.dtype(A.dtype), A.n_rows
         self.code = dtype_code(self.dtype)
+        for M in (A, B):
+            if isinstance(M, HipMatrix):
+                M.reserve_block_()                                       # the partials of mik_dense_mm: allocated here, not in the loop
 
     # -- storage ----------------------------------------------------------------------------------
     def matrix(self, rows, cols):
@@ -133,6 +143,9 @@ class DeviceOps:
 
     # -- the four block entries -------------------------------------------------------------------
     def spmm(self, A, X, b, Y):                                          # mul!(Y[:, 1:b], A, X[:, 1:b]), :124-139
+        if isinstance(A, HipMatrix):
+            A.mm_(Y, X, b)
+            return
         check(lib().mik_spmm(self.ctx.handle, A.handle, int(b), _vp(X.buf.ptr), X.ld, _vp(Y.buf.ptr), Y.ld), "mik_spmm", self.ctx.handle)
 
     def gram(self, X, p, Y, q, x0=0, y0=0):                              # X[:, x0:x0+p]' * Y[:, y0:y0+q] -> host
@@ -303,8 +316,8 @@ class LOBPCGIterator:
     """``LOBPCGIterator(A, [B,] largest, X, [nev,] P, C)`` (:435-522).  ``X``: the initial Ritz vectors (``HipMatrix`` or numpy, copied).
     With ``nev`` the constraint gets room for the pairs the multi-batch driver deflates (:497-522)."""
 
-    def __init__(self, A, B, largest, X, nev=None, P=None, C=None, ops=None):
-        ops = self.ops = ops if ops is not None else DeviceOps(A, B)
+    def __init__(self, A, B, largest, X, nev=None, P=None, C=None, ops=None, dense=False):
+        ops = self.ops = ops if ops is not None else DeviceOps(A, B, dense)
         self.A, self.B, self.largest, self.P = A, B, bool(largest), P
         Xh = np.asarray(_host(X), ops.dtype)
         if Xh.ndim != 2 or Xh.shape[0] != ops.n:
@@ -496,15 +509,16 @@ def _split_args(args):
     raise TypeError("lobpcg(A, [B,] largest::Bool, nev | X0 [, nev]; ...)")
 
 
-def lobpcg(A, *args, not_zeros=False, log=False, P=None, maxiter=200, C=None, tol=None, rng=None, ops=None):
+def lobpcg(A, *args, not_zeros=False, log=False, P=None, maxiter=200, C=None, tol=None, rng=None, ops=None, dense=False):
     """``lobpcg(A, [B,] largest, nev | X0 [, nev]; not_zeros, log, P, C, maxiter, tol)`` -> ``LOBPCGResults`` (:787-839, :925-962).
 
     ``largest``: True for the largest eigenvalues, False for the smallest.  ``nev`` alone: that many pairs from a random start.  ``X0``: the
     initial block, its width the number of pairs -- or, followed by ``nev``, the width of the batches in which ``nev`` pairs are found, each
     batch deflated against the ones before it.  ``P``: ``JacobiPrec``, ``Identity`` or an object with ``ldiv_(y, x)``; ``C``: a block the
-    result is kept B-orthogonal to; ``rng``: the generator behind every random column; ``ops``: the device side (tests swap it)."""
+    result is kept B-orthogonal to; ``rng``: the generator behind every random column; ``ops``: the device side (tests swap it); ``dense=True``: ``A`` and ``B`` may be square
+    ``HipMatrix`` operators (``mik_dense_mm``), refused otherwise."""
     B, largest, rest = _split_args(args)
-    ops = ops if ops is not None else DeviceOps(A, B)
+    ops = ops if ops is not None else DeviceOps(A, B, dense)
     n = ops.n
     tol = default_tolerance(ops.dtype) if tol is None else tol
     rng = np.random.default_rng() if rng is None else rng

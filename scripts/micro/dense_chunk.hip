@@ -29,8 +29,8 @@ static void product(int part, int64_t n, const T *A, const T *x, T *work, T *y, 
     }
     if (nc == 1) return;
     const dim3 cg((unsigned)((n + MIK_DM_CB - 1) / MIK_DM_CB));
-    if (part == WHOLE || part == COMBINE32 || part == UNCAPPED) hipLaunchKernelGGL((k_dense_n_combine<T, 32>), cg, dim3(MIK_DM_CB), 0, s, n, nc, (const T *)out, m_pad, y);
-    if (part == COMBINE8) hipLaunchKernelGGL((k_dense_n_combine<T, 8>), cg, dim3(MIK_DM_CB), 0, s, n, nc, (const T *)out, m_pad, y);
+    if (part == WHOLE || part == COMBINE32 || part == UNCAPPED) hipLaunchKernelGGL((k_dense_n_combine<T, 32>), cg, dim3(MIK_DM_CB), 0, s, n, nc, (const T *)out, m_pad, y, (int64_t)0, (int64_t)0);
+    if (part == COMBINE8) hipLaunchKernelGGL((k_dense_n_combine<T, 8>), cg, dim3(MIK_DM_CB), 0, s, n, nc, (const T *)out, m_pad, y, (int64_t)0, (int64_t)0);
 }
 
 template <typename T>
