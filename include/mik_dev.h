@@ -78,6 +78,17 @@ int mik_dev_dense_block_min_width(mik_dense *D, int width);
 /* Shape of the resident-w Modified Gram-Schmidt kernel (csrc/mik_mgs_res.h): threads per workgroup (threads / 256 segments per round), rounds of a
  * workgroup's segments kept in registers and in LDS; the rest of w is streamed in every pass.  For byte accounting (bench.py). */
 int mik_dev_mgs_resident_shape(int *threads, int *register_rounds, int *lds_rounds);
+/* The launch plan of y = A x for these arguments on the operator's context as it is now (csrc/mik_core.hip: the plan the launcher itself computes and
+ * executes; mik_spmv_kernel is this query for a whole launch with an aligned x and no fused dot).  skip_begin < 0: the request is row-blocks
+ * [rb_begin, rb_begin + rb_count) (rb_count < 0: all), as the solvers and the interior sweep of the row-partitioned CG ask for; else it is every
+ * row-block OUTSIDE [skip_begin, skip_end), the boundary sweep of that CG (rb_begin / rb_count are not read), which is one launch where the kernel leaves
+ * a range out itself and two ranges elsewhere.  x only matters through its 16-byte alignment; fuse_dot: the dot(x, y) segment sums are asked for.
+ * kernel_name (len bytes): the name mik_spmv_kernel uses, *grid = its workgroups, *pre_longrows = 1 when k_spmv_longrows goes first, *post_rowdot = 1
+ * when k_rowdot follows -- all of the first launching range of the request -- and *launches = kernel launches of the whole request (0: nothing to do).
+ * Returns the launcher's refusal (code, and the same text as the context's error) where the launcher would refuse.  Nothing is launched or read on the
+ * device.  Any out pointer may be NULL. */
+int mik_dev_spmv_plan(const mik_csr *A, const void *x, int fuse_dot, int rb_begin, int rb_count, int skip_begin, int skip_end, char *kernel_name, int len,
+                      int64_t *grid, int *launches, int *pre_longrows, int *post_rowdot);
 /* Host-only: the rule that places a 256-row block's window of x in LDS (k_spmv_rowblock XWIN) on caller-supplied per-block statistics
  * (first / last referenced column, entry count).  win_lo[b] = first column of block b's window (16-byte aligned) or -1 (the block gathers from
  * memory); *span = common window length in elements, 0 = no window table.  Guarantee the tests check: win_lo[b] >= 0 implies

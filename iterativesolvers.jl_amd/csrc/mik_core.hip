@@ -218,8 +218,6 @@ extern "C" int mik_spmv_long_group(int *group)
     return MIK_OK;
 }
 
-static inline bool spmv_csr_rowgather(const mik_csr *A);
-
 extern "C" int mik_ctx_set_tuning(mik_ctx *ctx, int key, int value)
 {
     if (!ctx || key < 0 || key >= MIK_KNOB_COUNT) return MIK_ERR_INVALID;
@@ -1279,7 +1277,61 @@ extern "C" int mik_csr_destroy(mik_csr *A)
     return MIK_OK;
 }
 
-static int spmv_kernel_choice(const mik_csr *A);
+// ---------------------------------------------------------------------------------------------
+// SpMV: the layout an operator runs on, and the predicates that pick its kernel -- each spelled here and nowhere else
+// ---------------------------------------------------------------------------------------------
+// The numbers are ABI: mik_csr_layout reports them and HipCSR.LAYOUTS (api.py) indexes by them (2 and 3 are retired).
+enum SpmvLayout : int {
+    LAYOUT_CSR = 0,     // the CSR arrays (k_spmv_rowgather / k_spmv_rowblock)
+    LAYOUT_JDS = 1,     // jagged slices (k_spmv_jds)
+    LAYOUT_SDIA = 4,    // sliced-ELL values + per-slice offsets (k_spmv_sdia)
+    LAYOUT_SDIAC = 5,   // per-slice offsets + slice-constant values (k_spmv_sdiab2 / k_spmv_sdiab / k_spmv_sdiac)
+    LAYOUT_SDIAW = 6,   // ... with up to 32 offsets per slice (k_spmv_sdiaw2 / k_spmv_sdiaw)
+};
+
+// Which layout the launcher runs this operator on under the current development knobs: read by the launch plan (spmv_plan: the
+// launcher and every query about it), by mik_csr_layout and by mik_csr_stored_bytes.
+static SpmvLayout spmv_kernel_choice(const mik_csr *A)
+{
+    const bool csr = A->col != nullptr;                     // false after mik_csr_compact: the development knobs cannot fall back to CSR
+    if (A->force_layout == 0 && csr) return LAYOUT_CSR;     // mik_csr_set_layout
+    if ((A->ctx->tuning[MIK_KNOB_LAYOUTS] & 1) == 0 || !csr) {
+        if (A->sdia_pats && ((A->ctx->tuning[MIK_KNOB_LAYOUTS] & 4) == 0 || !csr)) return LAYOUT_SDIAC;
+        if (A->sdia_val && ((A->ctx->tuning[MIK_KNOB_LAYOUTS] & 4) == 0 || !csr)) return LAYOUT_SDIA;
+        if (A->sdiaw_pats && ((A->ctx->tuning[MIK_KNOB_LAYOUTS] & 4) == 0 || !csr)) return LAYOUT_SDIAW;
+        if (A->jds_val && (A->ctx->tuning[MIK_KNOB_LAYOUTS] & 8) == 0) return LAYOUT_JDS;
+    }
+    return LAYOUT_CSR;
+}
+
+// CSR kernels.  k_spmv_rowgather (row-block tile filled by LDS-DMA, per-row gather) unless the operator has split-off long rows: then
+// k_spmv_rowblock, whose launch carries the long-row workgroups along (one launch instead of two: 180 vs 196 us on the random configs[4]
+// stand-in, 107 vs 121 us on the banded one).  Operators with x windows (irregular rows inside a band, csr_build_xwin) or a row
+// permutation run on the product tile too, which gathers from them.  MIK_KNOB_CSR_KERNEL: 0 = that rule, 1 = always k_spmv_rowblock,
+// 2 = always k_spmv_rowgather.  Same results bit for bit (tests/test_gpu_layouts.py).
+static inline bool spmv_csr_rowgather(const mik_csr *A)
+{
+    return A->ctx->tuning[MIK_KNOB_CSR_KERNEL] == 2 || (A->ctx->tuning[MIK_KNOB_CSR_KERNEL] == 0 && A->n_long == 0 && !A->xwin_lo && !A->rperm);
+}
+
+// The x windows, the long-row windows and the row permutation of the product tile are live (MIK_KNOB_LAYOUTS bit 32: never built, bit 64: built
+// but not used at launch)
+static inline bool spmv_windows_live(const mik_csr *A) { return (A->ctx->tuning[MIK_KNOB_LAYOUTS] & 96) == 0; }
+
+// k_spmv_sdiab (buffer loads) serves the slice-constant layout: finite pattern values and 32-bit offsets (csr_build_sdia allocates
+// sdia_recs exactly then), and MIK_KNOB_SDIA_KERNEL does not ask for the flat-load kernel k_spmv_sdiac (1)
+static inline bool spmv_sdiab_usable(const mik_csr *A) { return A->sdia_buf_ok && A->ctx->tuning[MIK_KNOB_SDIA_KERNEL] != 1; }
+
+// k_spmv_sdiab2 (two rows per lane): the operator's class has the lane-neighbour shape, n is even, and MIK_KNOB_SDIA_KERNEL asks for
+// no other form (2: no compiled-in class; 3: one row per lane)
+static inline bool sdiab2_applies(const mik_csr *A)
+{
+    return A->sdia_buf_ok && A->sdia_cls >= 1 && (A->n_rows & 1) == 0 && A->ctx->tuning[MIK_KNOB_SDIA_KERNEL] == 0;
+}
+
+// The kernels that run two rows per lane take PAIRS of row-blocks: an even first one, and an even count or a range that reaches the end
+static inline bool spmv_pair_range(int rb0, int nb, int nb_all) { return (rb0 & 1) == 0 && ((nb & 1) == 0 || rb0 + nb == nb_all); }
+
 extern "C" int mik_csr_layout(const mik_csr *A, int *layout)
 {
     if (!A || !layout) return MIK_ERR_INVALID;
@@ -1299,18 +1351,16 @@ extern "C" int mik_csr_set_layout(mik_csr *A, int layout)
 extern "C" int mik_csr_stored_bytes(const mik_csr *A, int64_t *bytes)
 {
     if (!A || !bytes) return MIK_ERR_INVALID;
-    int layout = 0;
-    (void)mik_csr_layout(A, &layout);
     const int64_t es = (int64_t)mik_dtype_size(A->dtype);
     const int64_t nb = (A->n_rows + MIK_BLOCK - 1) / MIK_BLOCK;
-    switch (layout) {
-    case 5: *bytes = A->n_rows + nb * ((A->sdia_recs && A->ctx->tuning[MIK_KNOB_SDIA_KERNEL] != 1) ? 64 : 4) + (int64_t)A->sdia_npat * (80 + 8 * es); break;
-    case 6: *bytes = A->n_rows * 4 + nb * 4 + (nb + 1) / 2 * 64 + (int64_t)A->sdiaw_npat * A->sdiaw_pat_bytes; break;
-    case 4: *bytes = A->sdia_entries * es + A->n_rows + nb * 36; break;
-    case 1: *bytes = A->jds_groups * (16 / es) * (es + 4) + A->n_rows * 2 + ((A->n_rows + 63) / 64 + 1) * 4 +
-                     (A->n_long ? (A->nnz - A->jds_short_nnz) * (es + 4) + 12LL * A->n_long + 4LL * A->n_seg + 16LL * A->n_cut : 0); break;
-    default: *bytes = A->nnz * (es + 4) + (A->n_rows + 1) * 4 + (A->n_long ? A->n_rows + 12LL * A->n_long + 4LL * A->n_seg + 16LL * A->n_cut : 0) +
-                      ((A->xwin_lo && !spmv_csr_rowgather(A)) ? nb * 4 : 0) + ((A->rperm && !spmv_csr_rowgather(A)) ? A->n_rows : 0); break;
+    switch (spmv_kernel_choice(A)) {
+    case LAYOUT_SDIAC: *bytes = A->n_rows + nb * (spmv_sdiab_usable(A) ? 64 : 4) + (int64_t)A->sdia_npat * (80 + 8 * es); break;
+    case LAYOUT_SDIAW: *bytes = A->n_rows * 4 + nb * 4 + (nb + 1) / 2 * 64 + (int64_t)A->sdiaw_npat * A->sdiaw_pat_bytes; break;
+    case LAYOUT_SDIA: *bytes = A->sdia_entries * es + A->n_rows + nb * 36; break;
+    case LAYOUT_JDS: *bytes = A->jds_groups * (16 / es) * (es + 4) + A->n_rows * 2 + ((A->n_rows + 63) / 64 + 1) * 4 +
+                              (A->n_long ? (A->nnz - A->jds_short_nnz) * (es + 4) + 12LL * A->n_long + 4LL * A->n_seg + 16LL * A->n_cut : 0); break;
+    case LAYOUT_CSR: *bytes = A->nnz * (es + 4) + (A->n_rows + 1) * 4 + (A->n_long ? A->n_rows + 12LL * A->n_long + 4LL * A->n_seg + 16LL * A->n_cut : 0) +
+                              ((A->xwin_lo && !spmv_csr_rowgather(A)) ? nb * 4 : 0) + ((A->rperm && !spmv_csr_rowgather(A)) ? A->n_rows : 0); break;
     }
     return MIK_OK;
 }
@@ -1323,29 +1373,6 @@ extern "C" int mik_csr_info(const mik_csr *A, int64_t *n_rows, int64_t *n_cols, 
     if (nnz) *nnz = A->nnz;
     if (dtype) *dtype = A->dtype;
     return MIK_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// SpMV
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-int mik_spmv_launch_range(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done, int rb_begin,
-                          int rb_count);
-
-// Which kernel mik_spmv_launch_range picks for this operator under the current development knobs -- ONE function, used
-// by the launcher, by mik_csr_layout and by mik_spmv_can_split, so the three can never disagree.
-//   5 per-slice offsets + slice-constant values, 4 sliced-ELL + per-slice offsets, 2 sliced-ELL + 8-bit codes, 1 sliced-ELL, 0 CSR
-static int spmv_kernel_choice(const mik_csr *A)
-{
-    const bool csr = A->col != nullptr;                     // false after mik_csr_compact: the development knobs cannot fall back to CSR
-    if (A->force_layout == 0 && csr) return 0;              // mik_csr_set_layout
-    if ((A->ctx->tuning[MIK_KNOB_LAYOUTS] & 1) == 0 || !csr) {
-        if (A->sdia_pats && ((A->ctx->tuning[MIK_KNOB_LAYOUTS] & 4) == 0 || !csr)) return 5;
-        if (A->sdia_val && ((A->ctx->tuning[MIK_KNOB_LAYOUTS] & 4) == 0 || !csr)) return 4;
-        if (A->sdiaw_pats && ((A->ctx->tuning[MIK_KNOB_LAYOUTS] & 4) == 0 || !csr)) return 6;
-        if (A->jds_val && (A->ctx->tuning[MIK_KNOB_LAYOUTS] & 8) == 0) return 1;
-    }
-    return 0;
 }
 
 // The CSR arrays (12 B per entry at fp64) are what every matrix can run on, and what the development knobs fall back to;
@@ -1362,56 +1389,406 @@ extern "C" int mik_csr_compact(mik_csr *A)
     return MIK_OK;
 }
 
-static inline bool spmv_csr_rowgather(const mik_csr *A)
+// ---------------------------------------------------------------------------------------------
+// SpMV: the launch plan.  ONE host function decides which kernel runs, on which grid, with which template and scalar arguments;
+// the launcher executes it and every query (mik_spmv_kernel, mik_spmv_has_epilogue, mik_spmv_can_split, mik_spmv_is_light,
+// mik_dev_spmv_plan) reads it, so none of them can disagree with what is launched.
+// ---------------------------------------------------------------------------------------------
+enum SpmvKernel { SPMV_ROWGATHER, SPMV_ROWBLOCK, SPMV_JDS, SPMV_SDIA, SPMV_SDIAC, SPMV_SDIAB, SPMV_SDIAB2, SPMV_SDIAW, SPMV_SDIAW2 };
+
+constexpr int SPMV_NO_SKIP = 0x7fffffff;   // skip_at of a launch that skips nothing (skip_len = 0)
+
+struct SpmvPlan {
+    int rc = MIK_OK;                 // MIK_OK, or the code of the launcher's refusal ...
+    const char *refusal = nullptr;   // ... and its text
+    bool empty = false;              // nothing to launch: no rows, or an empty range
+    // about the operator's kernel (valid in every plan, refused and empty ones included)
+    SpmvKernel kernel = SPMV_ROWGATHER;
+    bool can_split = false;          // the kernel serves a proper sub-range of row-blocks
+    bool skips = false;              // the kernel leaves out a range of row-blocks itself (skip_at, skip_len)
+    bool epilogue = false;           // this launch takes y = A x + c w / dot(z, y) (ctx->spmv_ep_*)
+    // the launches: [k_spmv_longrows] kernel [k_rowdot]
+    bool pre_longrows = false, post_rowdot = false;
+    int grid = 0;                    // workgroups of `kernel`
+    size_t lds = 0, pre_lds = 0;     // dynamic LDS bytes of `kernel` / of k_spmv_longrows
+    bool fd = false;                 // FUSE_DOT of `kernel` (the jagged slices leave dot(x, y) to k_rowdot when long rows exist)
+    int nb_all = 0, nlb = 0;         // row-blocks of the operator; long-row workgroups (4 virtual rows each)
+    int rb0 = 0, nb = 0, map_mode = 0;                  // first row-block, row-blocks, workgroup map (spmv_block_map)
+    int skip_at = SPMV_NO_SKIP, skip_len = 0;
+    int pb0 = 0, np = 0, pmode = 0, ps = -1, pfull = 0; // the same for PAIRS of row-blocks (k_spmv_sdiab2: ps, pfull; k_spmv_sdiaw2: pmode)
+    int sshift = -1, nfull = 0, cls = 0;                // k_spmv_sdiab: strips as shifts, row-blocks inside whole strips; compiled-in slot class
+    bool merge = false, nt_rb = false, xwin = false, rp = false;   // k_spmv_rowblock / k_spmv_jds: MERGE_LONG; k_spmv_rowblock: NT, XWIN, RPERM
+    bool long_win = false;           // the long-row workgroups read x through their LDS windows (A->long_win)
+    int lw_launch = 0;               // elements of x such a workgroup of the k_spmv_rowblock launch can hold; < 0: spread over the launch
+};
+
+static SpmvPlan spmv_refusal(SpmvPlan p, int rc, const char *text) { p.rc = rc; p.refusal = text; return p; }
+static inline bool spmv_ep_armed(const mik_ctx *ctx) { return ctx->spmv_ep_w || ctx->spmv_ep_c || ctx->spmv_ep_z; }
+
+// No HIP call, no allocation: reads the operator, its context's development knobs, and the arguments.  Row-blocks [rb_begin, rb_begin +
+// rb_count) (rb_count < 0: all) except [skip_at, skip_at + skip_len); es = element size; ep_armed: ctx->spmv_ep_* are set.
+static SpmvPlan spmv_plan(const mik_csr *A, size_t es, bool x_aligned, bool fuse_dot, int rb_begin, int rb_count, int skip_at, int skip_len, bool ep_armed)
 {
-    // operators with x windows (irregular rows inside a band, csr_build_xwin) run on the product tile, which gathers from them
-    return A->ctx->tuning[MIK_KNOB_CSR_KERNEL] == 2 || (A->ctx->tuning[MIK_KNOB_CSR_KERNEL] == 0 && A->n_long == 0 && !A->xwin_lo && !A->rperm);
+    SpmvPlan p;
+    const int *knob = A->ctx->tuning;
+    const int n = (int)A->n_rows, nb_all = (int)mik_spmv_nwg(n), nlong = A->n_long;
+    const bool whole = rb_count < 0 || (rb_begin == 0 && rb_count == nb_all);
+    const int rb0 = whole ? 0 : rb_begin, nb = whole ? nb_all : rb_count;
+    switch (spmv_kernel_choice(A)) {
+    case LAYOUT_SDIAC:   // MIK_KNOB_SDIA_KERNEL = 1: the flat-load kernel
+        p.kernel = !spmv_sdiab_usable(A) ? SPMV_SDIAC : (sdiab2_applies(A) && skip_len == 0 && spmv_pair_range(rb0, nb, nb_all)) ? SPMV_SDIAB2 : SPMV_SDIAB;
+        break;
+    case LAYOUT_SDIAW:   // MIK_KNOB_SDIA_KERNEL = 3: one row per lane
+        p.kernel = ((n & 1) == 0 && (uint64_t)A->n_cols * es < 0x7FFFFFF0ull && knob[MIK_KNOB_SDIA_KERNEL] != 3 && spmv_pair_range(rb0, nb, nb_all)) ? SPMV_SDIAW2 : SPMV_SDIAW;
+        break;
+    case LAYOUT_SDIA: p.kernel = SPMV_SDIA; break;
+    case LAYOUT_JDS: p.kernel = SPMV_JDS; break;
+    case LAYOUT_CSR: p.kernel = spmv_csr_rowgather(A) ? SPMV_ROWGATHER : SPMV_ROWBLOCK; break;
+    }
+    const bool row_per_thread = p.kernel == SPMV_ROWGATHER || p.kernel == SPMV_ROWBLOCK || p.kernel == SPMV_JDS;
+    // The sliced kernels and k_spmv_rowgather take a first row-block; k_spmv_rowblock and operators with split-off long rows (their
+    // wave-per-row workgroups cover the whole matrix) do not.
+    p.can_split = p.kernel != SPMV_ROWBLOCK && !(row_per_thread && nlong);
+    p.skips = p.kernel == SPMV_SDIAB || p.kernel == SPMV_SDIAB2;
+    // k_spmv_sdiab2, the two CSR kernels and the jagged slices (whole launches with the fused dot, no split-off long rows) take the epilogue
+    // y = A x + c w, dot(x, y) -- the Lanczos step of MINRES -- and dot(z, y) in place of dot(x, y) -- sigma and rho of BiCGStab(l).
+    // MIK_KNOB_SOLVER_FORM = 2: never.
+    p.epilogue = whole && fuse_dot && knob[MIK_KNOB_SOLVER_FORM] != 2 && (p.kernel == SPMV_SDIAB2 || (row_per_thread && nlong == 0));
+    if (n == 0) { p.empty = true; return p; }
+    if (!whole && !p.can_split) return spmv_refusal(p, MIK_ERR_NOTIMPL, "SpMV over a row-block range is not available for this operator layout");
+    if (!whole && (rb_begin < 0 || rb_begin + rb_count > nb_all)) return spmv_refusal(p, MIK_ERR_INVALID, "SpMV row-block range out of bounds");
+    if (!whole && rb_count == 0) { p.empty = true; return p; }
+    if (ep_armed && !p.epilogue)
+        return spmv_refusal(p, MIK_ERR_NOTIMPL, "SpMV: the y = A x + c w / dot(z, y) epilogue is not available for this operator's kernel");
+
+    // workgroup map: the operator's own choice (strips for banded operators, else identity; spmv_block_map)
+    p.map_mode = A->strip;
+    if (!whole && p.map_mode >= 8 && (rb0 % p.map_mode != 0 || nb % p.map_mode != 0)) p.map_mode = 0;   // strips need whole planes
+    if (skip_len > 0) p.map_mode = 0;
+    p.nb_all = nb_all; p.rb0 = rb0; p.nb = nb; p.skip_at = skip_at; p.skip_len = skip_len;
+    p.pb0 = rb0 / 2; p.np = (nb + 1) / 2;
+    p.fd = fuse_dot;
+    p.grid = nb;
+    p.nlb = (nlong + 3) / 4;                    // one wave per virtual row (a whole row or a segment of a cut row)
+    p.long_win = A->long_win && spmv_windows_live(A) && x_aligned;
+    p.pre_lds = p.long_win ? es * (size_t)A->long_lw : 0;
+    switch (p.kernel) {
+    case SPMV_SDIAB: case SPMV_SDIAB2:
+        // strips of a power-of-two number of row-blocks are mapped by shifts; any other map runs as identity here
+        if (p.map_mode >= 8) {
+            const int S = p.map_mode >> 3;
+            if ((S & (S - 1)) == 0) { p.sshift = 0; while ((1 << p.sshift) < S) ++p.sshift; p.nfull = nb / p.map_mode * p.map_mode; }
+        }
+        p.cls = knob[MIK_KNOB_SDIA_KERNEL] == 2 ? 0 : A->sdia_cls;           // MIK_KNOB_SDIA_KERNEL = 2: slot-by-slot path only
+        if (p.kernel == SPMV_SDIAB2) {   // workgroups over PAIRS of slices; strips halve with them
+            p.grid = (p.np + 7) / 8 * 8;
+            p.ps = p.sshift >= 1 ? p.sshift - 1 : -1;
+            p.pfull = p.sshift >= 1 ? p.nfull / 2 : 0;
+            break;
+        }
+        [[fallthrough]];
+    case SPMV_SDIAC: p.grid = ((nb + MIK_SDIAC_G - 1) / MIK_SDIAC_G + 7) / 8 * 8; break;    // G slices per workgroup; a multiple of 8: see k_spmv_sdiac
+    case SPMV_SDIAW2:
+        p.grid = p.np;
+        p.pmode = p.map_mode >= 16 ? (p.map_mode / 2 + 7) / 8 * 8 : 0;       // strips of slice PAIRS
+        break;
+    case SPMV_SDIAW: case SPMV_SDIA: break;
+    case SPMV_JDS:
+        // the workgroups of split-off long rows lead the same launch.  dot(x, y) is formed inside unless long rows exist (their sums
+        // arrive from other workgroups): then by k_rowdot.
+        p.fd = fuse_dot && nlong == 0;
+        p.merge = nlong > 0;
+        p.post_rowdot = fuse_dot && !p.fd;
+        p.grid = nb + (p.merge ? p.nlb : 0);
+        break;
+    case SPMV_ROWGATHER:
+        p.pre_longrows = nlong > 0;   // long rows first (whole launches only, see can_split); the row kernel then picks y[r] up
+        break;
+    case SPMV_ROWBLOCK: {
+        p.merge = nlong > 0 && !fuse_dot;           // one launch: long-row workgroups first, then row-blocks
+        p.pre_longrows = nlong > 0 && !p.merge;     // fused dot: long rows first in their own launch, the row-block kernel then picks y[r] up
+        // The operator streams of the product tile are read with the DEFAULT cache policy when x is served from LDS windows: non-temporal
+        // streams, right for the stencil operators, cost this kernel 10 % there (banded configs[4] stand-in: 72.8 us streamed, 65.7 us
+        // cached -- profiles/r04_c5_*).  (A/B in round 5: cached 186.1 us, streamed 191.0 us on `random` -- profiles/r05_c5_random_stream_policy_ab.txt.)
+        // (Only where x comes from LDS windows: without them -- the `random` stand-in -- cached streams gain 3 % back to back and lose 6 % inside
+        // gmres!, where they push the Krylov basis out of the caches: 260 -> 275 us per inner iteration.)
+        p.nt_rb = !A->xwin_lo;
+        p.grid = nb + (p.merge ? p.nlb : 0);
+        // x served from an LDS window per row-block (csr_build_xwin; MIK_KNOB_LAYOUTS bit 6: off at launch) -- an aligned x only
+        p.xwin = A->xwin_lo && spmv_windows_live(A) && x_aligned;
+        const size_t rb_tile = (size_t)MIK_SPMV_TILE * (8 / es);
+        p.lds = es * (rb_tile + 12 + (p.xwin ? (size_t)A->xwin_span : 0));          // [product tile + 8][4 wave sums][x window]
+        const int lw = (int)std::min<size_t>((size_t)A->long_lw, p.lds / 1024 * (1024 / es));  // what a long-row workgroup of this launch can hold
+        p.lw_launch = (p.merge && p.long_win && A->long_spread) ? -lw : lw;
+        p.rp = A->rperm && spmv_windows_live(A);    // rows of a block over its threads by length (mik_build_rperm_host)
+        break;
+    }
+    }
+    return p;
 }
 
-// k_spmv_sdiab2 (two rows per lane): the operator's class has the lane-neighbour shape, n is even, and no development
-// knob asks for another form (16: slices per workgroup; 18: no compiled-in class; 19: 1 = one row per lane)
-static bool sdiab2_applies(const mik_csr *A)
+static const char *spmv_kernel_name(const SpmvPlan &p)
 {
-    return A->sdia_buf_ok && A->sdia_cls >= 1 && (A->n_rows & 1) == 0 && A->ctx->tuning[MIK_KNOB_SDIA_KERNEL] == 0;
+    switch (p.kernel) {
+    case SPMV_ROWGATHER: return "k_spmv_rowgather";
+    case SPMV_ROWBLOCK: return p.xwin ? "k_spmv_rowblock+xwin" : "k_spmv_rowblock";
+    case SPMV_JDS: return "k_spmv_jds";
+    case SPMV_SDIA: return "k_spmv_sdia";
+    case SPMV_SDIAC: return "k_spmv_sdiac";
+    case SPMV_SDIAB: return "k_spmv_sdiab";
+    case SPMV_SDIAB2: return "k_spmv_sdiab2";
+    case SPMV_SDIAW: return "k_spmv_sdiaw";
+    case SPMV_SDIAW2: return "k_spmv_sdiaw2";
+    }
+    return "";
 }
 
-// k_spmv_sdiab2, the two CSR kernels and the jagged slices (whole launches with the fused dot, no split-off long rows) take the epilogue
-// y = A x + c w, dot(x, y) -- the Lanczos step of MINRES -- and dot(z, y) in place of dot(x, y) -- sigma and rho of BiCGStab(l)
-bool mik_spmv_has_epilogue(const mik_csr *A)
+// The plan of mul!(y, A, x): a whole launch, an aligned x, no fused dot, nothing armed.  fuse_dot = true: of the solvers' fused step head.
+static SpmvPlan spmv_plan_whole(const mik_csr *A, bool fuse_dot)
 {
-    if (!A || A->ctx->tuning[MIK_KNOB_SOLVER_FORM] == 2) return false;                    // MIK_KNOB_SOLVER_FORM = 2: never
-    const int kc = spmv_kernel_choice(A);
-    if (kc == 5) return A->sdia_buf_ok && A->ctx->tuning[MIK_KNOB_SDIA_KERNEL] != 1 && sdiab2_applies(A);
-    return (kc == 0 || kc == 1) && A->n_long == 0;                       // the CSR kernels and the jagged slices: one row per thread, no split-off long rows
+    return spmv_plan(A, mik_dtype_size(A->dtype), true, fuse_dot, 0, -1, SPMV_NO_SKIP, 0, false);
 }
 
-// the operator's SpMV moves little more than x and y (the slice-constant layout): the CG step then picks other cache hints
-bool mik_spmv_is_light(const mik_csr *A) { return A && (spmv_kernel_choice(A) == 5 || spmv_kernel_choice(A) == 6); }
+bool mik_spmv_has_epilogue(const mik_csr *A) { return A && spmv_plan_whole(A, true).epilogue; }
+bool mik_spmv_can_split(const mik_csr *A) { return spmv_plan_whole(A, false).can_split; }
+// the slice-constant layouts: the CG step then picks other cache hints
+bool mik_spmv_is_light(const mik_csr *A) { return A && (spmv_kernel_choice(A) == LAYOUT_SDIAC || spmv_kernel_choice(A) == LAYOUT_SDIAW); }
 
 extern "C" int mik_spmv_kernel(const mik_csr *A, char *name, int len)
 {
     if (!A || !name || len <= 0) return MIK_ERR_INVALID;
-    const char *k = "k_spmv_rowblock";
-    switch (spmv_kernel_choice(A)) {
-    case 5: k = A->sdia_buf_ok && A->ctx->tuning[MIK_KNOB_SDIA_KERNEL] != 1 ? (sdiab2_applies(A) ? "k_spmv_sdiab2" : "k_spmv_sdiab") : "k_spmv_sdiac"; break;
-    case 6: k = ((A->n_rows & 1) == 0 && A->ctx->tuning[MIK_KNOB_SDIA_KERNEL] != 3) ? "k_spmv_sdiaw2" : "k_spmv_sdiaw"; break;
-    case 4: k = "k_spmv_sdia"; break;
-    case 1: k = "k_spmv_jds"; break;
-    default: k = spmv_csr_rowgather(A) ? "k_spmv_rowgather" : ((A->xwin_lo && (A->ctx->tuning[MIK_KNOB_LAYOUTS] & 96) == 0) ? "k_spmv_rowblock+xwin" : "k_spmv_rowblock"); break;
-    }
-    snprintf(name, (size_t)len, "%s", k);
+    snprintf(name, (size_t)len, "%s", spmv_kernel_name(spmv_plan_whole(A, false)));
     return MIK_OK;
 }
 
-// Can mik_spmv_launch_range serve a sub-range of row-blocks for this operator?  The sliced-ELL kernels and the default
-// CSR kernel take a first row-block; the dictionary-coded kernel, k_spmv_rowblock (MIK_KNOB_CSR_KERNEL = 1) and operators with
-// split-off long rows (their wave-per-row launch covers the whole matrix) do not.
-bool mik_spmv_can_split(const mik_csr *A)
+// The plans of mik_spmv_launch_outside -- the rows OUTSIDE the row-blocks [skip_begin, skip_end): one launch where the kernel leaves a
+// range out itself (the slice-constant layout's buffer kernels), else the two ranges on either side.  Returns how many of out[] to run.
+static int spmv_plan_outside(const mik_csr *A, size_t es, bool x_aligned, bool fuse_dot, int skip_begin, int skip_end, bool ep_armed, SpmvPlan out[2])
 {
-    const int kc = spmv_kernel_choice(A);
-    if (kc == 0) return spmv_csr_rowgather(A) && A->n_long == 0;
-    if (kc == 1) return A->n_long == 0;
-    return true;
+    const int nb_all = (int)mik_spmv_nwg(A->n_rows), rest = skip_begin + (nb_all - skip_end);
+    if (skip_begin < 0 || skip_end < skip_begin || skip_end > nb_all) { out[0] = spmv_refusal(SpmvPlan{}, MIK_ERR_INVALID, "SpMV: bad interior range"); return 1; }
+    out[0] = spmv_plan(A, es, x_aligned, fuse_dot, 0, rest, skip_begin, skip_end - skip_begin, ep_armed);
+    if (out[0].skips && rest > 0) return 1;
+    out[0] = spmv_plan(A, es, x_aligned, fuse_dot, 0, skip_begin, SPMV_NO_SKIP, 0, ep_armed);
+    out[1] = spmv_plan(A, es, x_aligned, fuse_dot, skip_end, nb_all - skip_end, SPMV_NO_SKIP, 0, ep_armed);
+    return 2;
+}
+
+extern "C" int mik_dev_spmv_plan(const mik_csr *A, const void *x, int fuse_dot, int rb_begin, int rb_count, int skip_begin, int skip_end, char *kernel_name,
+                                 int len, int64_t *grid, int *launches, int *pre_longrows, int *post_rowdot)
+{
+    if (!A || (kernel_name && len <= 0)) return MIK_ERR_INVALID;
+    const bool armed = spmv_ep_armed(A->ctx);
+    SpmvPlan p[2];
+    int np = 1;
+    if (skip_begin < 0) p[0] = spmv_plan(A, mik_dtype_size(A->dtype), mik_aligned16(x), fuse_dot != 0, rb_begin, rb_count, SPMV_NO_SKIP, 0, armed);
+    else np = spmv_plan_outside(A, mik_dtype_size(A->dtype), mik_aligned16(x), fuse_dot != 0, skip_begin, skip_end, armed, p);
+    int total = 0;
+    const SpmvPlan *first = nullptr;            // the first plan that launches: its kernel, grid and companions are reported
+    for (int i = 0; i < np; ++i) {
+        if (p[i].rc != MIK_OK) return mik_fail(A->ctx, p[i].rc, "%s", p[i].refusal);
+        if (p[i].empty) continue;
+        total += (int)p[i].pre_longrows + 1 + (int)p[i].post_rowdot;
+        if (!first) first = &p[i];
+    }
+    if (kernel_name) snprintf(kernel_name, (size_t)len, "%s", spmv_kernel_name(first ? *first : p[0]));
+    if (grid) *grid = first ? first->grid : 0;
+    if (launches) *launches = total;
+    if (pre_longrows) *pre_longrows = first && first->pre_longrows;
+    if (post_rowdot) *post_rowdot = first && first->post_rowdot;
+    return MIK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// SpMV: the launcher executes the plan
+// ---------------------------------------------------------------------------------------------
+// Runtime flags as template arguments: with_consts(f, a, b, ...) calls f(A{}, B{}, ...) with std::true_type / std::false_type for
+// every bool, and std::integral_constant<int, 0 .. 3> for an SdiaCls (anything outside 1 .. 3: 0, the slot-by-slot path).
+struct SdiaCls { int c; };
+template <typename F> static inline void with_consts(F &&f) { f(); }
+template <typename F, typename... R> static inline void with_consts(F &&f, bool b, R... rest);
+template <typename F, typename... R> static inline void with_consts(F &&f, SdiaCls s, R... rest);
+template <typename C, typename F, typename... R> static inline void with_const(F &f, R... rest)
+{
+    with_consts([&](auto... c) { f(C{}, c...); }, rest...);
+}
+template <typename F, typename... R> static inline void with_consts(F &&f, bool b, R... rest)
+{
+    if (b) with_const<std::true_type>(f, rest...);
+    else with_const<std::false_type>(f, rest...);
+}
+template <typename F, typename... R> static inline void with_consts(F &&f, SdiaCls s, R... rest)
+{
+    switch (s.c) {
+    case 1: with_const<std::integral_constant<int, 1>>(f, rest...); break;
+    case 2: with_const<std::integral_constant<int, 2>>(f, rest...); break;
+    case 3: with_const<std::integral_constant<int, 3>>(f, rest...); break;
+    default: with_const<std::integral_constant<int, 0>>(f, rest...); break;
+    }
+}
+
+// what a launch needs that is a pointer
+template <typename T> struct SpmvIO {
+    mik_ctx *ctx;
+    const mik_csr *A;
+    const T *x;
+    T *y, *seg_out;
+    const int *done;
+    const T *ep_w() const { return (const T *)ctx->spmv_ep_w; }
+    const T *ep_c() const { return (const T *)ctx->spmv_ep_c; }
+    const T *ep_z() const { return (const T *)ctx->spmv_ep_z; }
+};
+
+static LongTab spmv_long_tab(const mik_csr *A)
+{
+    LongTab lt{};
+    if (const int nlong = A->n_long) {
+        int *tb = A->long_rows;
+        lt.rows = tb; lt.starts = tb + nlong; lt.lens = tb + 2 * nlong;
+        lt.seg_row = tb + 3 * nlong;
+        lt.cut_row = lt.seg_row + A->n_seg; lt.cut_first = lt.cut_row + A->n_cut; lt.cut_nseg = lt.cut_first + A->n_cut;
+        lt.tickets = (unsigned *)(tb + 3 * nlong + A->n_seg + 3 * A->n_cut);
+        lt.seg_sum = A->seg_sum; lt.nlong = nlong;
+    }
+    return lt;
+}
+
+// Every family function launches p.kernel on p.grid; the NT argument of the sliced kernels and of k_spmv_rowgather is always true.
+// slice patterns {offsets, values} + one mask byte per row (mik_sell.h), MIK_SDIAC_G slices per workgroup: buffer loads ...
+template <typename T> static void spmv_go_sdiab(const SpmvPlan &p, const SpmvIO<T> &io)
+{
+    const mik_csr *A = io.A;
+    with_consts([&](auto fd, auto cls) {
+        constexpr int C = decltype(cls)::value;
+        hipLaunchKernelGGL((k_spmv_sdiab<T, decltype(fd)::value, true, MIK_SDIAC_G, mik_sdiab_cls_ns(C), mik_sdiab_cls_cq(C)>), dim3(p.grid), dim3(MIK_BLOCK), 0,
+                           io.ctx->stream, (int)A->n_rows, (int)A->n_cols, A->sdia_koff, p.rb0, p.nb, p.nfull, p.sshift, p.skip_at, p.skip_len,
+                           (const SdiaSliceRec *)A->sdia_recs, (const SdiaPattern<T> *)A->sdia_pats, A->sdia_mask, io.x, io.y, io.seg_out, io.done);
+    }, p.fd, SdiaCls{p.cls});
+}
+
+// ... two rows per lane, 16-byte gathers: workgroups over PAIRS of slices (the classes 1 .. 3 only: sdiab2_applies) ...
+template <typename T> static void spmv_go_sdiab2(const SpmvPlan &p, const SpmvIO<T> &io)
+{
+    const mik_csr *A = io.A;
+    with_consts([&](auto fd, auto cls) {
+        constexpr int C = decltype(cls)::value;
+        if constexpr (C >= 1)
+            hipLaunchKernelGGL((k_spmv_sdiab2<T, decltype(fd)::value, true, mik_sdiab_cls_ns(C), mik_sdiab_cls_cq(C)>), dim3(p.grid), dim3(MIK_BLOCK), 0,
+                               io.ctx->stream, (int)A->n_rows, (int)A->n_cols, A->sdia_koff, p.pb0, p.np, p.pfull, p.ps, p.nb_all,
+                               (const SdiaSliceRec *)A->sdia_recs, (const SdiaPattern<T> *)A->sdia_pats, A->sdia_mask, io.x, io.y, io.seg_out, io.done,
+                               io.ep_w(), io.ep_c(), io.ep_z());
+    }, p.fd, SdiaCls{p.cls});
+}
+
+// ... and flat loads (non-finite coefficients, 64-bit offsets)
+template <typename T> static void spmv_go_sdiac(const SpmvPlan &p, const SpmvIO<T> &io)
+{
+    const mik_csr *A = io.A;
+    with_consts([&](auto fd) {
+        hipLaunchKernelGGL((k_spmv_sdiac<T, decltype(fd)::value, true, MIK_SDIAC_G>), dim3(p.grid), dim3(MIK_BLOCK), 0, io.ctx->stream, (int)A->n_rows,
+                           (int)A->n_cols, p.rb0, p.nb, p.map_mode, A->sdia_pat_id, (const SdiaPattern<T> *)A->sdia_pats, A->sdia_mask, io.x, io.y,
+                           io.seg_out, io.done);
+    }, p.fd);
+}
+
+// slice patterns of up to 32 {offset, value} pairs + one mask word per row (mik_sell.h): one row per lane, or two over PAIRS of slices
+template <typename T> static void spmv_go_sdiaw(const SpmvPlan &p, const SpmvIO<T> &io)
+{
+    const mik_csr *A = io.A;
+    with_consts([&](auto fd) {
+        if (p.kernel == SPMV_SDIAW2)
+            hipLaunchKernelGGL((k_spmv_sdiaw2<T, decltype(fd)::value, true>), dim3(p.grid), dim3(MIK_BLOCK), 0, io.ctx->stream, (int)A->n_rows, (int)A->n_cols,
+                               A->sdiaw_koff, p.pb0, p.np, p.pmode, p.nb_all, A->sdiaw_pat_id, (const SdiawPattern<T> *)A->sdiaw_pats, A->sdiaw_mask,
+                               (const uint4 *)A->sdiaw_uz, io.x, io.y, io.seg_out, io.done);
+        else
+            hipLaunchKernelGGL((k_spmv_sdiaw<T, decltype(fd)::value, true>), dim3(p.grid), dim3(MIK_BLOCK), 0, io.ctx->stream, (int)A->n_rows, A->sdiaw_koff,
+                               p.rb0, p.nb, p.map_mode, A->sdiaw_pat_id, (const SdiawPattern<T> *)A->sdiaw_pats, A->sdiaw_mask, io.x, io.y, io.seg_out,
+                               io.done);
+    }, p.fd);
+}
+
+// sliced-ELL values + per-slice offsets + row masks (mik_sell.h)
+template <typename T> static void spmv_go_sdia(const SpmvPlan &p, const SpmvIO<T> &io)
+{
+    const mik_csr *A = io.A;
+    with_consts([&](auto fd) {
+        hipLaunchKernelGGL((k_spmv_sdia<T, decltype(fd)::value, true>), dim3(p.grid), dim3(MIK_BLOCK), 0, io.ctx->stream, (int)A->n_rows, (int)A->n_cols, p.rb0,
+                           p.nb, p.map_mode, A->sdia_ptr, A->sdia_off, A->sdia_tri, A->sdia_mask, (const T *)A->sdia_val, io.x, io.y, io.seg_out, io.done);
+    }, p.fd);
+}
+
+// jagged slices (mik_jds.h): one row per lane, 16-byte operator streams; the fused dot never shares a launch with long-row workgroups
+template <typename T> static void spmv_go_jds(const SpmvPlan &p, const SpmvIO<T> &io)
+{
+    const mik_csr *A = io.A;
+    using IV = typename WideVec<T>::idx;
+    using VV = typename WideVec<T>::val;
+    with_consts([&](auto fd, auto mg) {
+        if constexpr (!(decltype(fd)::value && decltype(mg)::value))
+            hipLaunchKernelGGL((k_spmv_jds<T, decltype(fd)::value, true, decltype(mg)::value>), dim3(p.grid), dim3(MIK_BLOCK), 0, io.ctx->stream, (int)A->n_rows,
+                               p.rb0, A->jds_ptr, A->jds_len, (const IV *)A->jds_col, (const VV *)A->jds_val, io.x, io.y, io.seg_out, io.done, p.nlb,
+                               spmv_long_tab(A), A->col, (const T *)A->val, io.ep_w(), io.ep_c(), io.ep_z());
+    }, p.fd, p.merge);
+}
+
+// CSR: row-block tile filled by LDS-DMA, per-row gather
+template <typename T> static void spmv_go_rowgather(const SpmvPlan &p, const SpmvIO<T> &io)
+{
+    const mik_csr *A = io.A;
+    with_consts([&](auto fd) {
+        hipLaunchKernelGGL((k_spmv_rowgather<T, decltype(fd)::value, true>), dim3(p.grid), dim3(MIK_BLOCK), 0, io.ctx->stream, (int)A->n_rows, p.rb0, p.nb,
+                           p.map_mode, A->rowptr, A->col, (const T *)A->val, io.x, io.y, io.seg_out, io.done, A->is_long, io.ep_w(), io.ep_c(), io.ep_z());
+    }, p.fd);
+}
+
+// CSR: register-staged product tile (wide loads); the fused dot never shares a launch with long-row workgroups
+template <typename T> static void spmv_go_rowblock(const SpmvPlan &p, const SpmvIO<T> &io)
+{
+    const mik_csr *A = io.A;
+    with_consts([&](auto fd, auto mg, auto nt, auto xw, auto rp) {
+        if constexpr (!(decltype(fd)::value && decltype(mg)::value))
+            hipLaunchKernelGGL((k_spmv_rowblock<T, decltype(fd)::value, decltype(nt)::value, true, decltype(mg)::value, decltype(xw)::value, decltype(rp)::value>),
+                               dim3(p.grid), dim3(MIK_BLOCK), p.lds, io.ctx->stream, (int)A->n_rows, p.nb, p.map_mode, A->rowptr, A->col, (const T *)A->val,
+                               io.x, io.y, io.seg_out, io.done, A->is_long, p.nlb, spmv_long_tab(A), (const int *)A->xwin_lo, A->xwin_span,
+                               (const unsigned char *)A->rperm, (p.merge && p.long_win) ? (const int *)A->long_win : (const int *)nullptr, p.lw_launch,
+                               io.ep_w(), io.ep_c(), io.ep_z());
+    }, p.fd, p.merge, p.nt_rb, p.xwin, p.rp);
+}
+
+template <typename T> static int spmv_run(const SpmvPlan &p, const SpmvIO<T> &io)
+{
+    mik_ctx *ctx = io.ctx;
+    const mik_csr *A = io.A;
+    if (p.rc != MIK_OK) return mik_fail(ctx, p.rc, "%s", p.refusal);
+    if (p.empty) return MIK_OK;
+    if (p.pre_longrows) {
+        hipLaunchKernelGGL((k_spmv_longrows<T>), dim3(p.nlb), dim3(MIK_BLOCK), p.pre_lds, ctx->stream, spmv_long_tab(A), A->col, (const T *)A->val, io.x, io.y,
+                           io.done, p.long_win ? (const int *)A->long_win : (const int *)nullptr, A->long_lw);
+        MIK_LAUNCH_CHECK(ctx);
+    }
+    switch (p.kernel) {
+    case SPMV_ROWGATHER: spmv_go_rowgather<T>(p, io); break;
+    case SPMV_ROWBLOCK: spmv_go_rowblock<T>(p, io); break;
+    case SPMV_JDS: spmv_go_jds<T>(p, io); break;
+    case SPMV_SDIA: spmv_go_sdia<T>(p, io); break;
+    case SPMV_SDIAC: spmv_go_sdiac<T>(p, io); break;
+    case SPMV_SDIAB: spmv_go_sdiab<T>(p, io); break;
+    case SPMV_SDIAB2: spmv_go_sdiab2<T>(p, io); break;
+    case SPMV_SDIAW: case SPMV_SDIAW2: spmv_go_sdiaw<T>(p, io); break;
+    }
+    MIK_LAUNCH_CHECK(ctx);
+    if (p.post_rowdot) {
+        hipLaunchKernelGGL((k_rowdot<T>), dim3(p.nb_all), dim3(MIK_BLOCK), 0, ctx->stream, (int)A->n_rows, io.x, (const T *)io.y, io.seg_out, io.done);
+        MIK_LAUNCH_CHECK(ctx);
+    }
+    return MIK_OK;
+}
+
+template <typename T>
+int mik_spmv_launch_range(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done, int rb_begin,
+                          int rb_count)
+{
+    return spmv_run<T>(spmv_plan(A, sizeof(T), mik_aligned16(x), fuse_dot, rb_begin, rb_count, SPMV_NO_SKIP, 0, spmv_ep_armed(ctx)), {ctx, A, x, y, seg_out, done});
 }
 
 template <typename T>
@@ -1420,244 +1797,16 @@ int mik_spmv_launch(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_
     return mik_spmv_launch_range<T>(ctx, A, x, y, fuse_dot, seg_out, done, 0, -1);
 }
 
-// Row-blocks [rb_begin, rb_begin + rb_count) only (rb_count < 0: all).  Partial ranges need mik_spmv_can_split.
-// rows OUTSIDE the row-blocks [skip_begin, skip_end): one launch for the slice-constant layout's buffer kernel, else two ranges
-template <typename T>
-static int spmv_launch_impl(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done, int rb_begin, int rb_count,
-                            int skip_at, int skip_len);
-
-template <typename T>
-int mik_spmv_launch_range(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done, int rb_begin,
-                          int rb_count)
-{
-    return spmv_launch_impl<T>(ctx, A, x, y, fuse_dot, seg_out, done, rb_begin, rb_count, 0x7fffffff, 0);
-}
-
 template <typename T>
 int mik_spmv_launch_outside(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done, int skip_begin, int skip_end)
 {
-    const int nb_all = (int)mik_spmv_nwg(A->n_rows);
-    if (skip_begin < 0 || skip_end < skip_begin || skip_end > nb_all) return mik_fail(ctx, MIK_ERR_INVALID, "SpMV: bad interior range");
-    if (spmv_kernel_choice(A) == 5 && A->sdia_buf_ok && A->ctx->tuning[MIK_KNOB_SDIA_KERNEL] != 1 && skip_begin + (nb_all - skip_end) > 0)
-        return spmv_launch_impl<T>(ctx, A, x, y, fuse_dot, seg_out, done, 0, skip_begin + (nb_all - skip_end), skip_begin, skip_end - skip_begin);
-    MIK_TRY(mik_spmv_launch_range<T>(ctx, A, x, y, fuse_dot, seg_out, done, 0, skip_begin));
-    return mik_spmv_launch_range<T>(ctx, A, x, y, fuse_dot, seg_out, done, skip_end, nb_all - skip_end);
+    SpmvPlan p[2];
+    const int np = spmv_plan_outside(A, sizeof(T), mik_aligned16(x), fuse_dot, skip_begin, skip_end, spmv_ep_armed(ctx), p);
+    for (int i = 0; i < np; ++i) MIK_TRY(spmv_run<T>(p[i], {ctx, A, x, y, seg_out, done}));
+    return MIK_OK;
 }
 template int mik_spmv_launch_outside<double>(mik_ctx *, const mik_csr *, const double *, double *, bool, double *, const int *, int, int);
 template int mik_spmv_launch_outside<float>(mik_ctx *, const mik_csr *, const float *, float *, bool, float *, const int *, int, int);
-
-template <typename T>
-static int spmv_launch_impl(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done, int rb_begin, int rb_count,
-                            int skip_at, int skip_len)
-{
-    const int n = (int)A->n_rows;
-    if (n == 0) return MIK_OK;
-    const int nb_all = (int)mik_spmv_nwg(n);
-    const bool whole = rb_count < 0 || (rb_begin == 0 && rb_count == nb_all);
-    if (!whole && !mik_spmv_can_split(A)) return mik_fail(ctx, MIK_ERR_NOTIMPL, "SpMV over a row-block range is not available for this operator layout");
-    if (!whole && (rb_begin < 0 || rb_begin + rb_count > nb_all)) return mik_fail(ctx, MIK_ERR_INVALID, "SpMV row-block range out of bounds");
-    if (!whole && rb_count == 0) return MIK_OK;
-    const int rb0 = whole ? 0 : rb_begin;
-    // development knobs (mik_set_tuning): [0] 1 = temporal (cached) streams, [1] 1 = narrow loads,
-    // [2] block map (0 = the operator's own choice: strips for banded operators, else identity; < 0 identity;
-    //     1 contiguous range per XCD; P >= 8 strips of P row-blocks)
-    const int nb = whole ? nb_all : rb_count;
-    const bool wide = true;
-    int map_mode = A->strip;
-    if (!whole && map_mode >= 8 && (rb0 % map_mode != 0 || nb % map_mode != 0)) map_mode = 0;   // strips need whole planes
-    if (skip_len > 0) map_mode = 0;
-    const int choice = spmv_kernel_choice(A);
-    if ((ctx->spmv_ep_w || ctx->spmv_ep_c || ctx->spmv_ep_z) && !(whole && fuse_dot && mik_spmv_has_epilogue(A)))
-        return mik_fail(ctx, MIK_ERR_NOTIMPL, "SpMV: the y = A x + c w / dot(z, y) epilogue is not available for this operator's kernel");
-    if (choice == 5) {
-        // slice patterns {offsets, values} + one mask byte per row (mik_sell.h); G slices per workgroup
-        const int G = MIK_SDIAC_G;
-        const int wgs = ((nb + G - 1) / G + 7) / 8 * 8;                         // a multiple of 8: see k_spmv_sdiac
-        if (A->sdia_buf_ok && ctx->tuning[MIK_KNOB_SDIA_KERNEL] != 1) {                          // development knob MIK_KNOB_SDIA_KERNEL = 1: the flat-load kernel
-            // strips of a power-of-two number of row-blocks are mapped by shifts; any other map runs as identity here
-            int sshift = -1, nfull = 0;
-            if (map_mode >= 8) {
-                const int S = map_mode >> 3;
-                if ((S & (S - 1)) == 0) { sshift = 0; while ((1 << sshift) < S) ++sshift; nfull = nb / map_mode * map_mode; }
-            }
-#define MIK_SDIAB_GO4(FD, NTV, GG, C)                                                                                                      \
-    hipLaunchKernelGGL((k_spmv_sdiab<T, FD, NTV, GG, mik_sdiab_cls_ns(C), mik_sdiab_cls_cq(C)>), dim3(wgs), dim3(MIK_BLOCK), 0, ctx->stream, n, (int)A->n_cols, A->sdia_koff, \
-                       rb0, nb, nfull, sshift, skip_at, skip_len, (const SdiaSliceRec *)A->sdia_recs, (const SdiaPattern<T> *)A->sdia_pats, A->sdia_mask, x, y, seg_out, done)
-#define MIK_SDIAB_GO3(FD, NTV, GG)                                                                                                          \
-    do { if (cls == 1) MIK_SDIAB_GO4(FD, NTV, GG, 1); else if (cls == 2) MIK_SDIAB_GO4(FD, NTV, GG, 2); else if (cls == 3) MIK_SDIAB_GO4(FD, NTV, GG, 3); \
-         else MIK_SDIAB_GO4(FD, NTV, GG, 0); } while (0)
-#define MIK_SDIAB_GO(FD, NTV)                                                                      \
-    do { if (G == 1) MIK_SDIAB_GO4(FD, NTV, 1, 0); else if (G == 4) MIK_SDIAB_GO4(FD, NTV, 4, 0); else MIK_SDIAB_GO3(FD, NTV, 2); } while (0)
-            const int cls = ctx->tuning[MIK_KNOB_SDIA_KERNEL] == 2 ? 0 : A->sdia_cls;            // development knob MIK_KNOB_SDIA_KERNEL = 2: slot-by-slot path only
-            if (sdiab2_applies(A) && skip_len == 0 && (rb0 & 1) == 0 && ((nb & 1) == 0 || rb0 + nb == nb_all)) {
-                // two rows per lane, 16-byte gathers (k_spmv_sdiab2): workgroups over PAIRS of slices; strips halve with them
-                const int np = (nb + 1) / 2, pb0 = rb0 / 2, wg2 = (np + 7) / 8 * 8;
-                const int ps = sshift >= 1 ? sshift - 1 : -1, pfull = sshift >= 1 ? nfull / 2 : 0;
-#define MIK_SDIAB2_GO4(FD, NTV, C)                                                                                                       \
-    hipLaunchKernelGGL((k_spmv_sdiab2<T, FD, NTV, mik_sdiab_cls_ns(C), mik_sdiab_cls_cq(C)>), dim3(wg2), dim3(MIK_BLOCK), 0, ctx->stream, n, (int)A->n_cols, A->sdia_koff, \
-                       pb0, np, pfull, ps, nb_all, (const SdiaSliceRec *)A->sdia_recs, (const SdiaPattern<T> *)A->sdia_pats, A->sdia_mask, x, y, seg_out, done, \
-                       (const T *)ctx->spmv_ep_w, (const T *)ctx->spmv_ep_c, (const T *)ctx->spmv_ep_z)
-#define MIK_SDIAB2_GO(FD, NTV) do { if (cls == 1) MIK_SDIAB2_GO4(FD, NTV, 1); else if (cls == 2) MIK_SDIAB2_GO4(FD, NTV, 2); else MIK_SDIAB2_GO4(FD, NTV, 3); } while (0)
-                if (fuse_dot) { MIK_SDIAB2_GO(true, true); }
-                else          { MIK_SDIAB2_GO(false, true); }
-#undef MIK_SDIAB2_GO4
-#undef MIK_SDIAB2_GO
-                MIK_LAUNCH_CHECK(ctx);
-                return MIK_OK;
-            }
-            if (fuse_dot) { MIK_SDIAB_GO(true, true); }
-            else          { MIK_SDIAB_GO(false, true); }
-#undef MIK_SDIAB_GO4
-#undef MIK_SDIAB_GO3
-#undef MIK_SDIAB_GO
-            MIK_LAUNCH_CHECK(ctx);
-            return MIK_OK;
-        }
-#define MIK_SDIAC_GO3(FD, NTV, GG)                                                                                             \
-    hipLaunchKernelGGL((k_spmv_sdiac<T, FD, NTV, GG>), dim3(wgs), dim3(MIK_BLOCK), 0, ctx->stream, n, (int)A->n_cols, rb0, nb, map_mode, A->sdia_pat_id, \
-                       (const SdiaPattern<T> *)A->sdia_pats, A->sdia_mask, x, y, seg_out, done)
-#define MIK_SDIAC_GO(FD, NTV)                                                                      \
-    do { if (G == 1) MIK_SDIAC_GO3(FD, NTV, 1); else if (G == 4) MIK_SDIAC_GO3(FD, NTV, 4); else MIK_SDIAC_GO3(FD, NTV, 2); } while (0)
-        if (fuse_dot) { MIK_SDIAC_GO(true, true); }
-        else          { MIK_SDIAC_GO(false, true); }
-#undef MIK_SDIAC_GO3
-#undef MIK_SDIAC_GO
-        MIK_LAUNCH_CHECK(ctx);
-        return MIK_OK;
-    }
-    if (choice == 6 && (n & 1) == 0 && (uint64_t)A->n_cols * sizeof(T) < 0x7FFFFFF0ull && ctx->tuning[MIK_KNOB_SDIA_KERNEL] != 3 && (rb0 & 1) == 0 &&
-        ((nb & 1) == 0 || rb0 + nb == nb_all)) {
-        // ... two rows per lane (k_spmv_sdiaw2): workgroups over PAIRS of slices (MIK_KNOB_SDIA_KERNEL = 3: one row per lane)
-        const int np = (nb + 1) / 2, pb0 = rb0 / 2;
-        const int pmode = map_mode >= 16 ? (map_mode / 2 + 7) / 8 * 8 : 0;       // strips of slice PAIRS
-#define MIK_SDIAW2_GO(FD, NTV)                                                                                                \
-    hipLaunchKernelGGL((k_spmv_sdiaw2<T, FD, NTV>), dim3(np), dim3(MIK_BLOCK), 0, ctx->stream, n, (int)A->n_cols, A->sdiaw_koff, pb0, np, pmode, nb_all, \
-                       A->sdiaw_pat_id, (const SdiawPattern<T> *)A->sdiaw_pats, A->sdiaw_mask, (const uint4 *)A->sdiaw_uz, x, y, seg_out, done)
-        if (fuse_dot) { MIK_SDIAW2_GO(true, true); }
-        else          { MIK_SDIAW2_GO(false, true); }
-#undef MIK_SDIAW2_GO
-        MIK_LAUNCH_CHECK(ctx);
-        return MIK_OK;
-    }
-    if (choice == 6) {
-        // slice patterns of up to 32 {offset, value} pairs + one mask word per row (mik_sell.h)
-#define MIK_SDIAW_GO(FD, NTV)                                                                                                 \
-    hipLaunchKernelGGL((k_spmv_sdiaw<T, FD, NTV>), dim3(nb), dim3(MIK_BLOCK), 0, ctx->stream, n, A->sdiaw_koff, rb0, nb, map_mode, A->sdiaw_pat_id, \
-                       (const SdiawPattern<T> *)A->sdiaw_pats, A->sdiaw_mask, x, y, seg_out, done)
-        if (fuse_dot) { MIK_SDIAW_GO(true, true); }
-        else          { MIK_SDIAW_GO(false, true); }
-#undef MIK_SDIAW_GO
-        MIK_LAUNCH_CHECK(ctx);
-        return MIK_OK;
-    }
-    if (choice == 4) {
-        // sliced-ELL values + per-slice offsets + row masks (mik_sell.h)
-#define MIK_SDIA_GO(FD, NTV)                                                                                                  \
-    hipLaunchKernelGGL((k_spmv_sdia<T, FD, NTV>), dim3(nb), dim3(MIK_BLOCK), 0, ctx->stream, n, (int)A->n_cols, rb0, nb, map_mode, A->sdia_ptr, \
-                       A->sdia_off, A->sdia_tri, A->sdia_mask, (const T *)A->sdia_val, x, y, seg_out, done)
-        if (fuse_dot) { MIK_SDIA_GO(true, true); }
-        else          { MIK_SDIA_GO(false, true); }
-#undef MIK_SDIA_GO
-        MIK_LAUNCH_CHECK(ctx);
-        return MIK_OK;
-    }
-    const int nlong = A->n_long;
-    LongTab lt{};
-    if (nlong) {
-        int *tb = A->long_rows;
-        lt.rows = tb; lt.starts = tb + nlong; lt.lens = tb + 2 * nlong;
-        lt.seg_row = tb + 3 * nlong;
-        lt.cut_row = lt.seg_row + A->n_seg; lt.cut_first = lt.cut_row + A->n_cut; lt.cut_nseg = lt.cut_first + A->n_cut;
-        lt.tickets = (unsigned *)(tb + 3 * nlong + A->n_seg + 3 * A->n_cut);
-        lt.seg_sum = A->seg_sum; lt.nlong = nlong;
-    }
-    const int nlb = (nlong + 3) / 4;                    // one wave per virtual row (a whole row or a segment of a cut row)
-    const int *lwin = (A->long_win && (ctx->tuning[MIK_KNOB_LAYOUTS] & 96) == 0 && mik_aligned16(x)) ? A->long_win : nullptr;   // the long-row workgroups' windows of x in LDS
-    if (choice == 1) {
-        // jagged slices (mik_jds.h): one row per lane, 16-byte operator streams; the workgroups of split-off long rows lead the same
-        // launch.  dot(x, y) is formed inside unless long rows exist (their sums arrive from other workgroups): then by k_rowdot.
-        using IV = typename WideVec<T>::idx;
-        using VV = typename WideVec<T>::val;
-        const bool inside = fuse_dot && nlong == 0;
-#define MIK_JDS_GO(FD, NTV, MG)                                                                                                        \
-    hipLaunchKernelGGL((k_spmv_jds<T, FD, NTV, MG>), dim3(nb + (MG ? nlb : 0)), dim3(MIK_BLOCK), 0, ctx->stream, n, rb0, A->jds_ptr, A->jds_len, \
-                       (const IV *)A->jds_col, (const VV *)A->jds_val, x, y, seg_out, done, nlb, lt, A->col, (const T *)A->val, (const T *)ctx->spmv_ep_w, (const T *)ctx->spmv_ep_c, (const T *)ctx->spmv_ep_z)
-#define MIK_JDS_GO2(NTV)                                                                      \
-    do {                                                                                      \
-        if (inside) MIK_JDS_GO(true, NTV, false);                                             \
-        else if (nlong) MIK_JDS_GO(false, NTV, true);                                         \
-        else MIK_JDS_GO(false, NTV, false);                                                   \
-    } while (0)
-        MIK_JDS_GO2(true);
-#undef MIK_JDS_GO2
-#undef MIK_JDS_GO
-        MIK_LAUNCH_CHECK(ctx);
-        if (fuse_dot && !inside) {
-            hipLaunchKernelGGL((k_rowdot<T>), dim3(nb_all), dim3(MIK_BLOCK), 0, ctx->stream, n, x, (const T *)y, seg_out, done);
-            MIK_LAUNCH_CHECK(ctx);
-        }
-        return MIK_OK;
-    }
-    // CSR kernels.  k_spmv_rowgather (row-block tile filled by LDS-DMA, per-row gather) unless the operator has split-off
-    // long rows: then k_spmv_rowblock, whose launch carries the long-row workgroups along (one launch instead of two:
-    // 180 vs 196 us on the random configs[4] stand-in, 107 vs 121 us on the banded one).  MIK_KNOB_CSR_KERNEL: 0 = that rule,
-    // 1 = always k_spmv_rowblock, 2 = always k_spmv_rowgather.  Same results bit for bit (tests/test_gpu_layouts.py).
-    if (spmv_csr_rowgather(A)) {
-        if (nlong) {   // long rows first (whole launches only, see mik_spmv_can_split); the row kernel then picks y[r] up
-            hipLaunchKernelGGL((k_spmv_longrows<T>), dim3(nlb), dim3(MIK_BLOCK), lwin ? sizeof(T) * (size_t)A->long_lw : 0, ctx->stream, lt, A->col, (const T *)A->val, x, y, done,
-                               lwin, A->long_lw);
-            MIK_LAUNCH_CHECK(ctx);
-        }
-#define MIK_RG_GO(FD, NTV)                                                                                                      \
-    hipLaunchKernelGGL((k_spmv_rowgather<T, FD, NTV>), dim3(nb), dim3(MIK_BLOCK), 0, ctx->stream, n, rb0, nb, map_mode, A->rowptr, \
-                       A->col, (const T *)A->val, x, y, seg_out, done, A->is_long, (const T *)ctx->spmv_ep_w, (const T *)ctx->spmv_ep_c, (const T *)ctx->spmv_ep_z)
-        if (fuse_dot) { MIK_RG_GO(true, true); }
-        else          { MIK_RG_GO(false, true); }
-#undef MIK_RG_GO
-        MIK_LAUNCH_CHECK(ctx);
-        return MIK_OK;
-    }
-    const bool merge = nlong > 0 && !fuse_dot;           // one launch: long-row workgroups first, then row-blocks
-    // The operator streams of the product tile are read with the DEFAULT cache policy when x is served from LDS windows: non-temporal
-    // streams, right for the stencil operators, cost this kernel 10 % there (banded configs[4] stand-in: 72.8 us streamed, 65.7 us
-    // cached -- profiles/r04_c5_*).  (A/B in round 5: cached 186.1 us, streamed 191.0 us on `random` -- profiles/r05_c5_random_stream_policy_ab.txt.)
-    // (Only where x comes from LDS windows: without them -- the `random` stand-in -- cached streams gain 3 % back to back and lose 6 % inside
-    // gmres!, where they push the Krylov basis out of the caches: 260 -> 275 us per inner iteration.)
-    const bool nt_rb = !A->xwin_lo;
-    if (nlong && !merge) {
-        // fused dot: long rows first in their own launch, the row-block kernel then picks y[r] up
-        hipLaunchKernelGGL((k_spmv_longrows<T>), dim3(nlb), dim3(MIK_BLOCK), lwin ? sizeof(T) * (size_t)A->long_lw : 0, ctx->stream, lt, A->col, (const T *)A->val, x, y, done,
-                           lwin, A->long_lw);
-        MIK_LAUNCH_CHECK(ctx);
-    }
-    const dim3 grid(nb + (merge ? nlb : 0)), block(MIK_BLOCK);
-    // x served from an LDS window per row-block (csr_build_xwin; MIK_KNOB_LAYOUTS bit 6: off at launch) -- wide loads and an aligned x only
-    const bool xwin = A->xwin_lo && wide && (ctx->tuning[MIK_KNOB_LAYOUTS] & 96) == 0 && mik_aligned16(x);
-    constexpr int RB_TILE = MIK_SPMV_TILE * (int)(8 / sizeof(T));
-    const size_t dyn = sizeof(T) * ((size_t)RB_TILE + 12 + (xwin ? (size_t)A->xwin_span : 0));          // [product tile + 8][4 wave sums][x window]
-    const int lw_launch = (int)std::min<size_t>((size_t)A->long_lw, dyn / 1024 * (1024 / sizeof(T)));  // what a long-row workgroup of this launch can hold
-    const bool rp = A->rperm && wide && (ctx->tuning[MIK_KNOB_LAYOUTS] & 96) == 0;         // rows of a block over its threads by length (mik_build_rperm_host)
-#define MIK_SPMV_GO(FD, NT, WD, MG, XW, RP)                                                                      \
-    hipLaunchKernelGGL((k_spmv_rowblock<T, FD, NT, WD, MG, XW, RP>), grid, block, dyn, ctx->stream, n, nb, map_mode, A->rowptr, \
-                       A->col, (const T *)A->val, x, y, seg_out, done, A->is_long, nlb, lt, (const int *)A->xwin_lo, A->xwin_span, (const unsigned char *)A->rperm, \
-                       MG ? lwin : (const int *)nullptr, (MG && lwin && A->long_spread) ? -lw_launch : lw_launch, (const T *)ctx->spmv_ep_w, (const T *)ctx->spmv_ep_c, (const T *)ctx->spmv_ep_z)
-#define MIK_SPMV_GO3(FD, NT, MG)                                                          \
-    do {                                                                                  \
-        if (xwin) { if (rp) MIK_SPMV_GO(FD, NT, true, MG, true, true); else MIK_SPMV_GO(FD, NT, true, MG, true, false); }   \
-        else if (rp) MIK_SPMV_GO(FD, NT, true, MG, false, true);                          \
-        else if (wide) MIK_SPMV_GO(FD, NT, true, MG, false, false);                       \
-        else MIK_SPMV_GO(FD, NT, false, MG, false, false);                                \
-    } while (0)
-#define MIK_SPMV_GO2(FD, MG) do { if (nt_rb) MIK_SPMV_GO3(FD, true, MG); else MIK_SPMV_GO3(FD, false, MG); } while (0)
-    if (fuse_dot) MIK_SPMV_GO2(true, false);
-    else if (merge) MIK_SPMV_GO2(false, true);
-    else MIK_SPMV_GO2(false, false);
-#undef MIK_SPMV_GO2
-#undef MIK_SPMV_GO3
-#undef MIK_SPMV_GO
-    MIK_LAUNCH_CHECK(ctx);
-    return MIK_OK;
-}
 template int mik_spmv_launch<double>(mik_ctx *, const mik_csr *, const double *, double *, bool, double *, const int *);
 template int mik_spmv_launch<float>(mik_ctx *, const mik_csr *, const float *, float *, bool, float *, const int *);
 template int mik_spmv_launch_range<double>(mik_ctx *, const mik_csr *, const double *, double *, bool, double *, const int *, int, int);

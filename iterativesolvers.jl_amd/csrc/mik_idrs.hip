@@ -25,9 +25,6 @@
 #include <new>
 #include <vector>
 
-template <typename T>
-int mik_spmv_launch(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done);   // mik_core.hip
-
 namespace {
 
 constexpr int IDRS_MAX_S = 32;        // shadow-space dimension the device path takes (the reference's default is 8)

@@ -179,6 +179,18 @@ int mik_ensure_partials(mik_ctx *ctx, size_t bytes);
 // device builders of the wide slice-constant layout and of the jagged slices from A's device CSR arrays (mik_upload.hip)
 int mik_build_sdiaw_device(mik_ctx *ctx, mik_csr *A);
 int mik_build_jds_device(mik_ctx *ctx, mik_csr *A);
+// SpMV launchers and the queries about them (mik_core.hip: all of them read one launch plan, spmv_plan).  y = A x on ctx->stream; fuse_dot:
+// one dot(x, y) segment sum per row-block into seg_out.  _range: row-blocks [rb_begin, rb_begin + rb_count) only (rb_count < 0: all; partial
+// ranges need mik_spmv_can_split).  _outside: the rows OUTSIDE the row-blocks [skip_begin, skip_end).
+template <typename T>
+int mik_spmv_launch(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done);
+template <typename T>
+int mik_spmv_launch_range(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done, int rb_begin,
+                          int rb_count);
+template <typename T>
+int mik_spmv_launch_outside(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done, int skip_begin, int skip_end);
+bool mik_spmv_can_split(const mik_csr *A);      // mik_spmv_launch_range serves a proper sub-range of row-blocks for this operator
+bool mik_spmv_is_light(const mik_csr *A);       // the operator's SpMV moves little more than x and y (the slice-constant layouts)
 bool mik_spmv_has_epilogue(const mik_csr *A);   // the active SpMV kernel of A takes the y = A x + c w epilogue (ctx->spmv_ep_*)
 // The window rule of the product-tile kernel (k_spmv_rowblock XWIN), shared by the host builder (csr_build_xwin, mik_core.hip) and the
 // device builder (mik_build_xwin_device, mik_upload.hip) so that they cannot disagree.  Input: per 256-row block the smallest / largest

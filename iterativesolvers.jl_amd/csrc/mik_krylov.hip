@@ -16,18 +16,6 @@
 #include "mik_iter.h"
 #include "mik_mail.h"
 
-template <typename T>
-int mik_spmv_launch(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done);
-template <typename T>
-int mik_spmv_launch_range(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done, int rb_begin,
-                          int rb_count);
-template <typename T>
-int mik_spmv_launch_outside(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done, int skip_begin, int skip_end);
-bool mik_spmv_can_split(const mik_csr *A);
-bool mik_spmv_is_light(const mik_csr *A);
-
-
-
 // =============================================================================================
 // Hessenberg least squares (host) -- src/hessenberg.jl:15-46
 // =============================================================================================

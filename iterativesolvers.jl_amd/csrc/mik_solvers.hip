@@ -17,9 +17,6 @@
 #include <limits>
 #include <new>
 
-template <typename T>
-int mik_spmv_launch(mik_ctx *ctx, const mik_csr *A, const T *x, T *y, bool fuse_dot, T *seg_out, const int *done);   // mik_core.hip
-
 namespace {
 
 template <typename T> struct BicgDev {
