@@ -87,7 +87,20 @@ enum {
                               * mik_stationary_create: a zero or missing diagonal entry (src/stationary_sparse.jl:19) */
 };
 
-enum { MIK_F64 = 0, MIK_F32 = 1 };
+enum { MIK_F64 = 0, MIK_F32 = 1,
+       /* ComplexF64 / ComplexF32, stored interleaved (re, im) like Julia and numpy -- the element types test/cg.jl:27,99 and
+        * test/gmres.jl:16,38,76 run next to the real ones.  Accepted by the entries marked "complex:" below and by no other: everywhere
+        * else a complex code is answered like any unknown code.  Arithmetic (Base's definitions, nothing contracted):
+        *   z * w = (zr wr - zi wi) + (zr wi + zi wr) i;   a * z = (a zr) + (a zi) i for a real a;
+        *   dot(x, y) = sum conj(x_i) y_i: per element re = xr yr + xi yi and im = xr yi - xi yr (every product rounded, the two terms
+        *   added), then the two-level tree of "Reduction semantics", one for re and one for im, with W = 16 B / sizeof(element);
+        *   norm(x) = mik_nrm2 over the 2 n interleaved reals (same bits, the same safe second pass).
+        * No complex division runs on the device. */
+       MIK_C64 = 2, MIK_C32 = 3 };
+/* Or-ed into the `dtype` of mik_axpy / mik_xpby / mik_scal with a complex code: the scalar is a HOST REAL of the component type and the
+ * product is real * complex -- what Julia's broadcast does with the real beta of src/cg.jl:51 and with inv(nrm) of
+ * src/orthogonalize.jl:76, src/gmres.jl:253.  (The sweep is then the real one over the 2 n interleaved reals.) */
+#define MIK_SCALAR_REAL 0x100
 
 /* orthogonalisation methods -- src/orthogonalize.jl:4-7 */
 enum { MIK_MGS = 0, MIK_CGS = 1, MIK_DGKS = 2 };
@@ -129,7 +142,7 @@ int mik_ctx_info(const mik_ctx *ctx, mik_device_info *out);
 int mik_ctx_set_stream(mik_ctx *ctx, void *hip_stream);
 int mik_ctx_synchronize(mik_ctx *ctx);
 const char *mik_last_error(mik_ctx *ctx);   /* ctx may be NULL: last error of a failed create */
-/* (W, L) of the level-1 reduction tree for `dtype` (see "Reduction semantics"). */
+/* (W, L) of the level-1 reduction tree for `dtype` (see "Reduction semantics").  complex: W = 16 B / sizeof(element) = 1 (MIK_C64), 2 (MIK_C32). */
 int mik_reduce_shape(int dtype, int *W, int *L);
 /* (W, L) of the dot(u, c) fused into the SpMV of the CG step: one row per thread (W = 1), L
  * consecutive 256-row blocks per workgroup. */
@@ -150,8 +163,8 @@ int mik_malloc(mik_ctx *ctx, size_t bytes, void **dptr);            /* similar(x
 int mik_free(mik_ctx *ctx, void *dptr);
 int mik_memcpy_h2d(mik_ctx *ctx, void *dst, const void *src, size_t bytes);   /* synchronous  */
 int mik_memcpy_d2h(mik_ctx *ctx, void *dst, const void *src, size_t bytes);   /* synchronous  */
-int mik_copy(mik_ctx *ctx, int dtype, int64_t n, const void *x, void *y);     /* copyto!(y, x) src/cg.jl:130 */
-int mik_fill(mik_ctx *ctx, int dtype, int64_t n, const void *value, void *x); /* x .= value    src/cg.jl:129 */
+int mik_copy(mik_ctx *ctx, int dtype, int64_t n, const void *x, void *y);     /* copyto!(y, x) src/cg.jl:130, src/gmres.jl:241; complex: yes */
+int mik_fill(mik_ctx *ctx, int dtype, int64_t n, const void *value, void *x); /* x .= value    src/cg.jl:129; complex: value is a host complex */
 
 /* ---- operator ---------------------------------------------------------------------------- */
 /* Upload a SparseMatrixCSC (is_csc = 1: ptr = colptr, idx = rowval -- the layout of
@@ -160,7 +173,11 @@ int mik_fill(mik_ctx *ctx, int dtype, int64_t n, const void *value, void *x); /*
  * Int32 CSR (CSC -> CSR transpose, columns ascending within a row = the order Julia's column scatter reaches a row), the
  * operator statistics and the layout analysis run there as kernels (csrc/mik_upload.hip; 0.06 s for the 256^3 Laplacian).
  * Matrices with rows longer than mik_spmv_long_row() or with duplicate (row, column) entries take the host path
- * (single-threaded counting-sort transpose + builders), as does everything when the development knob MIK_KNOB_UPLOAD is set. */
+ * (single-threaded counting-sort transpose + builders), as does everything when the development knob MIK_KNOB_UPLOAD is set.
+ * complex (SparseMatrixCSC{ComplexF64} of test/cg.jl:99-121, test/gmres.jl:38-57): CSC or CSR, any index base, rectangular; always the
+ * host path, and the operator always runs on its CSR arrays: mik_csr_layout reports 0, mik_csr_set_layout changes nothing,
+ * mik_csr_compact answers MIK_ERR_NOTIMPL, mik_csr_info / mik_csr_stored_bytes work.  Only mik_spmv takes such an operator: the fused
+ * iterables and every other entry with a mik_csr argument answer MIK_ERR_NOTIMPL. */
 int mik_csr_create(mik_ctx *ctx, int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz,
                    const int64_t *ptr, const int64_t *idx, const void *val, int index_base,
                    int is_csc, mik_csr **out);
@@ -198,19 +215,23 @@ int mik_csr_stored_bytes(const mik_csr *A, int64_t *bytes);
 int mik_csr_info(const mik_csr *A, int64_t *n_rows, int64_t *n_cols, int64_t *nnz, int *dtype);
 
 /* ---- L1 operator / vector interface ------------------------------------------------------ */
-/* mul!(y, A, x) -- SparseArrays mul!, called at src/cg.jl:54,137; src/gmres.jl:245,287 */
+/* mul!(y, A, x) -- SparseArrays mul!, called at src/cg.jl:54,137; src/gmres.jl:245,287
+ * complex: a row is summed serially in ascending column order, re and im each (rows beyond mik_spmv_long_row() / mik_spmv_long_segment()
+ * entries: the wave shape and the left-to-right segments of the real path); mik_spmv_kernel names the kernel (k_spmv_complex). */
 int mik_spmv(mik_ctx *ctx, const mik_csr *A, const void *x, void *y);
-/* dot(x, y) -- src/cg.jl:55, src/orthogonalize.jl:71.  *out is a host scalar of `dtype`. */
+/* dot(x, y) -- src/cg.jl:55, src/orthogonalize.jl:71.  *out is a host scalar of `dtype`.  complex: sum conj(x_i) y_i, *out one host complex. */
 int mik_dot(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void *y, void *out);
-/* norm(x) -- src/cg.jl:62,140; src/orthogonalize.jl:75; src/gmres.jl:252 */
+/* norm(x) -- src/cg.jl:62,140; src/orthogonalize.jl:75; src/gmres.jl:252.  complex: *out is a host REAL of the component type. */
 int mik_nrm2(mik_ctx *ctx, int dtype, int64_t n, const void *x, void *out);
-/* y .+= alpha .* x  -- src/cg.jl:58 (alpha) / :59 (-alpha) */
+/* y .+= alpha .* x  -- src/cg.jl:58 (alpha) / :59 (-alpha).  complex: alpha is a host complex (a host real with dtype | MIK_SCALAR_REAL). */
 int mik_axpy(mik_ctx *ctx, int dtype, int64_t n, const void *alpha, const void *x, void *y);
-/* y .= x .+ beta .* y -- src/cg.jl:51 (u .= r .+ beta .* u) */
+/* y .= x .+ beta .* y -- src/cg.jl:51 (u .= r .+ beta .* u).  complex: beta is a host complex; the REAL beta of src/cg.jl:50-51 is
+ * passed as a host real with dtype | MIK_SCALAR_REAL and multiplies as real * complex, like Julia's promotion in beta .* u. */
 int mik_xpby(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void *beta, void *y);
-/* y .-= x -- src/cg.jl:138, src/gmres.jl:246 */
+/* y .-= x -- src/cg.jl:138, src/gmres.jl:246.  complex: yes */
 int mik_sub(mik_ctx *ctx, int dtype, int64_t n, const void *x, void *y);
-/* x .*= alpha -- src/orthogonalize.jl:76, src/gmres.jl:253 */
+/* x .*= alpha -- src/orthogonalize.jl:76, src/gmres.jl:253.  complex: a host complex, or (both reference lines: inv of a norm) a host
+ * real with dtype | MIK_SCALAR_REAL. */
 int mik_scal(mik_ctx *ctx, int dtype, int64_t n, const void *alpha, void *x);
 /* y .= x ./ d -- ldiv!(y, P::JacobiPrec, x) of test/cg.jl:18 (diagonal left preconditioner) */
 int mik_divide(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void *d, void *y);
@@ -218,7 +239,9 @@ int mik_divide(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void *d,
 /* ---- L2 Krylov helpers ------------------------------------------------------------------- */
 /* orthogonalize_and_normalize!(V[:, 1:k], w, h, method) -> nrm -- src/orthogonalize.jl:13-79.
  * V: device, column-major, leading dimension ldv (elements); w: device n-vector (updated in
- * place, normalised); h: HOST array of k scalars (written); nrm: HOST scalar (written). */
+ * place, normalised); h: HOST array of k scalars (written); nrm: HOST scalar (written).
+ * complex: MIK_MGS only (src/orthogonalize.jl:67-79; MIK_CGS / MIK_DGKS answer MIK_ERR_NOTIMPL): h[i] = dot(V[:, i], w), w -= h[i] V[:, i],
+ * nrm = norm(w) (a host REAL), w *= inv(nrm) with inv(nrm) real; one sweep over w per column, h on the device between the sweeps. */
 int mik_orthogonalize(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv,
                       void *w, void *h, void *nrm, int method);
 /* orthogonalize_and_normalize!(V::Vector{Vector}, w, h, ModifiedGramSchmidt()) -> nrm -- src/orthogonalize.jl:53-65: the basis as
@@ -226,7 +249,7 @@ int mik_orthogonalize(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, 
  * on a matrix holding those columns.  (The reference defines this method for ModifiedGramSchmidt only.) */
 int mik_orthogonalize_vectors(mik_ctx *ctx, int dtype, int64_t n, int k, const void *const *V, void *w, void *h, void *nrm);
 /* mul!(y, V[:, 1:k], c, alpha, 1) -- src/gmres.jl:275 (alpha = 1), src/orthogonalize.jl:16 (-1).
- * c: HOST array of k scalars. */
+ * c: HOST array of k scalars.  complex (src/gmres.jl:275): t_j = alpha * c[j], then y = y + t_j * V[:, j], columns ascending. */
 int mik_gemv_n(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv,
                const void *c, const void *alpha, void *y);
 
@@ -606,11 +629,13 @@ int mik_cgd_connect_ghosts(mik_cgd *it, const void *handles, const int64_t *ghos
 /* ---- Hessenberg least squares (host) ------------------------------------------------------ */
 /* ldiv!(FastHessenberg(H), rhs) -- src/hessenberg.jl:15-46.  Host arrays of `dtype`; H is
  * (width+1) x width column-major with leading dimension ldh, overwritten by R; rhs has width+1
- * entries, overwritten by [y; residual]. */
+ * entries, overwritten by [y; residual].  complex (src/hessenberg.jl:24-39 with c real and s complex: -conj(s) in :31, :37; pinned on
+ * H2 of test/hessenberg.jl:20-26): host arrays of complex; the back substitution divides on the host. */
 int mik_hessenberg_ldiv(int dtype, void *H, int64_t ldh, int width, void *rhs);
 
 /* Host: LinearAlgebra.givensAlgorithm(f, g) -> out = {c, s, r} with [c s; -s c] [f; g] = [r; 0]
- * (src/hessenberg.jl:24, src/minres.jl:129).  f, g, out: host scalars / 3-array of dtype. */
+ * (src/hessenberg.jl:24, src/minres.jl:129).  f, g, out: host scalars / 3-array of dtype.  complex: givensAlgorithm(f::Complex, g::Complex),
+ * LAPACK's lartg convention: out = {c + 0 i, s, r} (three complex) with c real and [c s; -conj(s) c] [f; g] = [r; 0]. */
 int mik_givens(int dtype, const void *f, const void *g, void *out);
 
 /* ---- stationary methods: jacobi / gauss_seidel / sor / ssor on a SparseMatrixCSC (src/stationary_sparse.jl) ------------------

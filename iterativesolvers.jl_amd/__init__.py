@@ -21,7 +21,7 @@ The directory name (``iterativesolvers.jl_amd``) is not a Python identifier; loa
 from . import _lib, fixtures                                    # noqa: F401
 from ._lib import MikError, lib                                  # noqa: F401
 from .api import (CGIterable, CGStateVariables, ClassicalGramSchmidt, ConvergenceHistory, DGKS,   # noqa: F401
-                  GenericCGIterable, GMRESIterable, HipContext, HipCSR, HipMatrix, HipMatrixAdjoint, HipVector, Identity,
+                  GenericCGIterable, GenericGMRESIterable, DeviceKrylovOps, GMRESIterable, HipContext, HipCSR, HipMatrix, HipMatrixAdjoint, HipVector, Identity,
                   JacobiPrec, ModifiedGramSchmidt, PCGIterable, cg, cg_, cg_iterator_, default_context,
                   dot, gemv_n_, gmres, gmres_, gmres_iterable_, hessenberg_ldiv_, mul_, niters, norm, nprods,
                   nrests, orthogonalize_and_normalize_, zerox, BiCGStabIterable, bicgstabl, bicgstabl_, bicgstabl_iterator_,

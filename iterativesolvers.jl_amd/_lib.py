@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_HERE, "libmik.so")
 
 MIK_OK = 0
 MIK_F64, MIK_F32 = 0, 1
+MIK_C64, MIK_C32 = 2, 3          # ComplexF64 / ComplexF32, interleaved (re, im)
+MIK_SCALAR_REAL = 0x100            # or-ed into the dtype of mik_axpy / mik_xpby / mik_scal: a real host scalar on a complex vector
 MIK_MGS, MIK_CGS, MIK_DGKS = 0, 1, 2
 STATUS = {1: "invalid argument", 2: "HIP runtime error", 3: "dimension/dtype mismatch",
           4: "out of memory", 5: "not implemented", 6: "callback failed", 7: "norm outside the safely representable range",
@@ -295,7 +297,18 @@ def dtype_code(dtype) -> int:
         return MIK_F64
     if dtype == np.float32:
         return MIK_F32
-    raise TypeError(f"libmik supports float64 and float32 (complex is out of scope), got {dtype}")
+    if dtype == np.complex128:             # cg / gmres on CSR operators and the L1 / L2 entries under them
+        return MIK_C64
+    if dtype == np.complex64:
+        return MIK_C32
+    raise TypeError(f"libmik supports float64, float32, complex128 and complex64, got {dtype}")
+
+
+def real_dtype_code(dtype, who: str) -> int:
+    """``dtype_code`` for the entries that stay real (everything but cg / gmres on a CSR operator and the L1 / L2 entries under them)."""
+    if np.dtype(dtype).kind == "c":
+        raise TypeError(f"{who} is not offered for complex element types (DESIGN.md section 17: cg and gmres on a CSR operator are)")
+    return dtype_code(dtype)
 
 
 def check(code: int, where: str, ctx_handle=None):

@@ -41,6 +41,15 @@ def _scalar(dtype, value):
     return a, a.ctypes.data_as(_vp)
 
 
+def _real_dtype(dtype) -> np.dtype:
+    """``real(T)``: the type of ``norm``, of tolerances and of the components of a complex element type."""
+    return np.dtype(np.dtype(dtype).type(0).real.dtype)
+
+
+def _is_complex(dtype) -> bool:
+    return np.dtype(dtype).kind == "c"
+
+
 # ==============================================================================================
 # context, vectors, operator  (the L1 interface: docs/src/getting_started.md:25-30)
 # ==============================================================================================
@@ -126,8 +135,10 @@ def default_context() -> HipContext:
 
 
 class HipVector:
-    """Device n-vector of float64/float32: what ``similar``/``zero``/``copyto!``/``dot``/``norm``
-    and in-place broadcast need (src/cg.jl:51,58-59,62,124,129-130,138)."""
+    """Device n-vector of float64/float32/complex128/complex64: what ``similar``/``zero``/``copyto!``/``dot``/``norm``
+    and in-place broadcast need (src/cg.jl:51,58-59,62,124,129-130,138).  On a complex vector a scalar keeps
+    its kind: a complex one multiplies as complex * complex, a real one (the beta of src/cg.jl:51, inv(nrm) of src/gmres.jl:253) as
+    real * complex, like Julia's promotion."""
 
     def __init__(self, n: int, dtype=np.float64, ctx: Optional[HipContext] = None, *, _ptr=None, _owner=None):
         self.ctx = ctx or default_context()
@@ -188,6 +199,14 @@ class HipVector:
         if other.n != self.n or other.dtype != self.dtype:
             raise ValueError(f"DimensionMismatch: {self.n}/{self.dtype} vs {other.n}/{other.dtype}")
 
+    def _coef(self, value):
+        """host scalar, pointer and dtype code of the scalar of axpy_ / xpby_ / scal_"""
+        if _is_complex(self.dtype) and not np.iscomplexobj(value):
+            a, p = _scalar(_real_dtype(self.dtype), value)
+            return a, p, self.code | _lib.MIK_SCALAR_REAL
+        a, p = _scalar(self.dtype, value)
+        return a, p, self.code
+
     def fill_(self, value) -> "HipVector":                               # x .= value
         _, p = _scalar(self.dtype, value)
         check(lib().mik_fill(self.ctx.handle, self.code, self.n, p, _vp(self.ptr)), "mik_fill", self.ctx.handle)
@@ -200,14 +219,14 @@ class HipVector:
 
     def axpy_(self, alpha, x: "HipVector") -> "HipVector":               # self .+= alpha .* x
         self._same(x)
-        _, p = _scalar(self.dtype, alpha)
-        check(lib().mik_axpy(self.ctx.handle, self.code, self.n, p, _vp(x.ptr), _vp(self.ptr)), "mik_axpy", self.ctx.handle)
+        _, p, code = self._coef(alpha)
+        check(lib().mik_axpy(self.ctx.handle, code, self.n, p, _vp(x.ptr), _vp(self.ptr)), "mik_axpy", self.ctx.handle)
         return self
 
     def xpby_(self, x: "HipVector", beta) -> "HipVector":                # self .= x .+ beta .* self
         self._same(x)
-        _, p = _scalar(self.dtype, beta)
-        check(lib().mik_xpby(self.ctx.handle, self.code, self.n, _vp(x.ptr), p, _vp(self.ptr)), "mik_xpby", self.ctx.handle)
+        _, p, code = self._coef(beta)
+        check(lib().mik_xpby(self.ctx.handle, code, self.n, _vp(x.ptr), p, _vp(self.ptr)), "mik_xpby", self.ctx.handle)
         return self
 
     def sub_(self, x: "HipVector") -> "HipVector":                       # self .-= x
@@ -216,8 +235,8 @@ class HipVector:
         return self
 
     def scal_(self, alpha) -> "HipVector":                               # self .*= alpha
-        _, p = _scalar(self.dtype, alpha)
-        check(lib().mik_scal(self.ctx.handle, self.code, self.n, p, _vp(self.ptr)), "mik_scal", self.ctx.handle)
+        _, p, code = self._coef(alpha)
+        check(lib().mik_scal(self.ctx.handle, code, self.n, p, _vp(self.ptr)), "mik_scal", self.ctx.handle)
         return self
 
     def __len__(self):
@@ -233,7 +252,7 @@ class HipVector:
 
 
 def dot(x: HipVector, y: HipVector):
-    """``dot(x, y)`` -- src/cg.jl:55."""
+    """``dot(x, y)`` -- src/cg.jl:55 (complex: ``sum(conj(x) .* y)``, a complex scalar of the element type)."""
     x._same(y)
     out = np.zeros(1, x.dtype)
     check(lib().mik_dot(x.ctx.handle, x.code, x.n, _vp(x.ptr), _vp(y.ptr), out.ctypes.data_as(_vp)), "mik_dot", x.ctx.handle)
@@ -241,8 +260,8 @@ def dot(x: HipVector, y: HipVector):
 
 
 def norm(x: HipVector):
-    """``norm(x)`` -- src/cg.jl:62."""
-    out = np.zeros(1, x.dtype)
+    """``norm(x)`` -- src/cg.jl:62 (a real scalar, also for a complex vector)."""
+    out = np.zeros(1, _real_dtype(x.dtype))
     check(lib().mik_nrm2(x.ctx.handle, x.code, x.n, _vp(x.ptr), out.ctypes.data_as(_vp)), "mik_nrm2", x.ctx.handle)
     return out[0]
 
@@ -250,6 +269,7 @@ def norm(x: HipVector):
 def axpy_dot_(alpha, x: Optional[HipVector], y: HipVector, z: Optional[HipVector], hints: int = 0):
     """``y .+= alpha .* x`` (skipped when x is None) and, in the same sweep, ``dot(z, y)`` -- or ``norm(y)`` when z is
     None (src/minres.jl:104+107, :109+112)."""
+    _lib.real_dtype_code(y.dtype, "axpy_dot")
     out = np.zeros(1, y.dtype)
     _, pa = _scalar(y.dtype, 0 if x is None else alpha)
     check(lib().mik_axpy_dot(y.ctx.handle, y.code, y.n, pa, _vp(x.ptr if x is not None else None), _vp(y.ptr),
@@ -259,6 +279,7 @@ def axpy_dot_(alpha, x: Optional[HipVector], y: HipVector, z: Optional[HipVector
 
 def axpy2_nrm2_(alpha, u: HipVector, x: HipVector, c: HipVector, r: HipVector, hints: int = 0):
     """``x .+= alpha .* u; r .-= alpha .* c; norm(r)`` in one sweep (src/chebyshev.jl:51-54)."""
+    _lib.real_dtype_code(x.dtype, "axpy2_nrm2")
     out = np.zeros(1, x.dtype)
     _, pa = _scalar(x.dtype, alpha)
     check(lib().mik_axpy2_nrm2(x.ctx.handle, x.code, x.n, pa, _vp(u.ptr), _vp(x.ptr), _vp(c.ptr), _vp(r.ptr), out.ctypes.data_as(_vp), int(hints)),
@@ -611,8 +632,16 @@ class JacobiPrec:
 
     def ldiv_(self, y: HipVector, x: Optional[HipVector] = None):
         x = y if x is None else x
+        _refuse_complex_jacobi(y.dtype, self)
         check(lib().mik_divide(y.ctx.handle, y.code, y.n, _vp(x.ptr), _vp(self.diagonal.ptr), _vp(y.ptr)), "mik_divide", y.ctx.handle)
         return y
+
+
+def _refuse_complex_jacobi(dtype, *preconditioners):
+    """No complex division runs on the device (Julia's is Base's robust algorithm): the fused diagonal preconditioner is real only."""
+    if _is_complex(dtype) and any(isinstance(P, JacobiPrec) for P in preconditioners):
+        raise TypeError("JacobiPrec is not offered for complex element types (no complex division on the device): "
+                        "pass a preconditioner object with ldiv_(y, x)")
 
 
 def zerox(A: HipCSR, b: HipVector) -> HipVector:
@@ -805,12 +834,16 @@ class GenericCGIterable:
     """The reference's ``iterate(::CGIterable)`` / ``iterate(::PCGIterable)`` spelled with the L1
     entry points only (mul_, dot, norm, broadcast forms) -- i.e. what the unmodified package does
     with a device vector type (SURVEY.md section 8b plug point 1).  Works with any ``Pl`` that has
-    ``ldiv_(y, x)``."""
+    ``ldiv_(y, x)``.  Complex operators always run through it: ``tol``, ``residual`` and the beta of :50 are real, alpha and rho
+    complex scalars of the element type (numpy's scalar arithmetic).  ``ops``: where mul_ / dot / norm come from (this module; a host
+    double of the device types supplies its own)."""
 
-    def __init__(self, A, x, b, statevars, Pl, *, abstol, reltol, maxiter, initially_zero):
+    def __init__(self, A, x, b, statevars, Pl, *, abstol, reltol, maxiter, initially_zero, ops=None):
         self.A, self.x, self.Pl = A, x, Pl
         self.u, self.r, self.c = statevars.u, statevars.r, statevars.c
-        T = x.dtype.type
+        self.ops = ops = DeviceKrylovOps if ops is None else ops
+        mul_, norm = ops.mul_, ops.norm
+        T = _real_dtype(x.dtype).type
         self.u.fill_(0)                                                  # src/cg.jl:129
         self.r.copyto_(b)                                                # :130
         if initially_zero:
@@ -822,7 +855,7 @@ class GenericCGIterable:
         self.residual = norm(self.r)                                     # :140
         self.tol = max(T(reltol) * self.residual, T(abstol))             # :141
         self.prev_residual = T(1)
-        self.rho = T(1)
+        self.rho = x.dtype.type(1)
         self.maxiter = int(maxiter)
         self.pcg = not isinstance(Pl, Identity)
 
@@ -839,6 +872,7 @@ class GenericCGIterable:
         iteration = 0 if iteration is None else iteration
         if self.done(iteration):
             return None
+        mul_, dot, norm = self.ops.mul_, self.ops.dot, self.ops.norm
         if not self.pcg:
             beta = self.residual * self.residual / (self.prev_residual * self.prev_residual)   # :50
             self.u.xpby_(self.r, beta)                                   # :51
@@ -874,17 +908,19 @@ def _default_reltol(b: HipVector) -> float:
 
 
 def cg_iterator_(x: HipVector, A: HipCSR, b: HipVector, Pl=None, *, abstol=0.0, reltol=None, maxiter=None,
-                 statevars: Optional[CGStateVariables] = None, initially_zero: bool = False, fused: bool = True):
-    """``cg_iterator!(x, A, b, Pl; ...)`` -- src/cg.jl:120-155."""
+                 statevars: Optional[CGStateVariables] = None, initially_zero: bool = False, fused: bool = True, ops=None):
+    """``cg_iterator!(x, A, b, Pl; ...)`` -- src/cg.jl:120-155.  ``ops``: the L1 entries of the generic iterable (``DeviceKrylovOps``
+    by default; given: the generic iterable over them, whatever ``fused`` says)."""
     Pl = Identity() if Pl is None else Pl
     reltol = _default_reltol(b) if reltol is None else reltol
     maxiter = A.size(2) if maxiter is None else maxiter
     if statevars is None:
         statevars = CGStateVariables(x.zero(), x.similar(), x.similar())  # :124
     kw = dict(abstol=abstol, reltol=reltol, maxiter=maxiter, initially_zero=initially_zero)
-    if fused:
+    _refuse_complex_jacobi(A.dtype, Pl)
+    if fused and ops is None and not _is_complex(A.dtype):               # complex: the L1 form whatever `fused` says (no fused complex handles)
         return CGIterable(A, x, b, statevars, Pl, **kw)
-    return GenericCGIterable(A, x, b, statevars, Pl, **kw)
+    return GenericCGIterable(A, x, b, statevars, Pl, ops=ops, **kw)
 
 
 def cg_(x: HipVector, A: HipCSR, b: HipVector, *, abstol=0.0, reltol=None, maxiter=None, log: bool = False,
@@ -958,7 +994,7 @@ def orthogonalize_and_normalize_(V, k: int, w: HipVector, h: np.ndarray, method=
     if w.n != V.n or w.dtype != V.dtype or k > V.cols:
         raise ValueError("DimensionMismatch in orthogonalize_and_normalize_")
     hh = np.zeros(max(k, 1), V.dtype)
-    nrm = np.zeros(1, V.dtype)
+    nrm = np.zeros(1, _real_dtype(V.dtype))                                # norm(w) is real, also for a complex basis
     check(lib().mik_orthogonalize(V.ctx.handle, dtype_code(V.dtype), V.n, int(k), _vp(V.buf.ptr), V.ld, _vp(w.ptr),
                                   hh.ctypes.data_as(_vp), nrm.ctypes.data_as(_vp), method.code), "mik_orthogonalize", V.ctx.handle)
     h[:k] = hh[:k]
@@ -976,6 +1012,7 @@ def gemv_n_(y: HipVector, V: HipMatrix, k: int, c: np.ndarray, alpha=1.0, col0: 
 
 def gemv_t_(V: HipMatrix, k: int, w: HipVector, col0: int = 0) -> np.ndarray:
     """``adjoint(view(V, :, col0+1 : col0+k)) * w`` -- src/orthogonalize.jl:15, one column of src/bicgstabl.jl:121."""
+    _lib.real_dtype_code(V.dtype, "gemv_t")
     h = np.zeros(max(k, 1), V.dtype)
     check(lib().mik_gemv_t(V.ctx.handle, dtype_code(V.dtype), V.n, int(k), _vp(V.col(col0).ptr), V.ld, _vp(w.ptr), h.ctypes.data_as(_vp)),
           "mik_gemv_t", V.ctx.handle)
@@ -984,6 +1021,7 @@ def gemv_t_(V: HipMatrix, k: int, w: HipVector, col0: int = 0) -> np.ndarray:
 
 def gram_(V: HipMatrix, k: int, col0: int = 0) -> np.ndarray:
     """``adjoint(V[:, col0+1 : col0+k]) * V[:, col0+1 : col0+k]`` in one pass (k <= 5) -- src/bicgstabl.jl:120."""
+    _lib.real_dtype_code(V.dtype, "gram")
     M = np.zeros((k, k), V.dtype, order="F")
     check(lib().mik_gram(V.ctx.handle, dtype_code(V.dtype), V.n, int(k), _vp(V.col(col0).ptr), V.ld, M.ctypes.data_as(_vp)),
           "mik_gram", V.ctx.handle)
@@ -1101,9 +1139,150 @@ class GMRESIterable:
             pass
 
 
+class DeviceKrylovOps:
+    """The L1 / L2 entries ``GenericCGIterable`` and ``GenericGMRESIterable`` are spelled with, on the device types of this module."""
+    mul_ = staticmethod(mul_)
+    dot = staticmethod(dot)
+    norm = staticmethod(norm)
+    orthogonalize_and_normalize_ = staticmethod(orthogonalize_and_normalize_)
+    gemv_n_ = staticmethod(gemv_n_)
+    hessenberg_ldiv_ = staticmethod(hessenberg_ldiv_)
+
+    @staticmethod
+    def basis(x: HipVector, cols: int) -> HipMatrix:                      # zeros(T, size(A, 1), order + 1), src/gmres.jl:13
+        return HipMatrix(x.n, cols, x.dtype, x.ctx)
+
+
+class GenericGMRESIterable:
+    """``GMRESIterable`` and its ``iterate`` (src/gmres.jl:57-136, 224-304) spelled with the L1 / L2 entry points only: the Arnoldi
+    basis ``V`` on the device (mul_, orthogonalize_and_normalize_, gemv_n_), ``H``, the Givens least squares and the null-vector
+    residual recurrence on the host.  What complex operators run through (the fused ``mik_gmres`` handle is real only); it serves real
+    element types as well.  ``Pl`` / ``Pr``: ``Identity`` or any object with ``ldiv_(y, x)`` (y may alias x)."""
+
+    def __init__(self, x, A, b, *, abstol, reltol, restart, maxiter, initially_zero, orth_meth, Pl=None, Pr=None, ops=None):
+        if x.n != A.n_rows or b.n != A.n_rows or A.n_rows != A.n_cols or x.dtype != A.dtype or b.dtype != A.dtype:
+            raise ValueError("DimensionMismatch in gmres_iterable_")
+        self.ops = DeviceKrylovOps if ops is None else ops
+        self.A, self.x, self.b = A, x, b
+        self.Pl = Identity() if Pl is None else Pl
+        self.Pr = Identity() if Pr is None else Pr
+        self.restart, self.maxiter, self.orth_meth = int(restart), int(maxiter), orth_meth
+        self.T, self.RT = x.dtype.type, _real_dtype(x.dtype).type
+        self.V = self.ops.basis(x, self.restart + 1)                       # ArnoldiDecomp, :11-15
+        self.H = np.zeros((self.restart + 1, self.restart), x.dtype, order="F")
+        self.nullvec = np.ones(self.restart + 1, x.dtype)                  # Residual, :24-29
+        self.accumulator = self.RT(1)
+        self.residual_beta = self.RT(1)
+        self.mv_products = 1 if initially_zero else 0                      # :122 (as the reference counts)
+        self.Ax = x.similar()                                              # :125
+        self.residual_current = self._init(initially_zero)                 # :126
+        self._init_residual(self.residual_current)                         # :127
+        self.tol = max(self.RT(reltol) * self.residual_current, self.RT(abstol))   # :129
+        self.k = 1
+        self.beta = self.residual_current
+
+    def _ldiv(self, P, y, x=None):
+        if isinstance(P, Identity):
+            return P.ldiv_(y, x)
+        return P.ldiv_(y, y if x is None else x)
+
+    def _init(self, initially_zero):                                       # init!, :235-255
+        first_col = self.V.col(0)
+        first_col.copyto_(self.b)                                          # :241
+        if not initially_zero:
+            self.ops.mul_(self.Ax, self.A, self.x)                         # :245
+            first_col.sub_(self.Ax)                                        # :246
+        self._ldiv(self.Pl, first_col)                                     # :249
+        beta = self.ops.norm(first_col)                                    # :252
+        first_col.scal_(self.RT(1) / beta)                                 # :253
+        return beta
+
+    def _init_residual(self, beta):                                        # :257-260
+        self.accumulator = self.RT(1)
+        self.residual_beta = beta
+
+    def _expand(self):                                                     # expand!, :285-304
+        cur, nxt = self.V.col(self.k - 1), self.V.col(self.k)
+        if isinstance(self.Pr, Identity):
+            self.ops.mul_(nxt, self.A, cur)                                # :287 / :293
+            if not isinstance(self.Pl, Identity):
+                self._ldiv(self.Pl, nxt)                                   # :294
+        else:
+            self._ldiv(self.Pr, nxt, cur)                                  # :300
+            self.ops.mul_(self.Ax, self.A, nxt)                            # :301
+            nxt.copyto_(self.Ax)                                           # :302
+            self._ldiv(self.Pl, nxt)                                       # :303
+
+    def _update_residual(self):                                            # update_residual!, :224-233
+        k, H, nv = self.k, self.H, self.nullvec
+        if H[k, k - 1] == 0:
+            self.residual_current = self.RT(0)
+            return
+        d = self.T(0)
+        for i in range(k):                                                 # dot(view(nullvec, 1:k), view(H, 1:k, k))
+            d = d + np.conj(nv[i]) * H[i, k - 1]
+        nv[k] = -np.conj(d / H[k, k - 1])                                  # :229
+        a = nv[k]
+        self.accumulator = self.accumulator + (a.real * a.real + a.imag * a.imag)   # abs2, :230
+        self.residual_current = self.residual_beta / np.sqrt(self.accumulator)      # :231
+
+    def converged(self) -> bool:                                           # :51
+        return self.residual_current <= self.tol
+
+    def start(self) -> int:
+        return 0
+
+    def done(self, iteration: int) -> bool:                                # :55
+        return iteration >= self.maxiter or self.converged()
+
+    def iterate(self, iteration: Optional[int] = None):                    # :57-106
+        iteration = 0 if iteration is None else iteration
+        if self.done(iteration):
+            return None
+        self._expand()                                                     # :64
+        self.mv_products += 1
+        k = self.k
+        h = np.zeros(k, self.V.dtype)
+        nrm = self.ops.orthogonalize_and_normalize_(self.V, k, self.V.col(k), h, self.orth_meth)   # :68-73
+        self.H[:k, k - 1] = h
+        self.H[k, k - 1] = nrm
+        self._update_residual()                                            # :76
+        self.k += 1
+        if self.k == self.restart + 1 or self.done(iteration + 1):         # :82
+            k = self.k
+            rhs = np.zeros(k, self.V.dtype)                                # solve_least_squares!, :262-271
+            rhs[0] = self.beta
+            Hk = np.asfortranarray(self.H[:k, :k - 1])
+            self.ops.hessenberg_ldiv_(Hk, rhs)
+            y = rhs[:k - 1]
+            if isinstance(self.Pr, Identity):                              # update_solution!, :273-283
+                self.ops.gemv_n_(self.x, self.V, k - 1, y, self.T(1))      # :275
+            else:
+                self.Ax.fill_(0)
+                self.ops.gemv_n_(self.Ax, self.V, k - 1, y, self.T(1))     # :280
+                self._ldiv(self.Pr, self.Ax)                               # :281
+                self.x.axpy_(self.RT(1), self.Ax)                          # :282
+            self.k = 1
+            if not self.done(iteration):                                   # :93 (the reference asks done(g, iteration))
+                self.beta = self._init(False)                              # :96
+                self._init_residual(self.beta)                             # :99
+                self.mv_products += 1
+        return self.residual_current, iteration + 1
+
+    def __iter__(self):
+        iteration = 0
+        while True:
+            nxt = self.iterate(iteration)
+            if nxt is None:
+                return
+            residual, iteration = nxt
+            yield residual
+
+
 def gmres_iterable_(x: HipVector, A: HipCSR, b: HipVector, *, Pl=None, Pr=None, abstol=0.0, reltol=None, restart=None,
-                    maxiter=None, initially_zero: bool = False, orth_meth: Optional[OrthogonalizationMethod] = None):
-    """``gmres_iterable!(x, A, b; ...)`` -- src/gmres.jl:108-136."""
+                    maxiter=None, initially_zero: bool = False, orth_meth: Optional[OrthogonalizationMethod] = None, ops=None):
+    """``gmres_iterable!(x, A, b; ...)`` -- src/gmres.jl:108-136.  ``ops``: the L1 / L2 entries of ``GenericGMRESIterable``
+    (``DeviceKrylovOps`` by default; given: that iterable over them)."""
     for P, name in ((Pl, "Pl"), (Pr, "Pr")):
         if P is not None and not isinstance(P, (Identity, JacobiPrec)) and not callable(getattr(P, "ldiv_", None)):
             raise MikError(5, "gmres_iterable_", f"{name} needs ldiv_(y, x) (docs/src/preconditioning.md:5-14)")
@@ -1111,12 +1290,16 @@ def gmres_iterable_(x: HipVector, A: HipCSR, b: HipVector, *, Pl=None, Pr=None, 
     restart = min(20, A.size(2)) if restart is None else restart           # :113
     maxiter = A.size(2) if maxiter is None else maxiter                    # :114
     orth_meth = ModifiedGramSchmidt() if orth_meth is None else orth_meth  # :116
+    if _is_complex(A.dtype) or ops is not None:                            # no fused complex handle: the iterable over the L1 / L2 entries
+        _refuse_complex_jacobi(A.dtype, Pl, Pr)
+        return GenericGMRESIterable(x, A, b, abstol=abstol, reltol=reltol, restart=restart, maxiter=maxiter, initially_zero=initially_zero,
+                                    orth_meth=orth_meth, Pl=Pl, Pr=Pr, ops=ops)
     return GMRESIterable(x, A, b, abstol=abstol, reltol=reltol, restart=restart, maxiter=maxiter, initially_zero=initially_zero,
                          orth_meth=orth_meth, Pl=Pl, Pr=Pr)
 
 
 def gmres_(x: HipVector, A: HipCSR, b: HipVector, *, Pl=None, Pr=None, abstol=0.0, reltol=None, restart=None, maxiter=None,
-           log: bool = False, initially_zero: bool = False, verbose: bool = False, orth_meth=None):
+           log: bool = False, initially_zero: bool = False, verbose: bool = False, orth_meth=None, ops=None):
     """``gmres!(x, A, b; ...)`` -> ``x`` or ``(x, history)`` -- src/gmres.jl:184-222."""
     reltol = _default_reltol(b) if reltol is None else reltol
     restart = min(20, A.size(2)) if restart is None else restart
@@ -1127,7 +1310,7 @@ def gmres_(x: HipVector, A: HipCSR, b: HipVector, *, Pl=None, Pr=None, abstol=0.
     if log:
         history.reserve_("resnorm", maxiter)                               # :198
     iterable = gmres_iterable_(x, A, b, Pl=Pl, Pr=Pr, abstol=abstol, reltol=reltol, maxiter=maxiter, restart=restart,
-                               initially_zero=initially_zero, orth_meth=orth_meth)
+                               initially_zero=initially_zero, orth_meth=orth_meth, ops=ops)
     if verbose:
         print("=== gmres ===\n%4s\t%4s\t%7s" % ("rest", "iter", "resnorm"))
     for iteration, residual in enumerate(iterable, start=1):               # :207
@@ -1291,6 +1474,7 @@ class BiCGStabIterable:
 def bicgstabl_iterator_(x: HipVector, A: HipCSR, b: HipVector, l: int = 2, *, Pl=None, max_mv_products=None, abstol=0.0,
                         reltol=None, initial_zero: bool = False, r_shadow: Optional[HipVector] = None, fused: bool = True):
     """``bicgstabl_iterator!(x, A, b, l; ...)`` -- src/bicgstabl.jl:25-73."""
+    _lib.real_dtype_code(b.dtype, "bicgstabl_iterator")
     reltol = _default_reltol(b) if reltol is None else reltol
     max_mv_products = A.size(2) if max_mv_products is None else max_mv_products
     return BiCGStabIterable(x, A, b, l, Pl=Pl, max_mv_products=max_mv_products, abstol=abstol, reltol=reltol,
@@ -1334,10 +1518,11 @@ def bicgstabl(A: HipCSR, b: HipVector, l: int = 2, **kwargs):
 # chebyshev.jl, minres.jl  (composed from the L1 entry points)
 # ==============================================================================================
 def givens_algorithm(f, g, dtype=np.float64):
-    """``LinearAlgebra.givensAlgorithm(f, g)`` -> (c, s, r) on the host -- src/minres.jl:129."""
+    """``LinearAlgebra.givensAlgorithm(f, g)`` -> (c, s, r) on the host -- src/minres.jl:129, src/hessenberg.jl:24 (complex: c is
+    real, ``[c s; -conj(s) c] * [f; g] = [r; 0]``)."""
     fa, ga, out = np.asarray([f], dtype), np.asarray([g], dtype), np.zeros(3, dtype)
     check(lib().mik_givens(dtype_code(dtype), fa.ctypes.data_as(_vp), ga.ctypes.data_as(_vp), out.ctypes.data_as(_vp)), "mik_givens", None)
-    return out[0], out[1], out[2]
+    return (out[0].real if _is_complex(dtype) else out[0]), out[1], out[2]
 
 
 class ChebyshevIterable:
@@ -1424,6 +1609,7 @@ class ChebyshevIterable:
 
 def chebyshev_iterable_(x, A, b, lmin, lmax, *, abstol=0.0, reltol=None, maxiter=None, Pl=None, initially_zero=False, fused=True):
     """``chebyshev_iterable!`` -- src/chebyshev.jl:59-91."""
+    _lib.real_dtype_code(b.dtype, "chebyshev_iterable")
     return ChebyshevIterable(x, A, b, lmin, lmax, abstol=abstol, reltol=_default_reltol(b) if reltol is None else reltol,
                              maxiter=A.size(2) if maxiter is None else maxiter, Pl=Pl, initially_zero=initially_zero, fused=fused)
 
@@ -1588,6 +1774,7 @@ class MINRESIterable:
 
 def minres_iterable_(x, A, b, *, initially_zero=False, skew_hermitian=False, abstol=0.0, reltol=None, maxiter=None, fused=True):
     """``minres_iterable!`` -- src/minres.jl:38-87."""
+    _lib.real_dtype_code(b.dtype, "minres_iterable")
     return MINRESIterable(x, A, b, initially_zero=initially_zero, skew_hermitian=skew_hermitian, abstol=abstol,
                           reltol=_default_reltol(b) if reltol is None else reltol, maxiter=A.size(2) if maxiter is None else maxiter,
                           fused=fused)

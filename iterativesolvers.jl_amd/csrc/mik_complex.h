@@ -1,0 +1,27 @@
+// mik_complex.h -- the complex element types (MIK_C64 / MIK_C32: interleaved re, im) behind the L1 / L2 entries that cg and gmres
+// on a CSR operator need.  The entries of include/mik.h forward here when they see a complex code; everything
+// else of the library keeps refusing it.  Kernels: csrc/mik_complex.hip.
+#pragma once
+#include "mik_internal.h"
+
+
+// mik_csr_create with a complex dtype: host transpose + validation, the operator runs on its CSR arrays (rows longer than
+// MIK_LONG_ROW entries are listed as wave segments).  on_device: the three arrays are device memory and are staged on the host.
+int mik_c_csr_create(mik_ctx *ctx, int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t *ptr, const int64_t *idx,
+                     const void *val, int index_base, int is_csc, bool on_device, mik_csr **out);
+int mik_c_spmv(mik_ctx *ctx, const mik_csr *A, const void *x, void *y);
+const char *mik_c_spmv_kernel_name(const mik_csr *A);
+int64_t mik_c_stored_bytes(const mik_csr *A);
+int mik_c_time_spmv(mik_ctx *ctx, const mik_csr *A, const void *x, void *y, int reps, double *avg_ms);
+
+int mik_c_dot(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void *y, void *out);
+int mik_c_fill(mik_ctx *ctx, int dtype, int64_t n, const void *value, void *x);
+// scalar: a host complex of `dtype` (the real-scalar forms are the real sweeps over 2 n and never come here)
+int mik_c_axpy(mik_ctx *ctx, int dtype, int64_t n, const void *alpha, const void *x, void *y);
+int mik_c_xpby(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void *beta, void *y);
+int mik_c_scal(mik_ctx *ctx, int dtype, int64_t n, const void *alpha, void *x);
+int mik_c_orthogonalize(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv, void *w, void *h, void *nrm, int method);
+int mik_c_gemv_n(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv, const void *c, const void *alpha, void *y);
+// host
+int mik_c_givens(int dtype, const void *f, const void *g, void *out);
+int mik_c_hessenberg_ldiv(int dtype, void *H, int64_t ldh, int width, void *rhs);

@@ -8,6 +8,7 @@
 
 #include "mik_kernels.h"
 #include "mik_spmv.h"
+#include "mik_complex.h"
 #include <algorithm>
 #include <mutex>
 
@@ -250,8 +251,8 @@ extern "C" int mik_dev_xwin_plan(int64_t n_blocks, const int *first_col, const i
 
 extern "C" int mik_reduce_shape(int dtype, int *W, int *L)
 {
-    if (dtype != MIK_F64 && dtype != MIK_F32) return MIK_ERR_INVALID;
-    if (W) *W = dtype == MIK_F64 ? VT<double>::W : VT<float>::W;
+    if (dtype != MIK_F64 && dtype != MIK_F32 && !mik_is_complex(dtype)) return MIK_ERR_INVALID;
+    if (W) *W = (int)(16 / mik_dtype_size(dtype));         // complex: the segment of the 2 n interleaved reals, counted in elements
     if (L) *L = MIK_RED_L;
     return MIK_OK;
 }
@@ -312,6 +313,7 @@ template <typename T> static int fill_impl(mik_ctx *ctx, int64_t n, const void *
 extern "C" int mik_fill(mik_ctx *ctx, int dtype, int64_t n, const void *value, void *x)
 {
     if (!ctx || n < 0 || !value || (n && !x)) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype)) return mik_c_fill(ctx, dtype, n, value, x);
     return dtype == MIK_F64 ? fill_impl<double>(ctx, n, value, x) : fill_impl<float>(ctx, n, value, x);
 }
 
@@ -884,7 +886,7 @@ extern "C" int mik_csr_create(mik_ctx *ctx, int dtype, int64_t n_rows, int64_t n
 {
     if (!ctx || !out) return MIK_ERR_INVALID;
     *out = nullptr;
-    if (dtype != MIK_F64 && dtype != MIK_F32) return mik_fail(ctx, MIK_ERR_INVALID, "mik_csr_create: bad dtype %d", dtype);
+    if (dtype != MIK_F64 && dtype != MIK_F32 && !mik_is_complex(dtype)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_csr_create: bad dtype %d", dtype);
     if (n_rows < 0 || n_cols < 0 || nnz < 0 || !ptr || (nnz && (!idx || !val)))
         return mik_fail(ctx, MIK_ERR_INVALID, "mik_csr_create: bad sizes or NULL arrays");
     if (n_rows >= (int64_t)INT32_MAX - MIK_BLOCK || n_cols >= INT32_MAX || nnz >= (int64_t)INT32_MAX - 2 * MIK_SPMV_TILE)
@@ -895,6 +897,7 @@ extern "C" int mik_csr_create(mik_ctx *ctx, int dtype, int64_t n_rows, int64_t n
     const bool dev_in = is_device_pointer(ptr);
     if (nnz && (is_device_pointer(idx) != dev_in || is_device_pointer(val) != dev_in))
         return mik_fail(ctx, MIK_ERR_INVALID, "mik_csr_create: ptr / idx / val must all be host arrays or all device arrays");
+    if (mik_is_complex(dtype)) return mik_c_csr_create(ctx, dtype, n_rows, n_cols, nnz, ptr, idx, val, index_base, is_csc, dev_in, out);
     if (!dev_in) return csr_create_impl(ctx, dtype, n_rows, n_cols, nnz, ptr, idx, val, index_base, is_csc, false, out);
     int rc = csr_create_impl(ctx, dtype, n_rows, n_cols, nnz, ptr, idx, val, index_base, is_csc, true, out);
     if (rc != MIK_ERR_NOTIMPL) return rc;
@@ -924,7 +927,7 @@ extern "C" int mik_csr_create_i32(mik_ctx *ctx, int dtype, int64_t n_rows, int64
     if (!ctx || !out) return MIK_ERR_INVALID;
     *out = nullptr;
     if (n_rows < 0 || n_cols < 0 || nnz < 0 || !ptr || (nnz && (!idx || !val))) return mik_fail(ctx, MIK_ERR_INVALID, "mik_csr_create_i32: bad sizes or NULL arrays");
-    if (dtype != MIK_F64 && dtype != MIK_F32) return mik_fail(ctx, MIK_ERR_INVALID, "mik_csr_create_i32: bad dtype %d", dtype);
+    if (dtype != MIK_F64 && dtype != MIK_F32 && !mik_is_complex(dtype)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_csr_create_i32: bad dtype %d", dtype);
     const int64_t n_major = is_csc ? n_cols : n_rows;
     (void)hipSetDevice(ctx->device);
     const bool dev_in = is_device_pointer(ptr);
@@ -1353,6 +1356,7 @@ extern "C" int mik_csr_stored_bytes(const mik_csr *A, int64_t *bytes)
     if (!A || !bytes) return MIK_ERR_INVALID;
     const int64_t es = (int64_t)mik_dtype_size(A->dtype);
     const int64_t nb = (A->n_rows + MIK_BLOCK - 1) / MIK_BLOCK;
+    if (mik_is_complex(A->dtype)) { *bytes = mik_c_stored_bytes(A); return MIK_OK; }
     switch (spmv_kernel_choice(A)) {
     case LAYOUT_SDIAC: *bytes = A->n_rows + nb * (spmv_sdiab_usable(A) ? 64 : 4) + (int64_t)A->sdia_npat * (80 + 8 * es); break;
     case LAYOUT_SDIAW: *bytes = A->n_rows * 4 + nb * 4 + (nb + 1) / 2 * 64 + (int64_t)A->sdiaw_npat * A->sdiaw_pat_bytes; break;
@@ -1557,6 +1561,7 @@ bool mik_spmv_is_light(const mik_csr *A) { return A && (spmv_kernel_choice(A) ==
 extern "C" int mik_spmv_kernel(const mik_csr *A, char *name, int len)
 {
     if (!A || !name || len <= 0) return MIK_ERR_INVALID;
+    if (mik_is_complex(A->dtype)) { snprintf(name, (size_t)len, "%s", mik_c_spmv_kernel_name(A)); return MIK_OK; }
     snprintf(name, (size_t)len, "%s", spmv_kernel_name(spmv_plan_whole(A, false)));
     return MIK_OK;
 }
@@ -1578,6 +1583,7 @@ extern "C" int mik_dev_spmv_plan(const mik_csr *A, const void *x, int fuse_dot, 
                                  int len, int64_t *grid, int *launches, int *pre_longrows, int *post_rowdot)
 {
     if (!A || (kernel_name && len <= 0)) return MIK_ERR_INVALID;
+    MIK_REFUSE_COMPLEX(A->ctx, A, "mik_dev_spmv_plan");
     const bool armed = spmv_ep_armed(A->ctx);
     SpmvPlan p[2];
     int np = 1;
@@ -1816,6 +1822,7 @@ extern "C" int mik_spmv(mik_ctx *ctx, const mik_csr *A, const void *x, void *y)
 {
     if (!ctx || !A || !x || !y) return MIK_ERR_INVALID;
     if (x == y) return mik_fail(ctx, MIK_ERR_INVALID, "mik_spmv: x and y must not alias");
+    if (mik_is_complex(A->dtype)) return mik_c_spmv(ctx, A, x, y);
     return A->dtype == MIK_F64 ? mik_spmv_launch<double>(ctx, A, (const double *)x, (double *)y, false, nullptr, nullptr)
                                : mik_spmv_launch<float>(ctx, A, (const float *)x, (float *)y, false, nullptr, nullptr);
 }
@@ -1846,6 +1853,7 @@ static int time_spmv_impl(mik_ctx *ctx, const mik_csr *A, const void *x, void *y
 extern "C" int mik_time_spmv(mik_ctx *ctx, const mik_csr *A, const void *x, void *y, int fused_dot, int reps, double *avg_ms)
 {
     if (!ctx || !A || !x || !y || reps <= 0 || !avg_ms) return MIK_ERR_INVALID;
+    if (mik_is_complex(A->dtype)) return mik_c_time_spmv(ctx, A, x, y, reps, avg_ms);        // (no fused dot for complex operators)
     return A->dtype == MIK_F64 ? time_spmv_impl<double>(ctx, A, x, y, fused_dot, reps, avg_ms)
                                : time_spmv_impl<float>(ctx, A, x, y, fused_dot, reps, avg_ms);
 }
@@ -1914,18 +1922,22 @@ template <typename T> static int dot_impl(mik_ctx *ctx, int64_t n, const void *x
 extern "C" int mik_dot(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void *y, void *out)
 {
     if (!ctx || n < 0 || !out || (n && (!x || !y))) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype)) return mik_c_dot(ctx, dtype, n, x, y, out);
     return dtype == MIK_F64 ? dot_impl<double>(ctx, n, x, y, out, false) : dot_impl<float>(ctx, n, x, y, out, false);
 }
 
 extern "C" int mik_nrm2(mik_ctx *ctx, int dtype, int64_t n, const void *x, void *out)
 {
     if (!ctx || n < 0 || !out || (n && !x)) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype)) return mik_nrm2(ctx, mik_real_dtype(dtype), 2 * n, x, out);      // by definition: the real norm over the 2 n interleaved reals
     return dtype == MIK_F64 ? dot_impl<double>(ctx, n, x, x, out, true) : dot_impl<float>(ctx, n, x, x, out, true);
 }
 
 extern "C" int mik_axpy(mik_ctx *ctx, int dtype, int64_t n, const void *alpha, const void *x, void *y)
 {
     if (!ctx || n < 0 || !alpha || (n && (!x || !y))) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype & ~MIK_SCALAR_REAL))      // a real scalar: real * complex is the real sweep over the 2 n interleaved reals
+        return (dtype & MIK_SCALAR_REAL) ? mik_axpy(ctx, mik_real_dtype(dtype & ~MIK_SCALAR_REAL), 2 * n, alpha, x, y) : mik_c_axpy(ctx, dtype, n, alpha, x, y);
     const bool vec = mik_aligned16(x) && mik_aligned16(y);
     if (dtype == MIK_F64) { OpAxpy<double> op{(const double *)x, (double *)y, coef_val(*(const double *)alpha)}; return launch_map<double>(ctx, n, op, vec, (double *)nullptr, nullptr); }
     if (dtype == MIK_F32) { OpAxpy<float> op{(const float *)x, (float *)y, coef_val(*(const float *)alpha)}; return launch_map<float>(ctx, n, op, vec, (float *)nullptr, nullptr); }
@@ -1935,6 +1947,8 @@ extern "C" int mik_axpy(mik_ctx *ctx, int dtype, int64_t n, const void *alpha, c
 extern "C" int mik_xpby(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void *beta, void *y)
 {
     if (!ctx || n < 0 || !beta || (n && (!x || !y))) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype & ~MIK_SCALAR_REAL))
+        return (dtype & MIK_SCALAR_REAL) ? mik_xpby(ctx, mik_real_dtype(dtype & ~MIK_SCALAR_REAL), 2 * n, x, beta, y) : mik_c_xpby(ctx, dtype, n, x, beta, y);
     const bool vec = mik_aligned16(x) && mik_aligned16(y);
     if (dtype == MIK_F64) { OpXpby<double> op{(const double *)x, (double *)y, coef_val(*(const double *)beta)}; return launch_map<double>(ctx, n, op, vec, (double *)nullptr, nullptr); }
     if (dtype == MIK_F32) { OpXpby<float> op{(const float *)x, (float *)y, coef_val(*(const float *)beta)}; return launch_map<float>(ctx, n, op, vec, (float *)nullptr, nullptr); }
@@ -1944,6 +1958,7 @@ extern "C" int mik_xpby(mik_ctx *ctx, int dtype, int64_t n, const void *x, const
 extern "C" int mik_sub(mik_ctx *ctx, int dtype, int64_t n, const void *x, void *y)
 {
     if (!ctx || n < 0 || (n && (!x || !y))) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype)) return mik_sub(ctx, mik_real_dtype(dtype), 2 * n, x, y);
     const bool vec = mik_aligned16(x) && mik_aligned16(y);
     if (dtype == MIK_F64) { OpSub<double> op{(const double *)x, (double *)y}; return launch_map<double>(ctx, n, op, vec, (double *)nullptr, nullptr); }
     if (dtype == MIK_F32) { OpSub<float> op{(const float *)x, (float *)y}; return launch_map<float>(ctx, n, op, vec, (float *)nullptr, nullptr); }
@@ -1953,6 +1968,8 @@ extern "C" int mik_sub(mik_ctx *ctx, int dtype, int64_t n, const void *x, void *
 extern "C" int mik_scal(mik_ctx *ctx, int dtype, int64_t n, const void *alpha, void *x)
 {
     if (!ctx || n < 0 || !alpha || (n && !x)) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype & ~MIK_SCALAR_REAL))
+        return (dtype & MIK_SCALAR_REAL) ? mik_scal(ctx, mik_real_dtype(dtype & ~MIK_SCALAR_REAL), 2 * n, alpha, x) : mik_c_scal(ctx, dtype, n, alpha, x);
     const bool vec = mik_aligned16(x);
     if (dtype == MIK_F64) { OpScal<double> op{(double *)x, coef_val(*(const double *)alpha)}; return launch_map<double>(ctx, n, op, vec, (double *)nullptr, nullptr); }
     if (dtype == MIK_F32) { OpScal<float> op{(float *)x, coef_val(*(const float *)alpha)}; return launch_map<float>(ctx, n, op, vec, (float *)nullptr, nullptr); }

@@ -314,6 +314,7 @@ extern "C" int mik_idrs_create(mik_ctx *ctx, const mik_csr *A, int s, void *x, v
     if (!ctx || !out) return MIK_ERR_INVALID;
     *out = nullptr;
     if (!A || A->ctx != ctx || A->n_rows != A->n_cols) return mik_fail(ctx, MIK_ERR_MISMATCH, "mik_idrs_create: A must be a square operator of this context");
+    MIK_REFUSE_COMPLEX(ctx, A, "mik_idrs_create");
     if (s < 1 || s > IDRS_MAX_S) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_idrs_create: s = %d (the device path takes 1 ... %d)", s, IDRS_MAX_S);
     const int64_t n = A->n_rows;
     if (n && (!x || !r || !P || !U || !G)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_idrs_create: NULL vector");

@@ -138,6 +138,8 @@ struct mik_csr {
     int sdia_koff = 0;               // - (most negative slot offset) of the operator, >= 0
     void *sdia_recs = nullptr;       // device, nb SdiaSliceRec (k_spmv_sdiab): scalar offsets + pattern shape per slice
     int sdia_cls = 0;                // (slots, centre slot) class k_spmv_sdiab runs specialised (mik_sdiab_cls_*), 0 = none
+    // complex operators (dtype MIK_C64 / MIK_C32, csrc/mik_complex.hip): CSR arrays only; long_rows = the wave-segment tables, seg_sum = one (re, im) per segment
+    int c_nlong = 0, c_nvirt = 0;    // rows longer than MIK_LONG_ROW entries, and the segments they are cut into
 };
 
 // norm(x) from t = sum of x_i^2: sqrt(t) whenever t lies inside [LO, HI] -- then no square that matters has
@@ -247,8 +249,19 @@ int mik_build_rperm_host(mik_ctx *ctx, mik_csr *A, const int *rowptr_host);   //
                             hipGetErrorString(e_), __FILE__, __LINE__);                       \
     } while (0)
 
+// complex element types (csrc/mik_complex.hip).  MIK_C64 -> MIK_F64, MIK_C32 -> MIK_F32: the type of a component, of norm(x) and of a
+// scalar passed with MIK_SCALAR_REAL
+static inline bool mik_is_complex(int dtype) { return dtype == MIK_C64 || dtype == MIK_C32; }
+static inline int mik_real_dtype(int dtype) { return dtype == MIK_C64 ? MIK_F64 : MIK_F32; }
+// a complex operator is served by mik_spmv and the operator queries only: every other entry with a mik_csr argument refuses it
+#define MIK_REFUSE_COMPLEX(ctx, A, who)                                                                                          \
+    do {                                                                                                                         \
+        if ((A) && mik_is_complex((A)->dtype))                                                                                   \
+            return mik_fail((ctx), MIK_ERR_NOTIMPL, "%s: complex operators run through mik_spmv and the L1 / L2 entries only", (who)); \
+    } while (0)
+
 static inline bool mik_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static inline size_t mik_dtype_size(int dtype) { return dtype == MIK_F64 ? 8 : 4; }
+static inline size_t mik_dtype_size(int dtype) { return dtype == MIK_C64 ? 16 : (dtype == MIK_F64 || dtype == MIK_C32) ? 8 : 4; }
 
 // number of level-1 segments of an n-vector for dtype T
 // number of SpMV workgroups (= fused-dot segment sums) for n rows

@@ -13,6 +13,7 @@
 
 #include "mik_kernels.h"
 #include "mik_mgs_res.h"
+#include "mik_complex.h"
 #include "mik_iter.h"
 #include "mik_mail.h"
 
@@ -76,6 +77,7 @@ template <typename T> static void hessenberg_ldiv(T *H, int64_t ldh, int width, 
 extern "C" int mik_hessenberg_ldiv(int dtype, void *H, int64_t ldh, int width, void *rhs)
 {
     if (!H || !rhs || width < 0 || ldh < width + 1) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype)) return mik_c_hessenberg_ldiv(dtype, H, ldh, width, rhs);
     if (dtype == MIK_F64) hessenberg_ldiv<double>((double *)H, ldh, width, (double *)rhs);
     else if (dtype == MIK_F32) hessenberg_ldiv<float>((float *)H, ldh, width, (float *)rhs);
     else return MIK_ERR_INVALID;
@@ -129,6 +131,7 @@ extern "C" int mik_gemv_n(mik_ctx *ctx, int dtype, int64_t n, int k, const void 
                           const void *alpha, void *y)
 {
     if (!ctx || n < 0 || k < 0 || !alpha || (k && !c) || (n && k && (!V || !y)) || ldv < n) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype)) return mik_c_gemv_n(ctx, dtype, n, k, V, ldv, c, alpha, y);
     if (dtype == MIK_F64) return gemv_n_impl<double>(ctx, n, k, V, ldv, c, alpha, y);
     if (dtype == MIK_F32) return gemv_n_impl<float>(ctx, n, k, V, ldv, c, alpha, y);
     return MIK_ERR_INVALID;
@@ -419,6 +422,7 @@ extern "C" int mik_orthogonalize(mik_ctx *ctx, int dtype, int64_t n, int k, cons
 {
     if (!ctx || n < 0 || k < 0 || !nrm || (k && (!h || !V)) || (n && !w) || (k && ldv < n)) return MIK_ERR_INVALID;
     if (method != MIK_MGS && method != MIK_CGS && method != MIK_DGKS) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype)) return mik_c_orthogonalize(ctx, dtype, n, k, V, ldv, w, h, nrm, method);
     if (dtype == MIK_F64) return gs_orthogonalize<double>(GsSums<double>(ctx, nullptr, n, k, (double *)h), (const double *)V, ldv, (double *)w, (double *)nrm, method);
     if (dtype == MIK_F32) return gs_orthogonalize<float>(GsSums<float>(ctx, nullptr, n, k, (float *)h), (const float *)V, ldv, (float *)w, (float *)nrm, method);
     return MIK_ERR_INVALID;
@@ -903,6 +907,7 @@ static int cg_create_common(mik_ctx *ctx, const mik_csr *A, int dtype, int64_t n
                             mik_ldiv_fn pl_fn, void *pl_user, void *x, const void *b, void *u, void *r, void *c, double abstol, double reltol,
                             int64_t maxiter, int initially_zero, mik_cg **out)
 {
+    MIK_REFUSE_COMPLEX(ctx, A, "mik_cg_create");
     if (n && (!x || !b || !u || !r || !c)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_cg_create: NULL vector");
     mik_cg *it = new (std::nothrow) mik_cg();
     if (!it) return mik_fail(ctx, MIK_ERR_NOMEM, "mik_cg_create: host allocation failed");
@@ -1300,6 +1305,7 @@ static int gmres_create_common(mik_ctx *ctx, const mik_csr *A, void *x, const vo
     if (!ctx || !out) return MIK_ERR_INVALID;
     *out = nullptr;
     if (!A && !(op && op->mul)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_gmres_create: NULL operator");
+    MIK_REFUSE_COMPLEX(ctx, A, "mik_gmres_create");
     if (A && !part && A->n_rows != A->n_cols) return mik_fail(ctx, MIK_ERR_MISMATCH, "mik_gmres_create: A must be square");
     if (part) {
         if (part->nranks < 1 || part->rank < 0 || part->rank >= part->nranks) return mik_fail(ctx, MIK_ERR_INVALID, "mik_gmres_create_partitioned: bad rank %d of %d", part->rank, part->nranks);
@@ -1872,6 +1878,7 @@ extern "C" int mik_cgd_create(mik_ctx *ctx, const mik_csr *A_loc, void *x, const
     if (!ctx || !out) return MIK_ERR_INVALID;
     *out = nullptr;
     if (!A_loc || A_loc->n_cols < A_loc->n_rows) return mik_fail(ctx, MIK_ERR_MISMATCH, "mik_cgd_create: local block must be n_loc x (n_loc + n_ghost)");
+    MIK_REFUSE_COMPLEX(ctx, A_loc, "mik_cgd_create");
     if (nranks < 1 || rank < 0 || rank >= nranks || !dot_all || !rr_all || (n_send && (!send_idx || !send_buf)))
         return mik_fail(ctx, MIK_ERR_INVALID, "mik_cgd_create: bad rank / comm buffers");
     const int64_t n = A_loc->n_rows;
@@ -2276,6 +2283,7 @@ extern "C" int mik_lu_solve(int dtype, void *A, int64_t lda, int n, void *b)
 extern "C" int mik_givens(int dtype, const void *f, const void *g, void *out)
 {
     if (!f || !g || !out) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype)) return mik_c_givens(dtype, f, g, out);
     if (dtype == MIK_F64) { double *o = (double *)out; givens_algorithm<double>(*(const double *)f, *(const double *)g, o[0], o[1], o[2]); return MIK_OK; }
     if (dtype == MIK_F32) { float *o = (float *)out; givens_algorithm<float>(*(const float *)f, *(const float *)g, o[0], o[1], o[2]); return MIK_OK; }
     return MIK_ERR_INVALID;

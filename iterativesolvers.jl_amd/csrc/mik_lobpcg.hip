@@ -118,6 +118,7 @@ int update_impl(mik_ctx *ctx, int64_t n, int sx, int b1, int b2, const T *X, int
 extern "C" int mik_spmm(mik_ctx *ctx, const mik_csr *A, int b, const void *X, int64_t ldx, void *Y, int64_t ldy)
 {
     if (!ctx || !A || b < 0) return MIK_ERR_INVALID;
+    MIK_REFUSE_COMPLEX(ctx, A, "mik_spmm");
     if (b > MIK_BLK_MAX) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_spmm: b = %d (at most %d columns)", b, MIK_BLK_MAX);
     if (b == 0) return MIK_OK;
     if (!X || !Y || ldx < A->n_cols || ldy < A->n_rows) return mik_fail(ctx, MIK_ERR_INVALID, "mik_spmm: null pointer or leading dimension too small");

@@ -197,6 +197,7 @@ extern "C" int mik_bicgstab_create(mik_ctx *ctx, const mik_csr *A, int l, void *
     if (!ctx || !out) return MIK_ERR_INVALID;
     *out = nullptr;
     if (!A || A->ctx != ctx || A->n_rows != A->n_cols) return mik_fail(ctx, MIK_ERR_MISMATCH, "mik_bicgstab_create: A must be a square operator of this context");
+    MIK_REFUSE_COMPLEX(ctx, A, "mik_bicgstab_create");
     if (l < 1 || l > 4) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_bicgstab_create: l = %d (1 ... 4; drive larger l through the L1 entry points)", l);
     const int64_t n = A->n_rows;
     if (n && (!x || !rs || !us || !r_shadow || ldr < n || ldu < n)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_bicgstab_create: NULL vector or leading dimension < n");
@@ -521,6 +522,7 @@ extern "C" int mik_minres_create(mik_ctx *ctx, const mik_csr *A, void *x, void *
     if (!ctx || !out) return MIK_ERR_INVALID;
     *out = nullptr;
     if (!A || A->ctx != ctx || A->n_rows != A->n_cols) return mik_fail(ctx, MIK_ERR_MISMATCH, "mik_minres_create: A must be a square operator of this context");
+    MIK_REFUSE_COMPLEX(ctx, A, "mik_minres_create");
     const int64_t n = A->n_rows;
     if (n && (!x || !v_prev || !v_curr || !v_next || !w_prev || !w_curr || !w_next)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_minres_create: NULL vector");
     mik_minres *it = new (std::nothrow) mik_minres();

@@ -282,6 +282,7 @@ extern "C" int mik_stationary_create(mik_ctx *ctx, const mik_csr *A, int64_t *si
     if (singular_col) *singular_col = 0;
     if (!ctx || !A || !out) return MIK_ERR_INVALID;
     *out = nullptr;
+    MIK_REFUSE_COMPLEX(ctx, A, "mik_stationary_create");
     if (A->n_rows != A->n_cols)
         return mik_fail(ctx, MIK_ERR_MISMATCH, "mik_stationary_create: the operator is %lld x %lld, not square", (long long)A->n_rows, (long long)A->n_cols);
     if (!A->col || !A->rowptr || !A->val)

@@ -36,7 +36,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import MikError, check, dtype_code, lib
+from ._lib import MikError, check, dtype_code, lib, real_dtype_code
 from .api import HipCSR, HipMatrix, Identity, JacobiPrec
 
 _vp = C.c_void_p
@@ -117,7 +117,7 @@ class DeviceOps:
         if A.n_rows != A.n_cols or (B is not None and (B.n_rows, B.n_cols, np.dtype(B.dtype)) != (A.n_rows, A.n_cols, np.dtype(A.dtype))):
             raise ValueError("DimensionMismatch: lobpcg needs square A and B of one size and element type")
         self.ctx, self.dtype, self.n = A.ctx, np.dtype(A.dtype), A.n_rows
-        self.code = dtype_code(self.dtype)
+        self.code = real_dtype_code(self.dtype, "lobpcg")
         for M in (A, B):
             if isinstance(M, HipMatrix):
                 M.reserve_block_()                                       # the partials of mik_dense_mm: allocated here, not in the loop

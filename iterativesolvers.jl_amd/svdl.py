@@ -34,7 +34,7 @@ import time
 import numpy as np
 
 from . import api
-from ._lib import MikError, check, dtype_code, lib
+from ._lib import MikError, check, dtype_code, lib, real_dtype_code
 from .api import ConvergenceHistory, HipCSR, HipMatrix, HipVector
 from .extras import with_adjoint, with_adjoint_from_scipy       # noqa: F401  (how an operator gets its adjoint)
 
@@ -158,7 +158,7 @@ class DeviceOps:
             raise MikError(5, "svdl", "this operator was uploaded without its adjoint: create it with extras.with_adjoint(...) / "
                                       "with_adjoint_from_scipy(m)")
         self.A, self.ctx, self.dtype = A, A.ctx, np.dtype(A.dtype)
-        self.code = dtype_code(self.dtype)
+        self.code = real_dtype_code(self.dtype, "svdl")
         self.m, self.n = A.n_rows, A.n_cols
 
     def matrix(self, rows, cols):
