@@ -796,10 +796,28 @@ int mik_block_update(mik_ctx *ctx, int dtype, int64_t n, int sx, int b1, int b2,
  * workgroups, the chunk partials combined in chunk order by a second small kernel.  T form: one sweep that reads every column once and
  * x once per workgroup pass, the segment sums through the segment toolkit and k_finalize_store.  No workgroup waits for another.
  * The handle owns the workspace of the chunk partials / segment sums (allocated once in create; nothing is allocated per call) and never
- * touches the context's reduction workspace, so the callbacks below may run in the middle of a fused CG / GMRES step. */
+ * touches the context's reduction workspace, so the callbacks below may run in the middle of a fused CG / GMRES step.
+ *
+ * Complex matrices (MIK_C64 / MIK_C32; added without a version bump, additive) -- Matrix{ComplexF64 / ComplexF32} of test/cg.jl:27,
+ * test/gmres.jl:16.  A is a DEVICE m x n column-major matrix of interleaved (re, im) elements; lda counts ELEMENTS; A, x and y need
+ * element alignment only (8 bytes for ComplexF32 and likewise 8 bytes for a ComplexF64 base).  mik_dense_mul, mik_dense_mul_fn and
+ * mik_dense_mul_adj_fn work on such a handle with the element arithmetic of the complex L1 entries; nothing is contracted.
+ *   y = A x    The same chunks of C ELEMENTS (one constant for all four element types).  p_c[i] is the serial sum from (+0, +0), over the
+ *              chunk's columns ascending, of the rounded product A[i,j] * x[j] = (ar xr - ai xi) + (ar xi + ai xr) i -- re and im each
+ *              their own chain -- then y[i] = ((p_0[i] + p_1[i]) + p_2[i]) + ... componentwise.  With n <= C this is Julia's generic
+ *              column-oriented mul!; with n <= min(C, mik_spmv_long_row()) it is mik_spmv on the same matrix stored fully, bit for bit.
+ *              The result depends on (m, n, dtype, C) only.
+ *   y = A' x   The conjugate transpose: y[j] equals the complex mik_dot(A[:, j], x) bit for bit -- per element re = ar xr + ai xi,
+ *              im = ar xi - ai xr, then one two-level tree of mik_reduce_shape(dtype) for re and one for im, through the same finaliser.
+ * Overlap, NULL and empty-dimension rules are those of the real codes (an empty sum is (+0, +0)).  mik_dense_mm and
+ * mik_dense_block_reserve answer a complex handle with MIK_ERR_NOTIMPL and a message that names the element type; a complex matrix of
+ * 2^30 columns or more is refused by mik_dense_create (MIK_ERR_NOTIMPL). */
 typedef struct mik_dense mik_dense;     /* opaque: (ctx, dtype, m, n, A, lda) + its own workspace */
 /* C (one compile-time constant for both dtypes, a power of two in [32, 256]) and the rows a workgroup of the N form owns. */
 int mik_dense_mul_shape(int *chunk, int *rows_per_workgroup);
+/* The same for any of the four element types: C is the same constant for all of them; the complex N form owns its own number of rows per
+ * workgroup.  MIK_F64 / MIK_F32 give what mik_dense_mul_shape gives.  MIK_ERR_INVALID for another code. */
+int mik_dense_mul_shape_for(int dtype, int *chunk, int *rows_per_workgroup);
 /* MIK_ERR_MISMATCH for lda < m; MIK_ERR_INVALID for a NULL argument; m = 0 or n = 0 is MIK_OK. */
 int mik_dense_create(mik_ctx *ctx, int dtype, int64_t m, int64_t n, const void *A, int64_t lda, mik_dense **out);
 int mik_dense_destroy(mik_dense *D);

@@ -227,6 +227,7 @@ SIGNATURES = {
     "mik_dense_sor_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
     "mik_dense_ssor_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
     "mik_dense_mul_shape": (C.c_int, [_ip, _ip]),
+    "mik_dense_mul_shape_for": (C.c_int, [C.c_int, _ip, _ip]),
     "mik_dense_create": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _i64, C.POINTER(_vp)]),
     "mik_dense_destroy": (C.c_int, [_vp]),
     "mik_dense_mul": (C.c_int, [_vp, C.c_int, _vp, _vp]),
@@ -307,7 +308,7 @@ def dtype_code(dtype) -> int:
 def real_dtype_code(dtype, who: str) -> int:
     """``dtype_code`` for the entries that stay real (everything but cg / gmres on a CSR operator and the L1 / L2 entries under them)."""
     if np.dtype(dtype).kind == "c":
-        raise TypeError(f"{who} is not offered for complex element types (DESIGN.md section 17: cg and gmres on a CSR operator are)")
+        raise TypeError(f"{who} is not offered for complex element types (DESIGN.md sections 17, 18: cg and gmres on a CSR or dense operator are)")
     return dtype_code(dtype)
 
 

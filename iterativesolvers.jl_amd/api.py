@@ -355,6 +355,7 @@ class HipMatrix:
     def mm_(self, Y: "HipMatrix", X: "HipMatrix", b: Optional[int] = None) -> "HipMatrix":
         """``mul!(Y[:, 1:b], A, X[:, 1:b])`` (src/lobpcg.jl:124-139 for ``A::Matrix``): every column has the bits of ``mul_`` on that
         column; the matrix is read once per group of columns (``mik_dense_mm``).  ``b`` defaults to the columns of ``X``; at most 32."""
+        self._refuse_complex_block("mm_")
         b = X.cols if b is None else int(b)
         if (X.n, Y.n) != (self.cols, self.n) or not 0 <= b <= min(X.cols, Y.cols) or not X.dtype == Y.dtype == self.dtype:
             raise ValueError(f"DimensionMismatch: mul!(Y, A, X) with A {self.n} x {self.cols}, X {X.n} x {X.cols}, Y {Y.n} x {Y.cols}, b = {b}")
@@ -364,8 +365,14 @@ class HipMatrix:
     def reserve_block_(self) -> "HipMatrix":
         """Allocate the workspace of ``mm_`` now (``mik_dense_block_reserve``): an iterator calls it when it is built, so that its loop allocates
         nothing."""
+        self._refuse_complex_block("reserve_block_")
         check(lib().mik_dense_block_reserve(self.dense), "mik_dense_block_reserve", self.ctx.handle)
         return self
+
+    def _refuse_complex_block(self, who: str) -> None:
+        """The block product is real only (``mik_dense_mm`` answers a complex handle with MIK_ERR_NOTIMPL): say so before the library does."""
+        if _is_complex(self.dtype):
+            raise TypeError(f"HipMatrix.{who}: the block product is not offered for a {self.dtype} matrix (lobpcg stays real; mul_ and A.adj serve it)")
 
     def __del__(self):
         try:

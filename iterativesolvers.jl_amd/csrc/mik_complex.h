@@ -4,6 +4,14 @@
 #pragma once
 #include "mik_internal.h"
 
+// z * w = (zr wr - zi wi) + (zr wi + zi wr) i: four rounded products, one rounded difference, one rounded sum (Base's definition)
+template <typename R> struct CxVal { R re, im; };
+
+template <typename R> __host__ __device__ __forceinline__ CxVal<R> cx_mul(R zr, R zi, R wr, R wi)
+{
+    const R a = zr * wr, b = zi * wi, c = zr * wi, d = zi * wr;
+    return CxVal<R>{a - b, c + d};
+}
 
 // mik_csr_create with a complex dtype: host transpose + validation, the operator runs on its CSR arrays (rows longer than
 // MIK_LONG_ROW entries are listed as wave segments).  on_device: the three arrays are device memory and are staged on the host.

@@ -21,14 +21,6 @@
 // =============================================================================================
 // element-wise sweeps over complex vectors
 // =============================================================================================
-template <typename R> struct CxVal { R re, im; };
-
-template <typename R> __host__ __device__ __forceinline__ CxVal<R> cx_mul(R zr, R zi, R wr, R wi)
-{
-    const R a = zr * wr, b = zi * wi, c = zr * wi, d = zi * wr;
-    return CxVal<R>{a - b, c + d};
-}
-
 // Op interface of k_cvec: which of the three operands are read (x, z: inputs; y: read and/or written), how many sums (NRED: 0, 1, 2) and
 //   __device__ void elem(R xr, R xi, R zr, R zi, R &yr, R &yi, R &a0, R &a1) const;     // one complex element
 // prepare(): once per thread before the sweep (coefficients that live in device memory).

@@ -7,6 +7,7 @@
 // state there.  Nothing is allocated per call; every call is asynchronous on the ctx stream; no workgroup waits for another.
 #include "mik_internal.h"
 #include "mik_dense_mul.h"
+#include "mik_dense_cmul.h"
 
 #include <new>
 
@@ -17,6 +18,7 @@ struct mik_dense {
     const void *A = nullptr;
     void *work = nullptr;            // N: [chunks][m_pad] partials;  T: [n][segments of m] segment sums
     int64_t m_pad = 0;               // m rounded up to whole workgroups of the N form (keeps every partial column 16-byte aligned)
+                                     // complex dtypes (csrc/mik_dense_cmul.h): the same layouts in complex elements, the segment sums as [n][re, im][segments]
     void *bwork = nullptr;           // block form: [right-hand side of the group][chunk][m_pad] partials of ONE group; never shared with `work`
     size_t bwork_bytes = 0;
     bool breserved = false;          // mik_dense_block_reserve has run (one chunk needs no workspace: bwork stays null)
@@ -219,7 +221,100 @@ int dm_mul_t(mik_dense *D, const T *x, T *y)
     return MIK_OK;
 }
 
+// ---- complex element types (csrc/mik_dense_cmul.h; R: the component type) -------------------------------------------------------------
+// The same plans over the same struct: the N form owns MIK_CDM_R rows per workgroup, the T form walks the 2 m reals of a column.
+inline const char *cdm_name(int dtype) { return dtype == MIK_C64 ? "ComplexF64" : "ComplexF32"; }
+
+template <typename R>
+dm_plan cdm_plan_n(const mik_dense *D, const R *x, const R *y)
+{
+    (void)x;
+    dm_plan p;
+    const int64_t m = D->m, n = D->n;
+    if (m == 0 || n == 0) return p;
+    p.cols = dm_chunks(n);
+    const R *out = p.cols == 1 ? y : (const R *)D->work;
+    p.vec = mik_aligned16(D->A) && (2 * D->lda) % VT<R>::W == 0 && mik_aligned16(out);
+    p.streamed = (double)m * (double)n * 2.0 * sizeof(R) > MIK_DM_STREAM_BYTES ? 1 : 0;
+    p.gx = (m + MIK_CDM_R - 1) / MIK_CDM_R;
+    p.gy = std::min<int64_t>(p.cols, std::max<int64_t>(1, std::min<int64_t>(65535, 4 * (int64_t)mik_cus(D->ctx) / p.gx)));      // as in the real N form
+    return p;
+}
+
+template <typename R>
+dm_plan cdm_plan_t(const mik_dense *D, const R *x, const R *y)
+{
+    (void)y;
+    dm_plan p;
+    const int64_t m = D->m, n = D->n;
+    p.nseg = mik_nseg<R>(2 * m);
+    if (n == 0 || p.nseg == 0) return p;
+    p.vec = mik_aligned16(D->A) && (2 * D->lda) % VT<R>::W == 0 && mik_aligned16(x);
+    p.streamed = (double)m * (double)n * 2.0 * sizeof(R) > MIK_DM_STREAM_BYTES ? 1 : 0;
+    p.cols = (n + MIK_CDM_TCOLS - 1) / MIK_CDM_TCOLS;
+    p.gx = std::min<int64_t>(p.nseg, mik_max_grid(D->ctx));
+    p.gy = std::min<int64_t>(p.cols, std::max<int64_t>(1, std::min<int64_t>(65535, 4 * (int64_t)mik_cus(D->ctx) / p.gx)));
+    return p;
+}
+
+template <typename R>
+int cdm_mul_n(mik_dense *D, const R *x, R *y)
+{
+    mik_ctx *ctx = D->ctx;
+    const int64_t m = D->m, n = D->n;
+    if (m == 0) return MIK_OK;
+    if (n == 0) {                                             // the empty sum: (+0, +0)
+        MIK_HIP(ctx, hipMemsetAsync(y, 0, 2 * sizeof(R) * (size_t)m, ctx->stream));
+        return MIK_OK;
+    }
+    const dm_plan p = cdm_plan_n<R>(D, x, y);
+    const int64_t nc = p.cols;
+    R *out = nc == 1 ? y : (R *)D->work;
+    const dim3 grid((unsigned)p.gx, (unsigned)p.gy);
+    if (p.vec && p.streamed) hipLaunchKernelGGL((k_cdense_n<R, MIK_CDM_R, true, true, MIK_DM_C>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const R *)D->A, D->lda, x, out, D->m_pad);
+    else if (p.vec) hipLaunchKernelGGL((k_cdense_n<R, MIK_CDM_R, true, false, MIK_DM_C>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const R *)D->A, D->lda, x, out, D->m_pad);
+    else hipLaunchKernelGGL((k_cdense_n<R, MIK_CDM_R, false, false, MIK_DM_C>), grid, dim3(MIK_BLOCK), 0, ctx->stream, m, n, (const R *)D->A, D->lda, x, out, D->m_pad);
+    MIK_LAUNCH_CHECK(ctx);
+    if (nc > 1) {                                             // complex addition is componentwise: the real combine over 2 m reals
+        hipLaunchKernelGGL((k_dense_n_combine<R, MIK_DM_PF>), dim3((unsigned)((2 * m + MIK_DM_CB - 1) / MIK_DM_CB)), dim3(MIK_DM_CB), 0, ctx->stream, 2 * m, nc, (const R *)out, 2 * D->m_pad, y, (int64_t)0, (int64_t)0);
+        MIK_LAUNCH_CHECK(ctx);
+    }
+    return MIK_OK;
+}
+
+template <typename R>
+int cdm_mul_t(mik_dense *D, const R *x, R *y)
+{
+    mik_ctx *ctx = D->ctx;
+    const int64_t m = D->m, n = D->n;
+    if (n == 0) return MIK_OK;
+    const dm_plan p = cdm_plan_t<R>(D, x, y);
+    const int64_t nseg = p.nseg;
+    if (nseg == 0) {                                          // empty columns: every dot is (+0, +0)
+        MIK_HIP(ctx, hipMemsetAsync(y, 0, 2 * sizeof(R) * (size_t)n, ctx->stream));
+        return MIK_OK;
+    }
+    R *part = (R *)D->work;
+    const dim3 grid((unsigned)p.gx, (unsigned)p.gy);
+    if (p.vec && p.streamed) hipLaunchKernelGGL((k_cdense_t<R, true, true>), grid, dim3(MIK_BLOCK), 0, ctx->stream, 2 * m, nseg, n, (const R *)D->A, D->lda, x, part);
+    else if (p.vec) hipLaunchKernelGGL((k_cdense_t<R, true, false>), grid, dim3(MIK_BLOCK), 0, ctx->stream, 2 * m, nseg, n, (const R *)D->A, D->lda, x, part);
+    else hipLaunchKernelGGL((k_cdense_t<R, false, false>), grid, dim3(MIK_BLOCK), 0, ctx->stream, 2 * m, nseg, n, (const R *)D->A, D->lda, x, part);
+    MIK_LAUNCH_CHECK(ctx);
+    // two sums per column: workgroup 2 j + c leaves component c of y[j] in real 2 j + c of y
+    hipLaunchKernelGGL((k_finalize_store<R>), dim3((unsigned)(2 * n)), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const R *)part, nseg, nseg, y, (const int *)nullptr);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
 }  // namespace
+
+extern "C" int mik_dense_mul_shape_for(int dtype, int *chunk, int *rows_per_workgroup)
+{
+    if (dtype != MIK_F64 && dtype != MIK_F32 && !mik_is_complex(dtype)) return MIK_ERR_INVALID;
+    if (chunk) *chunk = MIK_DM_C;
+    if (rows_per_workgroup) *rows_per_workgroup = mik_is_complex(dtype) ? MIK_CDM_R : MIK_DM_R;
+    return MIK_OK;
+}
 
 extern "C" int mik_dense_mul_shape(int *chunk, int *rows_per_workgroup)
 {
@@ -232,19 +327,23 @@ extern "C" int mik_dense_create(mik_ctx *ctx, int dtype, int64_t m, int64_t n, c
 {
     if (!ctx || !out) return MIK_ERR_INVALID;
     *out = nullptr;
-    if (dtype != MIK_F64 && dtype != MIK_F32) return mik_fail(ctx, MIK_ERR_INVALID, "mik_dense_create: dtype must be MIK_F64 or MIK_F32");
+    const bool cplx = mik_is_complex(dtype);
+    if (dtype != MIK_F64 && dtype != MIK_F32 && !cplx) return mik_fail(ctx, MIK_ERR_INVALID, "mik_dense_create: dtype must be MIK_F64, MIK_F32, MIK_C64 or MIK_C32");
     if (m < 0 || n < 0) return mik_fail(ctx, MIK_ERR_INVALID, "mik_dense_create: m = %lld, n = %lld", (long long)m, (long long)n);
     if (lda < m) return mik_fail(ctx, MIK_ERR_MISMATCH, "mik_dense_create: lda = %lld < m = %lld", (long long)lda, (long long)m);
     if (!A && m > 0 && n > 0) return MIK_ERR_INVALID;
     if (m > (int64_t)std::numeric_limits<int>::max() - MIK_DM_R || n > (int64_t)std::numeric_limits<int>::max() - MIK_DM_C)
         return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_dense_create: a dimension >= 2^31");
+    if (cplx && n >= ((int64_t)1 << 30)) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_dense_create: a %s matrix of 2^30 columns or more", cdm_name(dtype));   // 2 n finalisers
     mik_dense *D = new (std::nothrow) mik_dense();
     if (!D) return mik_fail(ctx, MIK_ERR_NOMEM, "mik_dense_create: host allocation failed");
     D->ctx = ctx; D->dtype = dtype; D->m = m; D->n = n; D->lda = lda; D->A = A;
-    D->m_pad = (m + MIK_DM_R - 1) / MIK_DM_R * MIK_DM_R;
+    const int64_t rw = cplx ? MIK_CDM_R : MIK_DM_R;
+    D->m_pad = (m + rw - 1) / rw * rw;
     const size_t es = mik_dtype_size(dtype);
     const int64_t nc = dm_chunks(n);
-    const int64_t nseg = dtype == MIK_F64 ? mik_nseg<double>(m) : mik_nseg<float>(m);
+    const int64_t nseg = dtype == MIK_F64 ? mik_nseg<double>(m) : dtype == MIK_F32 ? mik_nseg<float>(m)
+                       : dtype == MIK_C64 ? mik_nseg<double>(2 * m) : mik_nseg<float>(2 * m);     // complex: n x nseg (re, im) pairs = es bytes each
     const size_t bytes = std::max<size_t>(16, es * std::max<size_t>(nc > 1 ? (size_t)nc * (size_t)D->m_pad : 0, (size_t)n * (size_t)nseg));
     (void)hipSetDevice(ctx->device);
     const hipError_t e = hipMalloc(&D->work, bytes);
@@ -275,6 +374,10 @@ extern "C" int mik_dense_mul(mik_dense *D, int adjoint, const void *x, void *y)
     if (mik_overlap(x, es * (size_t)nx, y, es * (size_t)ny)) return mik_fail(D->ctx, MIK_ERR_INVALID, "mik_dense_mul: x and y must not overlap");
     const size_t abytes = (D->m > 0 && D->n > 0) ? es * ((size_t)(D->n - 1) * (size_t)D->lda + (size_t)D->m) : 0;
     if (mik_overlap(y, es * (size_t)ny, D->A, abytes)) return mik_fail(D->ctx, MIK_ERR_INVALID, "mik_dense_mul: y must not overlap A");
+    if (D->dtype == MIK_C64)
+        return adjoint ? cdm_mul_t<double>(D, (const double *)x, (double *)y) : cdm_mul_n<double>(D, (const double *)x, (double *)y);
+    if (D->dtype == MIK_C32)
+        return adjoint ? cdm_mul_t<float>(D, (const float *)x, (float *)y) : cdm_mul_n<float>(D, (const float *)x, (float *)y);
     if (D->dtype == MIK_F64)
         return adjoint ? dm_mul_t<double>(D, (const double *)x, (double *)y) : dm_mul_n<double>(D, (const double *)x, (double *)y);
     return adjoint ? dm_mul_t<float>(D, (const float *)x, (float *)y) : dm_mul_n<float>(D, (const float *)x, (float *)y);
@@ -289,12 +392,14 @@ extern "C" int mik_dense_block_shape(int *group_width)
 extern "C" int mik_dense_block_reserve(mik_dense *D)
 {
     if (!D) return MIK_ERR_INVALID;
+    if (mik_is_complex(D->dtype)) return mik_fail(D->ctx, MIK_ERR_NOTIMPL, "mik_dense_block_reserve: the block product is not implemented for %s matrices", cdm_name(D->dtype));
     return dm_block_reserve(D);
 }
 
 extern "C" int mik_dense_mm(mik_dense *D, int b, const void *X, int64_t ldx, void *Y, int64_t ldy)
 {
     if (!D || b < 0) return MIK_ERR_INVALID;
+    if (mik_is_complex(D->dtype)) return mik_fail(D->ctx, MIK_ERR_NOTIMPL, "mik_dense_mm: the block product is not implemented for %s matrices", cdm_name(D->dtype));
     if (b > MIK_DM_BMAX) return mik_fail(D->ctx, MIK_ERR_NOTIMPL, "mik_dense_mm: b = %d (at most %d columns)", b, MIK_DM_BMAX);
     if (b == 0) return MIK_OK;
     if (ldx < D->n || ldy < D->m)
@@ -315,6 +420,7 @@ extern "C" int mik_dev_dense_block_plan(const mik_dense *D, int b, const void *X
                                         int64_t *workspace_bytes)
 {
     if (!D) return MIK_ERR_INVALID;
+    if (mik_is_complex(D->dtype)) return mik_fail(D->ctx, MIK_ERR_NOTIMPL, "mik_dev_dense_block_plan: the block product is not implemented for %s matrices", cdm_name(D->dtype));
     const dm_bplan p = D->dtype == MIK_F64 ? dm_plan_nb<double>(D, b, (const double *)X, ldx, (const double *)Y, ldy)
                                            : dm_plan_nb<float>(D, b, (const float *)X, ldx, (const float *)Y, ldy);
     if (vec) *vec = p.vec;
@@ -341,7 +447,9 @@ extern "C" int mik_dev_dense_plan(const mik_dense *D, int adjoint, const void *x
 {
     if (!D) return MIK_ERR_INVALID;
     dm_plan p;
-    if (D->dtype == MIK_F64) p = adjoint ? dm_plan_t<double>(D, (const double *)x, (const double *)y) : dm_plan_n<double>(D, (const double *)x, (const double *)y);
+    if (D->dtype == MIK_C64) p = adjoint ? cdm_plan_t<double>(D, (const double *)x, (const double *)y) : cdm_plan_n<double>(D, (const double *)x, (const double *)y);
+    else if (D->dtype == MIK_C32) p = adjoint ? cdm_plan_t<float>(D, (const float *)x, (const float *)y) : cdm_plan_n<float>(D, (const float *)x, (const float *)y);
+    else if (D->dtype == MIK_F64) p = adjoint ? dm_plan_t<double>(D, (const double *)x, (const double *)y) : dm_plan_n<double>(D, (const double *)x, (const double *)y);
     else p = adjoint ? dm_plan_t<float>(D, (const float *)x, (const float *)y) : dm_plan_n<float>(D, (const float *)x, (const float *)y);
     if (vec) *vec = p.vec;
     if (streamed) *streamed = p.streamed;

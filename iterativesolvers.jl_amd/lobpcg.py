@@ -117,6 +117,8 @@ class DeviceOps:
         if A.n_rows != A.n_cols or (B is not None and (B.n_rows, B.n_cols, np.dtype(B.dtype)) != (A.n_rows, A.n_cols, np.dtype(A.dtype))):
             raise ValueError("DimensionMismatch: lobpcg needs square A and B of one size and element type")
         self.ctx, self.dtype, self.n = A.ctx, np.dtype(A.dtype), A.n_rows
+        if isinstance(A, HipMatrix) and self.dtype.kind == "c":
+            raise TypeError(f"lobpcg is not offered for a {self.dtype} HipMatrix (the block product mik_dense_mm is real only)")
         self.code = real_dtype_code(self.dtype, "lobpcg")
         for M in (A, B):
             if isinstance(M, HipMatrix):
