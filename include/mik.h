@@ -254,12 +254,15 @@ int mik_gemv_n(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t
                const void *c, const void *alpha, void *y);
 
 /* h = V[:, 1:k]' * w -- mul!(h, adjoint(V), w): src/orthogonalize.jl:15,43 and (column by column) the
- * Gram matrix of src/bicgstabl.jl:121.  One sweep reads w once and every column once.  h: HOST. */
+ * Gram matrix of src/bicgstabl.jl:121.  One sweep reads w once and every column once.  h: HOST.
+ * complex: h[j] has the bits of the complex mik_dot(V[:, j], w); h is k host complex scalars. */
 int mik_gemv_t(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv, const void *w,
                void *h);
 /* Host: solve the small dense system A x = b (column-major n x n) by LU with partial pivoting --
  * lu! + ldiv! at src/bicgstabl.jl:124-125.  A is overwritten by its factors, b by x; MIK_ERR_SINGULAR if A is
- * exactly singular. */
+ * exactly singular.
+ * complex: the pivot of a column is the FIRST row with the largest |re| + |im| (LAPACK getrf's izamax, what lu! reaches for a complex
+ * matrix); quotients by Smith's scaling; MIK_ERR_SINGULAR on an exactly zero pivot column. */
 int mik_lu_solve(int dtype, void *A, int64_t lda, int n, void *b);
 
 /* ---- L3 iterables ------------------------------------------------------------------------ */
@@ -351,13 +354,20 @@ int mik_gmres_create_op(mik_ctx *ctx, const mik_operator *A, const mik_precond *
  * bit mask of operands the caller will not touch again soon: they are streamed past the caches (non-temporal
  * loads / stores) so that the operands that ARE re-read stay resident; results never depend on it (0 = none). */
 /* y .+= alpha .* x (x NULL: no update); then *out = dot(z, y), or norm(y) when z is NULL
- *   -- src/minres.jl:104+107 and :109+112 */
+ *   -- src/minres.jl:104+107 and :109+112
+ * complex: alpha is a host complex, or, with MIK_SCALAR_REAL or-ed into dtype, a host real that multiplies as real x complex; *out is one
+ * host complex (dot(z, y) = sum conj(z_i) y_i, the bits of mik_dot) or, z NULL, a host REAL (norm(y), the bits and the safe second pass
+ * of mik_nrm2).  The flag on a fused entry means that EVERY scalar argument of the call is a real of the component type. */
 int mik_axpy_dot(mik_ctx *ctx, int dtype, int64_t n, const void *alpha, const void *x, void *y, const void *z, void *out,
                  int hints /* 1: x */);
-/* x .+= alpha .* u; r .-= alpha .* c; *out = norm(r)   -- src/chebyshev.jl:51-54 (same shape as src/cg.jl:58-62) */
+/* x .+= alpha .* u; r .-= alpha .* c; *out = norm(r)   -- src/chebyshev.jl:51-54 (same shape as src/cg.jl:58-62)
+ * complex: alpha is real in src/chebyshev.jl, so MIK_SCALAR_REAL is required (without it: MIK_ERR_INVALID); the sweep and the norm are
+ * the real ones over the 2 n interleaved reals. */
 int mik_axpy2_nrm2(mik_ctx *ctx, int dtype, int64_t n, const void *alpha, const void *u, void *x, const void *c, void *r, void *out,
                    int hints /* 1: x, 2: c, 4: u */);
-/* c = Pl \ r (pl_diag NULL = Identity); u .= c when `first`, else u .= c .+ beta .* c   -- src/chebyshev.jl:35-45 */
+/* c = Pl \ r (pl_diag NULL = Identity); u .= c when `first`, else u .= c .+ beta .* c   -- src/chebyshev.jl:35-45
+ * complex: beta is real, MIK_SCALAR_REAL is required (without it: MIK_ERR_INVALID); pl_diag != NULL is MIK_ERR_NOTIMPL (no complex
+ * division on the device). */
 int mik_cheb_direction(mik_ctx *ctx, int dtype, int64_t n, const void *r, const void *pl_diag, const void *beta, int first, void *u);
 /* LSQR / LSMR (src/lsqr.jl, src/lsmr.jl), groups of consecutive statements as single sweeps with the same per-element operations:
  *   mik_xpby_nrm2     y .= x .+ beta .* y; *out = norm(y)           u .= -alpha .* u .+ tmpm; beta = norm(u)  (src/lsqr.jl:151-152, :159-160;
@@ -380,16 +390,22 @@ int mik_scal2(mik_ctx *ctx, int dtype, int64_t n, const void *a, void *x, const 
 int mik_qmr_update(mik_ctx *ctx, int dtype, int64_t n, const void *v, const void *neg_h1, const void *p_curr, const void *neg_h0, const void *p_prev,
                    const void *inv, const void *g, void *x, void *p_out);
 /* v_next .*= inv_h3; w_next .= v_curr .+ neg_h1 .* w_curr .+ neg_h0 .* w_prev (each term skipped when its vector
- * is NULL); w_next .*= inv_h2; x .+= rhs0 .* w_next   -- src/minres.jl:113, :136-142 */
+ * is NULL); w_next .*= inv_h2; x .+= rhs0 .* w_next   -- src/minres.jl:113, :136-142
+ * complex: with MIK_SCALAR_REAL the five scalars are host reals (Hermitian: H and rhs are real(T)) and the sweep is the real one over
+ * 2 n; without it the five are host complex (skew-Hermitian) and every product is the complex one, in the statement order above. */
 int mik_minres_update(mik_ctx *ctx, int dtype, int64_t n, const void *inv_h3, void *v_next, const void *v_curr, const void *neg_h1,
                       const void *w_curr, const void *neg_h0, const void *w_prev, const void *inv_h2, void *w_next,
                       const void *rhs0, void *x, int hints /* 1: x, 2: w_prev */);
 
 /* M = V' * V for k <= 5 columns in ONE pass over V (all pairwise dots; M is k x k, column-major, host) -- the
- * Gram matrix of src/bicgstabl.jl:120; entry (r, c) equals mik_dot(V[:, r], V[:, c]) bit for bit. */
+ * Gram matrix of src/bicgstabl.jl:120; entry (r, c) equals mik_dot(V[:, r], V[:, c]) bit for bit.
+ * complex: for r <= c, M[r, c] has the bits of the complex mik_dot(V[:, r], V[:, c]); the lower triangle is the conjugate of the upper
+ * (equal real parts, negated imaginary parts: mik_dot as numbers, the sign of a zero aside); the diagonal's imaginary part is +0. */
 int mik_gram(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv, void *M);
 /* BiCGStab(l) minimal-residual update, src/bicgstabl.jl:127-132, as one sweep: us[:, 1] -= us[:, 2:l+1] * gamma;
- * x += rs[:, 1:l] * gamma; rs[:, 1] -= rs[:, 2:l+1] * gamma; *out = norm(rs[:, 1]).  l <= 8; gamma: l host scalars. */
+ * x += rs[:, 1:l] * gamma; rs[:, 1] -= rs[:, 2:l+1] * gamma; *out = norm(rs[:, 1]).  l <= 8; gamma: l host scalars.
+ * complex: gamma is l host complex scalars, *out a host real; the per-element operations are those of three complex mik_gemv_n calls
+ * with alpha = -/+(1 + 0 i) (t_j = alpha * gamma_j on the host, columns ascending); l <= 8 as for the real types. */
 int mik_bicgstab_mr_update(mik_ctx *ctx, int dtype, int64_t n, int l, void *us, int64_t ldu, void *rs, int64_t ldr, void *x,
                            const void *gamma, void *out);
 

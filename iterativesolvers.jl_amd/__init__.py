@@ -26,7 +26,8 @@ from .api import (CGIterable, CGStateVariables, ClassicalGramSchmidt, Convergenc
                   dot, gemv_n_, gmres, gmres_, gmres_iterable_, hessenberg_ldiv_, mul_, niters, norm, nprods,
                   nrests, orthogonalize_and_normalize_, zerox, BiCGStabIterable, bicgstabl, bicgstabl_, bicgstabl_iterator_,
                   gemv_t_, lu_solve_, ChebyshevIterable, chebyshev, chebyshev_, chebyshev_iterable_, MINRESIterable, minres, minres_,
-                  minres_iterable_, givens_algorithm, axpy_dot_, axpy2_nrm2_, gram_, LinearOperator)
+                  minres_iterable_, givens_algorithm, axpy_dot_, axpy2_nrm2_, gram_, LinearOperator, cheb_direction_, minres_update_,
+                  bicgstab_mr_update_)
 from .stationary import (GaussSeidelIterable, JacobiIterable, SingularException, SORIterable, SSORIterable,   # noqa: F401
                          StationaryOperator)
 from .stationary_dense import (DenseGaussSeidelIterable, DenseJacobiIterable, DenseSORIterable, DenseSSORIterable,   # noqa: F401

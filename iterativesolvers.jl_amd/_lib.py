@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libmik.so")
 MIK_OK = 0
 MIK_F64, MIK_F32 = 0, 1
 MIK_C64, MIK_C32 = 2, 3          # ComplexF64 / ComplexF32, interleaved (re, im)
-MIK_SCALAR_REAL = 0x100            # or-ed into the dtype of mik_axpy / mik_xpby / mik_scal: a real host scalar on a complex vector
+MIK_SCALAR_REAL = 0x100            # or-ed into the dtype of mik_axpy / mik_xpby / mik_scal and of the fused sweeps: real host scalars on complex vectors
 MIK_MGS, MIK_CGS, MIK_DGKS = 0, 1, 2
 STATUS = {1: "invalid argument", 2: "HIP runtime error", 3: "dimension/dtype mismatch",
           4: "out of memory", 5: "not implemented", 6: "callback failed", 7: "norm outside the safely representable range",
@@ -298,7 +298,7 @@ def dtype_code(dtype) -> int:
         return MIK_F64
     if dtype == np.float32:
         return MIK_F32
-    if dtype == np.complex128:             # cg / gmres on CSR operators and the L1 / L2 entries under them
+    if dtype == np.complex128:             # the five solver rows and the L1 / L2 entries under them (DESIGN.md sections 17 - 19)
         return MIK_C64
     if dtype == np.complex64:
         return MIK_C32
@@ -306,9 +306,10 @@ def dtype_code(dtype) -> int:
 
 
 def real_dtype_code(dtype, who: str) -> int:
-    """``dtype_code`` for the entries that stay real (everything but cg / gmres on a CSR operator and the L1 / L2 entries under them)."""
+    """``dtype_code`` for what stays real: svdl, lobpcg, the stationary methods and the extras."""
     if np.dtype(dtype).kind == "c":
-        raise TypeError(f"{who} is not offered for complex element types (DESIGN.md sections 17, 18: cg and gmres on a CSR or dense operator are)")
+        raise TypeError(f"{who} is not offered for complex element types (DESIGN.md sections 17 - 19: cg, gmres, bicgstabl, minres and chebyshev "
+                        "on a CSR or dense operator are)")
     return dtype_code(dtype)
 
 

@@ -41,6 +41,22 @@ def _scalar(dtype, value):
     return a, a.ctypes.data_as(_vp)
 
 
+def _coef_of(dtype, code, *values):
+    """Host scalars of a fused entry: ``([(array, pointer), ...], dtype code)``.  On a complex vector, real Python scalars select
+    ``MIK_SCALAR_REAL``: every scalar of the call is then a real of the component type (mixed calls do not occur)."""
+    if _is_complex(dtype) and not any(np.iscomplexobj(v) for v in values):
+        return [_scalar(_real_dtype(dtype), v) for v in values], code | _lib.MIK_SCALAR_REAL
+    return [_scalar(dtype, v) for v in values], code
+
+
+def _require_device(who: str, dtype, ops, *operands):
+    """A complex solve without ``ops`` runs on this module's device types only (``_DEVICE_TYPES``, below the classes) -- said before
+    anything reaches the library."""
+    if ops is None and _is_complex(dtype) and not all(isinstance(o, _DEVICE_TYPES) for o in operands):
+        raise TypeError(f"{who}: {np.dtype(dtype)} operands must be this module's device types (HipVector, HipCSR, HipMatrix, LinearOperator); "
+                        "a host double of them needs its backend's `ops`")
+
+
 def _real_dtype(dtype) -> np.dtype:
     """``real(T)``: the type of ``norm``, of tolerances and of the components of a complex element type."""
     return np.dtype(np.dtype(dtype).type(0).real.dtype)
@@ -268,21 +284,20 @@ def norm(x: HipVector):
 
 def axpy_dot_(alpha, x: Optional[HipVector], y: HipVector, z: Optional[HipVector], hints: int = 0):
     """``y .+= alpha .* x`` (skipped when x is None) and, in the same sweep, ``dot(z, y)`` -- or ``norm(y)`` when z is
-    None (src/minres.jl:104+107, :109+112)."""
-    _lib.real_dtype_code(y.dtype, "axpy_dot")
-    out = np.zeros(1, y.dtype)
-    _, pa = _scalar(y.dtype, 0 if x is None else alpha)
-    check(lib().mik_axpy_dot(y.ctx.handle, y.code, y.n, pa, _vp(x.ptr if x is not None else None), _vp(y.ptr),
+    None (src/minres.jl:104+107, :109+112).  Complex: a real ``alpha`` multiplies as real x complex, ``dot`` is complex, ``norm`` real."""
+    out = np.zeros(1, y.dtype if z is not None else _real_dtype(y.dtype))
+    ((_, pa),), code = _coef_of(y.dtype, y.code, 0 if x is None else alpha)
+    check(lib().mik_axpy_dot(y.ctx.handle, code, y.n, pa, _vp(x.ptr if x is not None else None), _vp(y.ptr),
                              _vp(z.ptr if z is not None else None), out.ctypes.data_as(_vp), int(hints)), "mik_axpy_dot", y.ctx.handle)
     return out[0]
 
 
 def axpy2_nrm2_(alpha, u: HipVector, x: HipVector, c: HipVector, r: HipVector, hints: int = 0):
-    """``x .+= alpha .* u; r .-= alpha .* c; norm(r)`` in one sweep (src/chebyshev.jl:51-54)."""
-    _lib.real_dtype_code(x.dtype, "axpy2_nrm2")
-    out = np.zeros(1, x.dtype)
-    _, pa = _scalar(x.dtype, alpha)
-    check(lib().mik_axpy2_nrm2(x.ctx.handle, x.code, x.n, pa, _vp(u.ptr), _vp(x.ptr), _vp(c.ptr), _vp(r.ptr), out.ctypes.data_as(_vp), int(hints)),
+    """``x .+= alpha .* u; r .-= alpha .* c; norm(r)`` in one sweep (src/chebyshev.jl:51-54; ``alpha`` is real there, also on complex
+    vectors, and only that form is offered)."""
+    out = np.zeros(1, _real_dtype(x.dtype))
+    ((_, pa),), code = _coef_of(x.dtype, x.code, alpha)
+    check(lib().mik_axpy2_nrm2(x.ctx.handle, code, x.n, pa, _vp(u.ptr), _vp(x.ptr), _vp(c.ptr), _vp(r.ptr), out.ctypes.data_as(_vp), int(hints)),
           "mik_axpy2_nrm2", x.ctx.handle)
     return out[0]
 
@@ -649,6 +664,9 @@ def _refuse_complex_jacobi(dtype, *preconditioners):
     if _is_complex(dtype) and any(isinstance(P, JacobiPrec) for P in preconditioners):
         raise TypeError("JacobiPrec is not offered for complex element types (no complex division on the device): "
                         "pass a preconditioner object with ldiv_(y, x)")
+
+
+_DEVICE_TYPES = (HipVector, HipMatrix, HipMatrixAdjoint, HipCSR, LinearOperator)
 
 
 def zerox(A: HipCSR, b: HipVector) -> HipVector:
@@ -1019,7 +1037,6 @@ def gemv_n_(y: HipVector, V: HipMatrix, k: int, c: np.ndarray, alpha=1.0, col0: 
 
 def gemv_t_(V: HipMatrix, k: int, w: HipVector, col0: int = 0) -> np.ndarray:
     """``adjoint(view(V, :, col0+1 : col0+k)) * w`` -- src/orthogonalize.jl:15, one column of src/bicgstabl.jl:121."""
-    _lib.real_dtype_code(V.dtype, "gemv_t")
     h = np.zeros(max(k, 1), V.dtype)
     check(lib().mik_gemv_t(V.ctx.handle, dtype_code(V.dtype), V.n, int(k), _vp(V.col(col0).ptr), V.ld, _vp(w.ptr), h.ctypes.data_as(_vp)),
           "mik_gemv_t", V.ctx.handle)
@@ -1028,7 +1045,6 @@ def gemv_t_(V: HipMatrix, k: int, w: HipVector, col0: int = 0) -> np.ndarray:
 
 def gram_(V: HipMatrix, k: int, col0: int = 0) -> np.ndarray:
     """``adjoint(V[:, col0+1 : col0+k]) * V[:, col0+1 : col0+k]`` in one pass (k <= 5) -- src/bicgstabl.jl:120."""
-    _lib.real_dtype_code(V.dtype, "gram")
     M = np.zeros((k, k), V.dtype, order="F")
     check(lib().mik_gram(V.ctx.handle, dtype_code(V.dtype), V.n, int(k), _vp(V.col(col0).ptr), V.ld, M.ctypes.data_as(_vp)),
           "mik_gram", V.ctx.handle)
@@ -1053,6 +1069,46 @@ def hessenberg_ldiv_(H: np.ndarray, rhs: np.ndarray):
     check(lib().mik_hessenberg_ldiv(dtype_code(H.dtype), H.ctypes.data_as(_vp), H.shape[0], H.shape[1], rhs.ctypes.data_as(_vp)),
           "mik_hessenberg_ldiv", None)
     return rhs
+
+
+def givens_algorithm(f, g, dtype=np.float64):
+    """``LinearAlgebra.givensAlgorithm(f, g)`` -> (c, s, r) on the host -- src/minres.jl:129, src/hessenberg.jl:24 (complex: c is
+    real, ``[c s; -conj(s) c] * [f; g] = [r; 0]``)."""
+    fa, ga, out = np.asarray([f], dtype), np.asarray([g], dtype), np.zeros(3, dtype)
+    check(lib().mik_givens(dtype_code(dtype), fa.ctypes.data_as(_vp), ga.ctypes.data_as(_vp), out.ctypes.data_as(_vp)), "mik_givens", None)
+    return (out[0].real if _is_complex(dtype) else out[0]), out[1], out[2]
+
+
+def cheb_direction_(u: HipVector, r: HipVector, beta, first: bool, diagonal: Optional[HipVector] = None) -> HipVector:
+    """``c = Pl \\ r`` (Identity, or a real diagonal); ``u .= c`` (first) or ``u .= c .+ beta .* c`` in one sweep -- src/chebyshev.jl:35-45.
+    ``beta`` is real, also on complex vectors."""
+    ((_, pb),), code = _coef_of(u.dtype, u.code, beta)
+    check(lib().mik_cheb_direction(u.ctx.handle, code, u.n, _vp(r.ptr), _vp(diagonal.ptr if diagonal is not None else None), pb, int(first), _vp(u.ptr)),
+          "mik_cheb_direction", u.ctx.handle)
+    return u
+
+
+def minres_update_(x: HipVector, v_next: HipVector, v_curr: HipVector, w_curr: Optional[HipVector], w_prev: Optional[HipVector], w_next: HipVector,
+                   inv_h3, neg_h1, neg_h0, inv_h2, rhs0, hints: int = 0) -> None:
+    """``v_next .*= inv_h3; w_next .= v_curr; w_next .+= neg_h1 .* w_curr; w_next .+= neg_h0 .* w_prev; w_next .*= inv_h2;
+    x .+= rhs0 .* w_next`` in one sweep (a term is skipped when its vector is None) -- src/minres.jl:115, :138-144.  On complex vectors the five
+    scalars are all real (Hermitian) or all complex (skew-Hermitian)."""
+    sc, code = _coef_of(x.dtype, x.code, inv_h3, neg_h1, neg_h0, inv_h2, rhs0)
+    check(lib().mik_minres_update(x.ctx.handle, code, x.n, sc[0][1], _vp(v_next.ptr), _vp(v_curr.ptr),
+                                  sc[1][1], _vp(w_curr.ptr if w_curr is not None else None),
+                                  sc[2][1], _vp(w_prev.ptr if w_prev is not None else None),
+                                  sc[3][1], _vp(w_next.ptr), sc[4][1], _vp(x.ptr), int(hints)), "mik_minres_update", x.ctx.handle)
+
+
+def bicgstab_mr_update_(us: HipMatrix, rs: HipMatrix, x: HipVector, l: int, gamma: np.ndarray):
+    """``us[:, 1] -= us[:, 2:l+1] gamma; x += rs[:, 1:l] gamma; rs[:, 1] -= rs[:, 2:l+1] gamma`` and ``norm(rs[:, 1])`` in one sweep
+    (l <= 8) -- src/bicgstabl.jl:126-132."""
+    out = np.zeros(1, _real_dtype(x.dtype))
+    g = np.ascontiguousarray(gamma, x.dtype)
+    check(lib().mik_bicgstab_mr_update(x.ctx.handle, x.code, x.n, int(l), _vp(us.col(0).ptr), us.ld, _vp(rs.col(0).ptr),
+                                       rs.ld, _vp(x.ptr), g.ctypes.data_as(_vp), out.ctypes.data_as(_vp)),
+          "mik_bicgstab_mr_update", x.ctx.handle)
+    return out[0]
 
 
 # ==============================================================================================
@@ -1147,13 +1203,23 @@ class GMRESIterable:
 
 
 class DeviceKrylovOps:
-    """The L1 / L2 entries ``GenericCGIterable`` and ``GenericGMRESIterable`` are spelled with, on the device types of this module."""
+    """The L1 / L2 entries the iterables over them are spelled with (``GenericCGIterable``, ``GenericGMRESIterable``, ``BiCGStabIterable``,
+    ``MINRESIterable``, ``ChebyshevIterable``), on the device types of this module."""
     mul_ = staticmethod(mul_)
     dot = staticmethod(dot)
     norm = staticmethod(norm)
     orthogonalize_and_normalize_ = staticmethod(orthogonalize_and_normalize_)
     gemv_n_ = staticmethod(gemv_n_)
     hessenberg_ldiv_ = staticmethod(hessenberg_ldiv_)
+    gemv_t_ = staticmethod(gemv_t_)
+    gram_ = staticmethod(gram_)
+    lu_solve_ = staticmethod(lu_solve_)
+    axpy_dot_ = staticmethod(axpy_dot_)
+    axpy2_nrm2_ = staticmethod(axpy2_nrm2_)
+    cheb_direction_ = staticmethod(cheb_direction_)
+    minres_update_ = staticmethod(minres_update_)
+    bicgstab_mr_update_ = staticmethod(bicgstab_mr_update_)
+    givens_algorithm = staticmethod(givens_algorithm)
 
     @staticmethod
     def basis(x: HipVector, cols: int) -> HipMatrix:                      # zeros(T, size(A, 1), order + 1), src/gmres.jl:13
@@ -1346,40 +1412,58 @@ def gmres(A: HipCSR, b: HipVector, **kwargs):
 class BiCGStabIterable:
     """``BiCGStabIterable`` -- src/bicgstabl.jl:5-23; construction follows ``bicgstabl_iterator!`` (:25-73).
     ``r_shadow`` replaces the reference's ``rand(T, n)`` (:38) so that runs are reproducible; by default it
-    is the hashed vector of ``fixtures.hashed_rhs`` shifted into (0, 1)."""
+    is the hashed vector of ``fixtures.hashed_rhs`` shifted into (0, 1) (complex: re from the first n hashed values, im from the next n).
+    A complex operator, or ``ops`` given, runs the statement-by-statement branch over ``ops`` (rho, sigma, beta, alpha, gamma, omega complex
+    numpy scalars), with the one-pass Gram matrix and the one-sweep MR update when ``fused``; the whole-iteration handle is real only.
+    ``Pl`` is then ``Identity`` or any object with ``ldiv_(y, x)`` (y may alias x)."""
 
     def __init__(self, x: HipVector, A: HipCSR, b: HipVector, l: int = 2, *, Pl=None, max_mv_products, abstol, reltol,
-                 initial_zero, r_shadow: Optional[HipVector] = None, fused: bool = True):
+                 initial_zero, r_shadow: Optional[HipVector] = None, fused: bool = True, ops=None):
         from . import fixtures
-        T = x.dtype.type
+        T, RT = x.dtype.type, _real_dtype(x.dtype).type
         self.fused = bool(fused)          # one-pass Gram matrix and one-sweep MR update (same bits) for l <= 4
+        self.generic = ops is not None or _is_complex(x.dtype)
+        self.ops = ops = DeviceKrylovOps if ops is None else ops
+        mul_, norm = ops.mul_, ops.norm
         n = A.size(1)
         self.A, self.l, self.x = A, int(l), x
         self.Pl = Identity() if Pl is None else Pl
-        if not isinstance(self.Pl, (Identity, JacobiPrec)):
+        if self.generic:
+            _refuse_complex_jacobi(x.dtype, self.Pl)
+            if not isinstance(self.Pl, (Identity, JacobiPrec)) and not callable(getattr(self.Pl, "ldiv_", None)):
+                raise MikError(5, "bicgstabl_iterator_", "Pl needs ldiv_(y, x) (docs/src/preconditioning.md:5-14)")
+        elif not isinstance(self.Pl, (Identity, JacobiPrec)):
             raise MikError(5, "bicgstabl_iterator_", "Pl must be Identity() or a diagonal JacobiPrec on the device path")
         self.mv_products = 0
-        self.r_shadow = r_shadow if r_shadow is not None else HipVector.from_numpy((fixtures.hashed_rhs(n) + 0.5).astype(x.dtype), x.ctx)
-        self.rs = HipMatrix(n, self.l + 1, x.dtype, x.ctx)                  # :39
-        self.us = HipMatrix(n, self.l + 1, x.dtype, x.ctx)                  # :40 zeros
+        if r_shadow is not None:
+            self.r_shadow = r_shadow
+        elif self.generic:
+            shadow = fixtures.hashed_rhs(n) + 0.5
+            if _is_complex(x.dtype):
+                shadow = shadow + 1j * (fixtures.hashed_rhs(2 * n, start=n) + 0.5)
+            self.r_shadow = x.similar().copy_from_host(shadow.astype(x.dtype))
+        else:
+            self.r_shadow = HipVector.from_numpy((fixtures.hashed_rhs(n) + 0.5).astype(x.dtype), x.ctx)
+        self.rs = ops.basis(x, self.l + 1)                                   # :39
+        self.us = ops.basis(x, self.l + 1)                                   # :40 zeros
         residual = self.rs.col(0)
         if initial_zero:
             residual.copyto_(b)                                              # :46
         else:
             mul_(residual, A, x)                                             # :48
-            residual.xpby_(b, T(-1))                                         # residual .= b .- residual  :49
+            residual.xpby_(b, RT(-1))                                        # residual .= b .- residual  :49
             self.mv_products += 1
         self._ldiv(residual)                                                 # :55
         self.gamma = np.zeros(self.l, x.dtype)                               # :58
         self.omega = self.sigma = T(1)                                       # :59
         self.residual = norm(residual)                                       # :61
         self.M = np.zeros((self.l + 1, self.l + 1), x.dtype, order="F")      # :66
-        self.tol = max(T(reltol) * self.residual, T(abstol))                 # :69
+        self.tol = max(RT(reltol) * self.residual, RT(abstol))               # :69
         self.max_mv_products = int(max_mv_products)
-        # fused, l <= 4, a HipCSR operator: the whole outer iteration is one C call with its scalars on the device
+        # fused, l <= 4, a real HipCSR operator: the whole outer iteration is one C call with its scalars on the device
         # (mik_bicgstab_step); omega, sigma, gamma and M then live there and the host copies above stay at their initial values
         self._step = None
-        if self.fused and self.l <= 4 and isinstance(A, HipCSR):
+        if self.fused and self.l <= 4 and isinstance(A, HipCSR) and not self.generic:
             h = _vp()
             d = self.Pl.diagonal.ptr if isinstance(self.Pl, JacobiPrec) else None
             check(lib().mik_bicgstab_create(x.ctx.handle, A.handle, self.l, _vp(x.ptr), _vp(self.rs.col(0).ptr), self.rs.ld, _vp(self.us.col(0).ptr),
@@ -1389,6 +1473,8 @@ class BiCGStabIterable:
     def _ldiv(self, v: HipVector):
         if isinstance(self.Pl, JacobiPrec):
             self.Pl.ldiv_(v)
+        elif not isinstance(self.Pl, Identity):
+            self.Pl.ldiv_(v, v)
 
     def dot_shape(self):
         """(W, L) of the reduction tree of ``sigma = dot(r_shadow, A u)`` (src/bicgstabl.jl:100) and of ``rho`` from the second column on
@@ -1415,6 +1501,8 @@ class BiCGStabIterable:
         if self.done(iteration):
             return None
         l, rs, us = self.l, self.rs, self.us
+        ops = self.ops
+        mul_, dot, norm, gemv_n_ = ops.mul_, ops.dot, ops.norm, ops.gemv_n_
         if self._step is not None:
             out = np.zeros(1, self.x.dtype)
             rc = lib().mik_bicgstab_step(self._step, out.ctypes.data_as(_vp))
@@ -1442,20 +1530,15 @@ class BiCGStabIterable:
         self.mv_products += 2 * l                                            # :115
         fused = self.fused and l + 1 <= 5
         if fused:
-            self.M[:, :] = gram_(rs, l + 1)                                  # M = rs' * rs  :120, one pass
+            self.M[:, :] = ops.gram_(rs, l + 1)                              # M = rs' * rs  :120, one pass
         else:
             for c in range(l + 1):                                           # M = rs' * rs  :120
-                self.M[:, c] = gemv_t_(rs, l + 1, rs.col(c))
+                self.M[:, c] = ops.gemv_t_(rs, l + 1, rs.col(c))
         Msub = np.asfortranarray(self.M[1:, 1:].copy())
-        self.gamma = lu_solve_(Msub, self.M[1:, 0].copy())                   # :123-125
+        self.gamma = ops.lu_solve_(Msub, self.M[1:, 0].copy())               # :123-125
         self.omega = self.gamma[l - 1]                                       # :131
         if fused:                                                            # :127-129, :132 in one sweep
-            out = np.zeros(1, self.x.dtype)
-            g = np.ascontiguousarray(self.gamma, self.x.dtype)
-            check(lib().mik_bicgstab_mr_update(self.x.ctx.handle, self.x.code, self.x.n, l, _vp(us.col(0).ptr), us.ld, _vp(rs.col(0).ptr),
-                                               rs.ld, _vp(self.x.ptr), g.ctypes.data_as(_vp), out.ctypes.data_as(_vp)),
-                  "mik_bicgstab_mr_update", self.x.ctx.handle)
-            self.residual = out[0]
+            self.residual = ops.bicgstab_mr_update_(us, rs, self.x, l, self.gamma)
             return self.residual, iteration + 1
         gemv_n_(us.col(0), us, l, self.gamma, -1.0, col0=1)                  # :127
         gemv_n_(self.x, rs, l, self.gamma, 1.0, col0=0)                      # :128
@@ -1479,13 +1562,14 @@ class BiCGStabIterable:
 
 
 def bicgstabl_iterator_(x: HipVector, A: HipCSR, b: HipVector, l: int = 2, *, Pl=None, max_mv_products=None, abstol=0.0,
-                        reltol=None, initial_zero: bool = False, r_shadow: Optional[HipVector] = None, fused: bool = True):
-    """``bicgstabl_iterator!(x, A, b, l; ...)`` -- src/bicgstabl.jl:25-73."""
-    _lib.real_dtype_code(b.dtype, "bicgstabl_iterator")
+                        reltol=None, initial_zero: bool = False, r_shadow: Optional[HipVector] = None, fused: bool = True, ops=None):
+    """``bicgstabl_iterator!(x, A, b, l; ...)`` -- src/bicgstabl.jl:25-73.  ``ops``: the L1 / L2 entries of the statement-by-statement
+    branch (``DeviceKrylovOps`` by default; given: that branch over them)."""
+    _require_device("bicgstabl_iterator_", b.dtype, ops, x, A, b)
     reltol = _default_reltol(b) if reltol is None else reltol
     max_mv_products = A.size(2) if max_mv_products is None else max_mv_products
     return BiCGStabIterable(x, A, b, l, Pl=Pl, max_mv_products=max_mv_products, abstol=abstol, reltol=reltol,
-                            initial_zero=initial_zero, r_shadow=r_shadow, fused=fused)
+                            initial_zero=initial_zero, r_shadow=r_shadow, fused=fused, ops=ops)
 
 
 def bicgstabl_(x: HipVector, A: HipCSR, b: HipVector, l: int = 2, *, abstol=0.0, reltol=None, max_mv_products=None,
@@ -1524,24 +1608,25 @@ def bicgstabl(A: HipCSR, b: HipVector, l: int = 2, **kwargs):
 # ==============================================================================================
 # chebyshev.jl, minres.jl  (composed from the L1 entry points)
 # ==============================================================================================
-def givens_algorithm(f, g, dtype=np.float64):
-    """``LinearAlgebra.givensAlgorithm(f, g)`` -> (c, s, r) on the host -- src/minres.jl:129, src/hessenberg.jl:24 (complex: c is
-    real, ``[c s; -conj(s) c] * [f; g] = [r; 0]``)."""
-    fa, ga, out = np.asarray([f], dtype), np.asarray([g], dtype), np.zeros(3, dtype)
-    check(lib().mik_givens(dtype_code(dtype), fa.ctypes.data_as(_vp), ga.ctypes.data_as(_vp), out.ctypes.data_as(_vp)), "mik_givens", None)
-    return (out[0].real if _is_complex(dtype) else out[0]), out[1], out[2]
-
-
 class ChebyshevIterable:
     """``ChebyshevIterable`` -- src/chebyshev.jl:5-22, construction per ``chebyshev_iterable!`` (:59-91).  Follows the
     v0.9.4 source as written: ``start = 0`` with the ``iteration == 1`` branch (:26, :37) and
     ``u .= c .+ beta .* c`` (:45)."""
 
-    def __init__(self, x, A, b, lmin, lmax, *, abstol, reltol, maxiter, Pl=None, initially_zero=False, fused=True):
-        T = x.dtype.type
+    def __init__(self, x, A, b, lmin, lmax, *, abstol, reltol, maxiter, Pl=None, initially_zero=False, fused=True, ops=None):
+        T = _real_dtype(x.dtype).type     # l_avg, l_diff, alpha and beta are reals of the component type (alpha::realT, :8)
         self.fused = bool(fused)          # one sweep per statement group (same bits) instead of one L1 call per statement
+        self.generic = ops is not None or _is_complex(x.dtype)
+        self.ops = ops = DeviceKrylovOps if ops is None else ops
+        mul_, norm = ops.mul_, ops.norm
         self.Pl = Identity() if Pl is None else Pl
-        if not isinstance(self.Pl, (Identity, JacobiPrec)):
+        if self.generic:                  # Identity, or any object with ldiv_(y, x): that one through the statement-by-statement branch
+            _refuse_complex_jacobi(x.dtype, self.Pl)
+            if not isinstance(self.Pl, (Identity, JacobiPrec)):
+                if not callable(getattr(self.Pl, "ldiv_", None)):
+                    raise MikError(5, "chebyshev_iterable_", "Pl needs ldiv_(y, x) (docs/src/preconditioning.md:5-14)")
+                self.fused = False
+        elif not isinstance(self.Pl, (Identity, JacobiPrec)):
             raise MikError(5, "chebyshev_iterable_", "Pl must be Identity() or a diagonal JacobiPrec on the device path")
         self.A, self.x = A, x
         self.l_avg = (T(lmax) + T(lmin)) / T(2)                              # :66
@@ -1573,7 +1658,9 @@ class ChebyshevIterable:
         iteration = 0 if iteration is None else iteration
         if self.done(iteration):
             return None
-        T = self.x.dtype.type
+        T = _real_dtype(self.x.dtype).type
+        ops = self.ops
+        mul_, norm = ops.mul_, ops.norm
         if self.fused:
             first = iteration == 1                                           # :37
             if first:
@@ -1583,13 +1670,11 @@ class ChebyshevIterable:
                 h = (self.l_diff * self.alpha) / T(2)
                 beta = h * h                                                 # :41
                 self.alpha = T(1) / (self.l_avg - beta)                      # :42
-            _, pb = _scalar(self.x.dtype, beta)
-            d = self.Pl.diagonal.ptr if isinstance(self.Pl, JacobiPrec) else None
-            check(lib().mik_cheb_direction(self.x.ctx.handle, self.x.code, self.x.n, _vp(self.r.ptr), _vp(d), pb, int(first), _vp(self.u.ptr)),
-                  "mik_cheb_direction", self.x.ctx.handle)                   # :35-45
+            d = self.Pl.diagonal if isinstance(self.Pl, JacobiPrec) else None
+            ops.cheb_direction_(self.u, self.r, beta, first, d)              # :35-45
             mul_(self.c, self.A, self.u)                                     # :48
             self.mv_products += 1
-            self.resnorm = axpy2_nrm2_(self.alpha, self.u, self.x, self.c, self.r, hints=7)   # :51-54; x, c, u are not re-read
+            self.resnorm = ops.axpy2_nrm2_(self.alpha, self.u, self.x, self.c, self.r, hints=7)   # :51-54; x, c, u are not re-read
             return self.resnorm, iteration + 1
         self.Pl.ldiv_(self.c, self.r)                                        # :35
         if iteration == 1:                                                   # :37
@@ -1614,11 +1699,11 @@ class ChebyshevIterable:
             yield resnorm
 
 
-def chebyshev_iterable_(x, A, b, lmin, lmax, *, abstol=0.0, reltol=None, maxiter=None, Pl=None, initially_zero=False, fused=True):
-    """``chebyshev_iterable!`` -- src/chebyshev.jl:59-91."""
-    _lib.real_dtype_code(b.dtype, "chebyshev_iterable")
+def chebyshev_iterable_(x, A, b, lmin, lmax, *, abstol=0.0, reltol=None, maxiter=None, Pl=None, initially_zero=False, fused=True, ops=None):
+    """``chebyshev_iterable!`` -- src/chebyshev.jl:59-91.  ``ops``: as in ``bicgstabl_iterator_``."""
+    _require_device("chebyshev_iterable_", b.dtype, ops, x, A, b)
     return ChebyshevIterable(x, A, b, lmin, lmax, abstol=abstol, reltol=_default_reltol(b) if reltol is None else reltol,
-                             maxiter=A.size(2) if maxiter is None else maxiter, Pl=Pl, initially_zero=initially_zero, fused=fused)
+                             maxiter=A.size(2) if maxiter is None else maxiter, Pl=Pl, initially_zero=initially_zero, fused=fused, ops=ops)
 
 
 def _drive(iterable, history, log, verbose, per_iter_mvps=None):
@@ -1635,14 +1720,15 @@ def _drive(iterable, history, log, verbose, per_iter_mvps=None):
 
 
 def chebyshev_(x, A, b, lmin, lmax, *, abstol=0.0, reltol=None, Pl=None, maxiter=None, log=False, verbose=False,
-               initially_zero=False):
+               initially_zero=False, fused=True, ops=None):
     """``chebyshev!(x, A, b, lmin, lmax; ...)`` -- src/chebyshev.jl:142-169."""
     reltol = _default_reltol(b) if reltol is None else reltol
     maxiter = A.size(2) if maxiter is None else maxiter
     history = ConvergenceHistory(partial=not log)
     history["abstol"], history["reltol"] = abstol, reltol
     history.reserve_("resnorm", maxiter)                                     # :154
-    it = chebyshev_iterable_(x, A, b, lmin, lmax, abstol=abstol, reltol=reltol, maxiter=maxiter, Pl=Pl, initially_zero=initially_zero)
+    it = chebyshev_iterable_(x, A, b, lmin, lmax, abstol=abstol, reltol=reltol, maxiter=maxiter, Pl=Pl, initially_zero=initially_zero,
+                             fused=fused, ops=ops)
     history.mvps = it.mv_products                                            # :160
     _drive(it, history, log, verbose)
     return (x, history) if log else x
@@ -1654,30 +1740,37 @@ def chebyshev(A, b, lmin, lmax, **kwargs):
 
 
 class MINRESIterable:
-    """``MINRESIterable`` -- src/minres.jl:6-36, construction per ``minres_iterable!`` (:38-87); real element types."""
+    """``MINRESIterable`` -- src/minres.jl:6-36, construction per ``minres_iterable!`` (:38-87).  A complex operator, or ``ops`` given,
+    runs the statement-by-statement branch over ``ops`` (with the fused sweeps when ``fused``; the whole-iteration handle is real only).
+    Hermitian: ``H``, ``rhs``, c and s are real (``HessenbergT = real(T)``, :46), only ``proj`` is complex; skew-Hermitian: all of type T."""
 
-    def __init__(self, x, A, b, *, initially_zero=False, skew_hermitian=False, abstol, reltol, maxiter, fused=True):
-        T = x.dtype.type
+    def __init__(self, x, A, b, *, initially_zero=False, skew_hermitian=False, abstol, reltol, maxiter, fused=True, ops=None):
+        RT = _real_dtype(x.dtype).type
         self.fused = bool(fused)          # one sweep per statement group (same bits) instead of one L1 call per statement
+        self.generic = ops is not None or _is_complex(x.dtype)
+        self.ops = ops = DeviceKrylovOps if ops is None else ops
+        mul_, norm = ops.mul_, ops.norm
         self.A, self.x, self.skew = A, x, bool(skew_hermitian)
+        self.ht = x.dtype if self.skew else _real_dtype(x.dtype)           # HessenbergT, :46
+        HT = self.ht.type
         self.v_prev, self.v_curr, self.v_next = x.similar(), x.similar().copyto_(b), x.similar()       # :47-50
         self.w_prev, self.w_curr, self.w_next = x.zero(), x.zero(), x.zero()                            # :51-53
         self.mv_products = 0
         if not initially_zero:
             mul_(self.v_next, A, x)                                          # :60
-            self.v_curr.axpy_(T(-1), self.v_next)                            # :61
+            self.v_curr.axpy_(RT(-1), self.v_next)                           # :61
             self.mv_products = 1
         self.resnorm = norm(self.v_curr)                                     # :65
-        self.tol = max(T(reltol) * self.resnorm, T(abstol))                  # :66
-        self.H = np.zeros(4, x.dtype)                                        # :70
-        self.rhs = np.array([self.resnorm, 0], x.dtype)                      # :71
-        self.v_curr.scal_(T(1) / self.resnorm)                               # :74
-        self.c_prev, self.s_prev, self.c_curr, self.s_curr = T(1), T(0), T(1), T(0)
+        self.tol = max(RT(reltol) * self.resnorm, RT(abstol))                # :66
+        self.H = np.zeros(4, self.ht)                                        # :70
+        self.rhs = np.array([self.resnorm, 0], self.ht)                      # :71
+        self.v_curr.scal_(RT(1) / self.resnorm)                              # :74
+        self.c_prev, self.s_prev, self.c_curr, self.s_curr = HT(1), HT(0), HT(1), HT(0)
         self.maxiter = int(maxiter)
-        # fused, a HipCSR operator: the whole iteration is one C call with H, rhs and the rotations on the device (mik_minres_step);
+        # fused, a real HipCSR operator: the whole iteration is one C call with H, rhs and the rotations on the device (mik_minres_step);
         # the host copies above then stay at their initial values
         self._step = None
-        if self.fused and isinstance(A, HipCSR):
+        if self.fused and isinstance(A, HipCSR) and not self.generic:
             h = _vp()
             check(lib().mik_minres_create(x.ctx.handle, A.handle, _vp(x.ptr), _vp(self.v_prev.ptr), _vp(self.v_curr.ptr), _vp(self.v_next.ptr),
                                           _vp(self.w_prev.ptr), _vp(self.w_curr.ptr), _vp(self.w_next.ptr), float(self.resnorm), int(self.skew), C.byref(h)),
@@ -1707,7 +1800,10 @@ class MINRESIterable:
         iteration = 1 if iteration is None else iteration
         if self.done(iteration):
             return None
-        T, H, rhs = self.x.dtype.type, self.H, self.rhs
+        RT, HT, H, rhs = _real_dtype(self.x.dtype).type, self.ht.type, self.H, self.rhs
+        ops = self.ops
+        mul_, dot, norm = ops.mul_, ops.dot, ops.norm
+        cx = _is_complex(self.x.dtype)
         if self._step is not None:
             out = np.zeros(1, self.x.dtype)
             check(lib().mik_minres_step(self._step, int(iteration), out.ctypes.data_as(_vp)), "mik_minres_step", self.x.ctx.handle)
@@ -1718,42 +1814,45 @@ class MINRESIterable:
             return self.resnorm, iteration + 1
         mul_(self.v_next, self.A, self.v_curr)                               # :102
         if self.fused:
-            proj = axpy_dot_(-H[1], self.v_prev if iteration > 1 else None, self.v_next, self.v_curr, hints=1)   # :104, :107; v_prev is dead
-            H[2] = proj
-            H[3] = axpy_dot_(-proj, self.v_curr, self.v_next, None)          # :109, :112
+            if self.x.dtype == np.complex64:                                 # the fused alpha + dot sweep measured no faster than axpy + dot at
+                if iteration > 1:                                            # ComplexF32: the chain, same bits
+                    self.v_next.axpy_(-H[1], self.v_prev)                    # :104
+                proj = dot(self.v_curr, self.v_next)                         # :107
+            else:
+                proj = ops.axpy_dot_(-H[1], self.v_prev if iteration > 1 else None, self.v_next, self.v_curr, hints=1)   # :104, :107; v_prev is dead
+            H[2] = proj.real if cx and not self.skew else proj               # :110
+            nrm = ops.axpy_dot_(-proj, self.v_curr, self.v_next, None)       # :109, :112
         else:
             if iteration > 1:
                 self.v_next.axpy_(-H[1], self.v_prev)                        # :104
             proj = dot(self.v_curr, self.v_next)                             # :107
-            H[2] = proj
+            H[2] = proj.real if cx and not self.skew else proj               # :110
             self.v_next.axpy_(-proj, self.v_curr)                            # :109
-            H[3] = norm(self.v_next)                                         # :112
-            self.v_next.scal_(T(1) / H[3])                                   # :113
-        inv_h3 = T(1) / H[3]
+            nrm = norm(self.v_next)                                          # :112
+        H[3] = nrm
+        inv_h3 = HT(RT(1) / nrm)                                             # inv(H[4]), :115: a real, carried in HessenbergT
+        if not self.fused:
+            self.v_next.scal_(inv_h3)                                        # :113
         if iteration > 2:                                                    # :116-119
             H[0] = self.s_prev * H[1]
             H[1] = self.c_prev * H[1]
         if iteration > 1:                                                    # :122-126
-            tmp = -self.s_curr * H[1] + self.c_curr * H[2]
+            tmp = -np.conj(self.s_curr) * H[1] + self.c_curr * H[2]          # :125
             H[1] = self.c_curr * H[1] + self.s_curr * H[2]
             H[2] = tmp
-        c, s, H[2] = givens_algorithm(H[2], H[3], self.x.dtype)              # :129
-        rhs[1] = -s * rhs[0]                                                 # :132
+        c, s, H[2] = ops.givens_algorithm(H[2], H[3], self.ht)               # :129
+        rhs[1] = -np.conj(s) * rhs[0]                                        # :132
         rhs[0] = c * rhs[0]                                                  # :133
         if self.fused:                                                       # :113, :136-142 in one sweep
-            dt = self.x.dtype
-            sc = [_scalar(dt, v) for v in (inv_h3, -H[1], -H[0], T(1) / H[2], rhs[0])]
-            check(lib().mik_minres_update(self.x.ctx.handle, self.x.code, self.x.n, sc[0][1], _vp(self.v_next.ptr), _vp(self.v_curr.ptr),
-                                          sc[1][1], _vp(self.w_curr.ptr if iteration > 1 else None),
-                                          sc[2][1], _vp(self.w_prev.ptr if iteration > 2 else None),
-                                          sc[3][1], _vp(self.w_next.ptr), sc[4][1], _vp(self.x.ptr), 3), "mik_minres_update", self.x.ctx.handle)
+            ops.minres_update_(self.x, self.v_next, self.v_curr, self.w_curr if iteration > 1 else None, self.w_prev if iteration > 2 else None,
+                               self.w_next, inv_h3, -H[1], -H[0], HT(1) / H[2], rhs[0], hints=3)
         else:
             self.w_next.copyto_(self.v_curr)                                 # :136
             if iteration > 1:
                 self.w_next.axpy_(-H[1], self.w_curr)                        # :137
             if iteration > 2:
                 self.w_next.axpy_(-H[0], self.w_prev)                        # :138
-            self.w_next.scal_(T(1) / H[2])                                   # :139
+            self.w_next.scal_(HT(1) / H[2])                                  # :139
             self.x.axpy_(rhs[0], self.w_next)                                # :142
         self.v_prev, self.v_curr, self.v_next = self.v_curr, self.v_next, self.v_prev       # :145
         self.w_prev, self.w_curr, self.w_next = self.w_curr, self.w_next, self.w_prev       # :146
@@ -1779,15 +1878,16 @@ class MINRESIterable:
             pass
 
 
-def minres_iterable_(x, A, b, *, initially_zero=False, skew_hermitian=False, abstol=0.0, reltol=None, maxiter=None, fused=True):
-    """``minres_iterable!`` -- src/minres.jl:38-87."""
-    _lib.real_dtype_code(b.dtype, "minres_iterable")
+def minres_iterable_(x, A, b, *, initially_zero=False, skew_hermitian=False, abstol=0.0, reltol=None, maxiter=None, fused=True, ops=None):
+    """``minres_iterable!`` -- src/minres.jl:38-87.  ``ops``: as in ``bicgstabl_iterator_``."""
+    _require_device("minres_iterable_", b.dtype, ops, x, A, b)
     return MINRESIterable(x, A, b, initially_zero=initially_zero, skew_hermitian=skew_hermitian, abstol=abstol,
                           reltol=_default_reltol(b) if reltol is None else reltol, maxiter=A.size(2) if maxiter is None else maxiter,
-                          fused=fused)
+                          fused=fused, ops=ops)
 
 
-def minres_(x, A, b, *, skew_hermitian=False, verbose=False, log=False, abstol=0.0, reltol=None, maxiter=None, initially_zero=False):
+def minres_(x, A, b, *, skew_hermitian=False, verbose=False, log=False, abstol=0.0, reltol=None, maxiter=None, initially_zero=False,
+            fused=True, ops=None):
     """``minres!(x, A, b; ...)`` -- src/minres.jl:197-230."""
     reltol = _default_reltol(b) if reltol is None else reltol
     maxiter = A.size(2) if maxiter is None else maxiter
@@ -1795,7 +1895,8 @@ def minres_(x, A, b, *, skew_hermitian=False, verbose=False, log=False, abstol=0
     history["abstol"], history["reltol"] = abstol, reltol
     if log:
         history.reserve_("resnorm", maxiter)
-    it = minres_iterable_(x, A, b, skew_hermitian=skew_hermitian, abstol=abstol, reltol=reltol, maxiter=maxiter, initially_zero=initially_zero)
+    it = minres_iterable_(x, A, b, skew_hermitian=skew_hermitian, abstol=abstol, reltol=reltol, maxiter=maxiter, initially_zero=initially_zero,
+                          fused=fused, ops=ops)
     mv0 = it.mv_products
     if log:
         history.mvps = mv0                                                   # :211

@@ -30,6 +30,15 @@ int mik_c_xpby(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void *be
 int mik_c_scal(mik_ctx *ctx, int dtype, int64_t n, const void *alpha, void *x);
 int mik_c_orthogonalize(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv, void *w, void *h, void *nrm, int method);
 int mik_c_gemv_n(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv, const void *c, const void *alpha, void *y);
+// what bicgstabl, minres and chebyshev stand on; h, M, gamma, out: host memory
+int mik_c_gemv_t(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv, const void *w, void *h);
+int mik_c_gram(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv, void *M);
+// x != NULL or z != NULL; real_alpha needs z != NULL (the other forms are the real entry over 2 n and never come here)
+int mik_c_axpy_dot(mik_ctx *ctx, int dtype, int64_t n, int real_alpha, const void *alpha, const void *x, void *y, const void *z, void *out);
+int mik_c_minres_update(mik_ctx *ctx, int dtype, int64_t n, const void *inv_h3, void *v_next, const void *v_curr, const void *neg_h1, const void *w_curr,
+                        const void *neg_h0, const void *w_prev, const void *inv_h2, void *w_next, const void *rhs0, void *x);
+int mik_c_bicgstab_mr_update(mik_ctx *ctx, int dtype, int64_t n, int l, void *us, int64_t ldu, void *rs, int64_t ldr, void *x, const void *gamma, void *out);
 // host
+int mik_c_lu_solve(int dtype, void *A, int64_t lda, int n, void *b);
 int mik_c_givens(int dtype, const void *f, const void *g, void *out);
 int mik_c_hessenberg_ldiv(int dtype, void *H, int64_t ldh, int width, void *rhs);

@@ -14,6 +14,7 @@
 #include "mik_complex.h"
 #include "mik_kernels.h"
 #include "mik_spmv.h"
+#include "mik_dense_cmul.h"
 
 #include <new>
 #include <vector>
@@ -719,4 +720,418 @@ int mik_c_hessenberg_ldiv(int dtype, void *H, int64_t ldh, int width, void *rhs)
     if (dtype == MIK_C64) c_hessenberg_ldiv<double>((HC<double> *)H, ldh, width, (HC<double> *)rhs);
     else c_hessenberg_ldiv<float>((HC<float> *)H, ldh, width, (HC<float> *)rhs);
     return MIK_OK;
+}
+
+// =============================================================================================
+// what bicgstabl, minres and chebyshev stand on
+// =============================================================================================
+// The thread's share of dot(a, b) = sum conj(a_i) b_i over one segment held in registers: the products, the order (l ascending, then the
+// elements of a 16-byte group) and the two accumulators of OpCDot.
+template <typename R>
+__device__ __forceinline__ void cseg_dot(const R (&a)[SEG_REGS<R>], const R (&b)[SEG_REGS<R>], int64_t base, int64_t n2, R &re, R &im)
+{
+    constexpr int W = VT<R>::W;
+    R a0 = R(0), a1 = R(0);
+#pragma unroll
+    for (int l = 0; l < MIK_RED_L; ++l)
+#pragma unroll
+        for (int e = 0; e < W; e += 2) {
+            const int q = l * W + e;
+            if (base + (int64_t)l * MIK_BLOCK * W + e < n2) {
+                const R p = a[q] * b[q], r = a[q + 1] * b[q + 1], s = a[q] * b[q + 1], t = a[q + 1] * b[q];
+                const R vr = p + r, vi = s - t;
+                a0 = a0 + vr;
+                a1 = a1 + vi;
+            }
+        }
+    re = a0;
+    im = a1;
+}
+
+// ... and of the sum of squares of a: ar^2 then ai^2 into one accumulator in memory order -- the bits mik_nrm2 squares over the 2 n reals
+template <typename R> __device__ __forceinline__ R cseg_sumsq(const R (&a)[SEG_REGS<R>], int64_t base, int64_t n2)
+{
+    constexpr int W = VT<R>::W;
+    R acc = R(0);
+#pragma unroll
+    for (int l = 0; l < MIK_RED_L; ++l)
+#pragma unroll
+        for (int e = 0; e < W; ++e)
+            if (base + (int64_t)l * MIK_BLOCK * W + e < n2) { const R p = a[l * W + e] * a[l * W + e]; acc = acc + p; }
+    return acc;
+}
+
+// ---- mik_gemv_t: h[j] = dot(V[:, j], w) -- mul!(h, adjoint(V), w), one column of src/bicgstabl.jl:121 --------------------------------
+// k_cdense_t (csrc/mik_dense_cmul.h) is this sweep: a workgroup holds its segment of w and reads every column against it, each column's
+// two sums with the bits of the complex mik_dot.  Launched here on the basis instead of a mik_dense; the segment sums go to ctx->partials.
+template <typename R> static int c_gemv_t(mik_ctx *ctx, int64_t n, int k, const R *V, int64_t ldv, const R *w, R *h)
+{
+    if (k == 0) return MIK_OK;
+    if ((size_t)(2 * k) * sizeof(R) > mik_ctx::COEF_SAFE_SLOT) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_gemv_t: too many columns (k = %d) for a complex basis", k);
+    const int64_t nseg = mik_nseg<R>(2 * n);
+    if (nseg == 0) { memset(h, 0, sizeof(R) * 2 * (size_t)k); return MIK_OK; }
+    MIK_TRY(mik_ensure_partials(ctx, sizeof(R) * 2 * (size_t)k * (size_t)nseg));
+    const bool vec = mik_aligned16(V) && (2 * ldv) % VT<R>::W == 0 && mik_aligned16(w);
+    const int64_t gx = std::min<int64_t>(nseg, mik_max_grid(ctx));
+    const int64_t batches = ((int64_t)k + MIK_CDM_TCOLS - 1) / MIK_CDM_TCOLS;
+    const int64_t gy = std::min<int64_t>(batches, std::max<int64_t>(1, std::min<int64_t>(65535, 4 * (int64_t)mik_cus(ctx) / gx)));
+    const dim3 grid((unsigned)gx, (unsigned)gy);
+    R *part = (R *)ctx->partials;
+    if (vec) hipLaunchKernelGGL((k_cdense_t<R, true, false>), grid, dim3(MIK_BLOCK), 0, ctx->stream, 2 * n, nseg, (int64_t)k, V, ldv, w, part);
+    else hipLaunchKernelGGL((k_cdense_t<R, false, false>), grid, dim3(MIK_BLOCK), 0, ctx->stream, 2 * n, nseg, (int64_t)k, V, ldv, w, part);
+    MIK_LAUNCH_CHECK(ctx);
+    MIK_TRY(c_finalize<R>(ctx, nseg, 2 * k, (R *)ctx->coef));
+    return mik_read_scalars<R>(ctx, (const R *)ctx->coef, 2 * k, h);
+}
+
+int mik_c_gemv_t(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv, const void *w, void *h)
+{
+    return dtype == MIK_C64 ? c_gemv_t<double>(ctx, n, k, (const double *)V, ldv, (const double *)w, (double *)h)
+                            : c_gemv_t<float>(ctx, n, k, (const float *)V, ldv, (const float *)w, (float *)h);
+}
+
+// ---- mik_gram: M = V' V for K <= 5 columns in one pass -- src/bicgstabl.jl:120 --------------------------------------------------------
+// The K segments stay in registers (K * SEG_REGS reals a lane); K * K sums a segment: re of the K diagonal pairs (their im is a sum of
+// xr xi - xi xr = +0), then re and im of the pairs r < c in row-major order of the upper triangle.  seg_out: [K * K][nseg].
+template <typename R, bool VEC, int K>
+__global__ __launch_bounds__(MIK_BLOCK) void k_cgram(int64_t n2, int64_t nseg, const R *__restrict__ V, int64_t ldv2, R *__restrict__ seg_out)
+{
+    constexpr int NS = K * K;
+    constexpr int64_t SEG = (int64_t)MIK_BLOCK * SEG_REGS<R>;
+    __shared__ R lds[NS][4];
+    for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const int64_t base = s * SEG + (int64_t)VT<R>::W * threadIdx.x;
+        R cr[K][SEG_REGS<R>];
+#pragma unroll
+        for (int j = 0; j < K; ++j) seg_load<R, VEC>(V + (int64_t)j * ldv2, base, n2, 0, cr[j]);
+        int p = K;
+#pragma unroll
+        for (int r = 0; r < K; ++r) {
+            R re, im;
+            cseg_dot<R>(cr[r], cr[r], base, n2, re, im);
+            pair_put(re, lds[r]);
+#pragma unroll
+            for (int c = r + 1; c < K; ++c) {
+                cseg_dot<R>(cr[r], cr[c], base, n2, re, im);
+                pair_put(re, lds[p]);
+                pair_put(im, lds[p + 1]);
+                p += 2;
+            }
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < NS) seg_out[(int64_t)threadIdx.x * nseg + s] = pair_total(lds[threadIdx.x]);
+        __syncthreads();
+    }
+}
+
+template <typename R, int K> static int launch_cgram_k(mik_ctx *ctx, int64_t n, const R *V, int64_t ldv)
+{
+    const bool vec = mik_aligned16(V) && (2 * ldv) % VT<R>::W == 0;
+    return launch_segments<R>(ctx, 2 * n, vec, 0, [&](auto v, int grid, int64_t nseg) {
+        hipLaunchKernelGGL((k_cgram<R, decltype(v)::value, K>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, 2 * n, nseg, V, 2 * ldv, (R *)ctx->partials);
+    });
+}
+
+template <typename R> static int c_gram(mik_ctx *ctx, int64_t n, int k, const R *V, int64_t ldv, R *M)
+{
+    const int ns = k * k;
+    const int64_t nseg = mik_nseg<R>(2 * n);
+    if (nseg == 0) { memset(M, 0, sizeof(R) * 2 * (size_t)ns); return MIK_OK; }
+    MIK_TRY(mik_ensure_partials(ctx, sizeof(R) * (size_t)ns * (size_t)nseg));
+    switch (k) {
+    case 1: MIK_TRY((launch_cgram_k<R, 1>(ctx, n, V, ldv))); break;
+    case 2: MIK_TRY((launch_cgram_k<R, 2>(ctx, n, V, ldv))); break;
+    case 3: MIK_TRY((launch_cgram_k<R, 3>(ctx, n, V, ldv))); break;
+    case 4: MIK_TRY((launch_cgram_k<R, 4>(ctx, n, V, ldv))); break;
+    default: MIK_TRY((launch_cgram_k<R, 5>(ctx, n, V, ldv))); break;
+    }
+    MIK_TRY(c_finalize<R>(ctx, nseg, ns, (R *)ctx->coef));
+    R out[25];
+    MIK_TRY(mik_read_scalars<R>(ctx, (const R *)ctx->coef, ns, out));
+    auto at = [&](int r, int c) { return M + 2 * ((size_t)c * k + r); };
+    int p = k;
+    for (int r = 0; r < k; ++r) {
+        at(r, r)[0] = out[r];
+        at(r, r)[1] = R(0);
+        for (int c = r + 1; c < k; ++c) {
+            at(r, c)[0] = out[p]; at(r, c)[1] = out[p + 1];
+            at(c, r)[0] = out[p]; at(c, r)[1] = -out[p + 1];                // the lower triangle: the conjugate
+            p += 2;
+        }
+    }
+    return MIK_OK;
+}
+
+int mik_c_gram(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv, void *M)
+{
+    return dtype == MIK_C64 ? c_gram<double>(ctx, n, k, (const double *)V, ldv, (double *)M) : c_gram<float>(ctx, n, k, (const float *)V, ldv, (float *)M);
+}
+
+// ---- mik_axpy_dot: y .+= alpha .* x, then dot(z, y) or the sum of squares of y -- src/minres.jl:106+109, :111+114 ---------------------
+// REALA: alpha is real (real x complex: a xr, a xi); UPD: x is given; DOT: a0 + a1 i = dot(z, y), else a0 = the sum of yr^2, yi^2
+template <typename R, bool REALA, bool UPD, bool DOT> struct OpCAxpyDot {
+    static constexpr bool LOADX = UPD, LOADZ = DOT, LOADY = true, STORE = UPD;
+    static constexpr int NRED = DOT ? 2 : 1;
+    const R *x, *z; R *y; R ar, ai;
+    __device__ __forceinline__ void prepare() {}
+    __device__ __forceinline__ void elem(R xr, R xi, R zr, R zi, R &yr, R &yi, R &a0, R &a1) const
+    {
+        if (UPD) {
+            if (REALA) {
+                const R p = ar * xr, q = ar * xi;
+                yr = yr + p;
+                yi = yi + q;
+            } else {
+                const CxVal<R> p = cx_mul(ar, ai, xr, xi);
+                yr = yr + p.re;
+                yi = yi + p.im;
+            }
+        }
+        if (DOT) {
+            const R p = zr * yr, q = zi * yi, s = zr * yi, t = zi * yr;
+            const R re = p + q, im = s - t;
+            a0 = a0 + re;
+            a1 = a1 + im;
+        } else {
+            const R p = yr * yr;
+            a0 = a0 + p;
+            const R q = yi * yi;
+            a0 = a0 + q;
+        }
+    }
+};
+
+template <typename R, bool REALA, bool UPD, bool DOT>
+static int c_axpy_dot_form(mik_ctx *ctx, int64_t n, const R *alpha, const R *x, R *y, const R *z, R *out)
+{
+    const int64_t nseg = mik_nseg<R>(2 * n);
+    MIK_TRY(mik_ensure_partials(ctx, sizeof(R) * 2 * (size_t)std::max<int64_t>(nseg, 1)));
+    OpCAxpyDot<R, REALA, UPD, DOT> op{x, z, y, UPD ? alpha[0] : R(0), (UPD && !REALA) ? alpha[1] : R(0)};
+    const bool vec = mik_aligned16(y) && (!UPD || mik_aligned16(x)) && (!DOT || mik_aligned16(z));
+    MIK_TRY((launch_cvec<R>(ctx, n, op, vec, (R *)ctx->partials)));
+    MIK_TRY(c_finalize<R>(ctx, nseg, DOT ? 2 : 1, (R *)ctx->coef));
+    if (DOT) return mik_read_scalars<R>(ctx, (const R *)ctx->coef, 2, out);
+    R ss;
+    MIK_TRY(mik_read_scalars<R>(ctx, (const R *)ctx->coef, 1, &ss));
+    if (mik_nrm_in_range(ss)) { *out = (R)std::sqrt(ss); return MIK_OK; }
+    return mik_safe_norm_slow<R>(ctx, 2 * n, y, out);                       // include/mik.h "Norms"
+}
+
+// real_alpha with z == NULL never comes here (the real entry over 2 n); x == NULL with z == NULL neither
+template <typename R> static int c_axpy_dot(mik_ctx *ctx, int64_t n, bool real_alpha, const R *alpha, const R *x, R *y, const R *z, R *out)
+{
+    if (!z) return c_axpy_dot_form<R, false, true, false>(ctx, n, alpha, x, y, z, out);
+    if (!x) return c_axpy_dot_form<R, false, false, true>(ctx, n, alpha, x, y, z, out);
+    return real_alpha ? c_axpy_dot_form<R, true, true, true>(ctx, n, alpha, x, y, z, out) : c_axpy_dot_form<R, false, true, true>(ctx, n, alpha, x, y, z, out);
+}
+
+int mik_c_axpy_dot(mik_ctx *ctx, int dtype, int64_t n, int real_alpha, const void *alpha, const void *x, void *y, const void *z, void *out)
+{
+    return dtype == MIK_C64 ? c_axpy_dot<double>(ctx, n, real_alpha != 0, (const double *)alpha, (const double *)x, (double *)y, (const double *)z, (double *)out)
+                            : c_axpy_dot<float>(ctx, n, real_alpha != 0, (const float *)alpha, (const float *)x, (float *)y, (const float *)z, (float *)out);
+}
+
+// ---- mik_minres_update with five complex scalars (skew-Hermitian) -- src/minres.jl:115, :138-144 --------------------------------------
+// per element, in statement order: v_next *= inv_h3; w = v_curr; w += neg_h1 w_curr; w += neg_h0 w_prev; w *= inv_h2; x += rhs0 w
+template <typename R> struct CMinresCoef { R inv_h3[2], neg_h1[2], neg_h0[2], inv_h2[2], rhs0[2]; };
+
+template <typename R, bool VEC>
+__global__ __launch_bounds__(MIK_BLOCK) void k_cminres_update(int64_t n2, int64_t nseg, R *__restrict__ v_next, const R *__restrict__ v_curr,
+                                                              const R *__restrict__ w_curr, const R *__restrict__ w_prev, R *__restrict__ w_next,
+                                                              R *__restrict__ x, CMinresCoef<R> cf)
+{
+    constexpr int64_t SEG = (int64_t)MIK_BLOCK * SEG_REGS<R>;
+    for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const int64_t base = s * SEG + (int64_t)VT<R>::W * threadIdx.x;
+        R vn[SEG_REGS<R>], w[SEG_REGS<R>], xx[SEG_REGS<R>], t[SEG_REGS<R>];
+        seg_load<R, VEC>(v_next, base, n2, 0, vn);
+        seg_load<R, VEC>(v_curr, base, n2, 0, w);
+        seg_load<R, VEC>(x, base, n2, 0, xx);
+#pragma unroll
+        for (int q = 0; q < SEG_REGS<R>; q += 2) {
+            const CxVal<R> p = cx_mul(vn[q], vn[q + 1], cf.inv_h3[0], cf.inv_h3[1]);
+            vn[q] = p.re;
+            vn[q + 1] = p.im;
+        }
+        seg_store<R, VEC>(v_next, base, n2, vn);
+        if (w_curr) {
+            seg_load<R, VEC>(w_curr, base, n2, 0, t);
+#pragma unroll
+            for (int q = 0; q < SEG_REGS<R>; q += 2) {
+                const CxVal<R> p = cx_mul(cf.neg_h1[0], cf.neg_h1[1], t[q], t[q + 1]);
+                w[q] = w[q] + p.re;
+                w[q + 1] = w[q + 1] + p.im;
+            }
+        }
+        if (w_prev) {
+            seg_load<R, VEC>(w_prev, base, n2, 0, t);
+#pragma unroll
+            for (int q = 0; q < SEG_REGS<R>; q += 2) {
+                const CxVal<R> p = cx_mul(cf.neg_h0[0], cf.neg_h0[1], t[q], t[q + 1]);
+                w[q] = w[q] + p.re;
+                w[q + 1] = w[q + 1] + p.im;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < SEG_REGS<R>; q += 2) {
+            const CxVal<R> p = cx_mul(w[q], w[q + 1], cf.inv_h2[0], cf.inv_h2[1]);
+            w[q] = p.re;
+            w[q + 1] = p.im;
+            const CxVal<R> u = cx_mul(cf.rhs0[0], cf.rhs0[1], w[q], w[q + 1]);
+            xx[q] = xx[q] + u.re;
+            xx[q + 1] = xx[q + 1] + u.im;
+        }
+        seg_store<R, VEC>(w_next, base, n2, w);
+        seg_store<R, VEC>(x, base, n2, xx);
+    }
+}
+
+template <typename R>
+static int c_minres_update(mik_ctx *ctx, int64_t n, const R *inv_h3, R *v_next, const R *v_curr, const R *neg_h1, const R *w_curr, const R *neg_h0,
+                           const R *w_prev, const R *inv_h2, R *w_next, const R *rhs0, R *x)
+{
+    CMinresCoef<R> cf{};
+    cf.inv_h3[0] = inv_h3[0]; cf.inv_h3[1] = inv_h3[1];
+    if (w_curr) { cf.neg_h1[0] = neg_h1[0]; cf.neg_h1[1] = neg_h1[1]; }
+    if (w_prev) { cf.neg_h0[0] = neg_h0[0]; cf.neg_h0[1] = neg_h0[1]; }
+    cf.inv_h2[0] = inv_h2[0]; cf.inv_h2[1] = inv_h2[1];
+    cf.rhs0[0] = rhs0[0]; cf.rhs0[1] = rhs0[1];
+    const bool vec = mik_aligned16(v_next) && mik_aligned16(v_curr) && mik_aligned16(w_next) && mik_aligned16(x) && (!w_curr || mik_aligned16(w_curr)) &&
+                     (!w_prev || mik_aligned16(w_prev));
+    return launch_segments<R>(ctx, 2 * n, vec, 0, [&](auto v, int grid, int64_t nseg) {
+        hipLaunchKernelGGL((k_cminres_update<R, decltype(v)::value>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, 2 * n, nseg, v_next, v_curr, w_curr, w_prev,
+                           w_next, x, cf);
+    });
+}
+
+int mik_c_minres_update(mik_ctx *ctx, int dtype, int64_t n, const void *inv_h3, void *v_next, const void *v_curr, const void *neg_h1, const void *w_curr,
+                        const void *neg_h0, const void *w_prev, const void *inv_h2, void *w_next, const void *rhs0, void *x)
+{
+    if (dtype == MIK_C64)
+        return c_minres_update<double>(ctx, n, (const double *)inv_h3, (double *)v_next, (const double *)v_curr, (const double *)neg_h1, (const double *)w_curr,
+                                       (const double *)neg_h0, (const double *)w_prev, (const double *)inv_h2, (double *)w_next, (const double *)rhs0, (double *)x);
+    return c_minres_update<float>(ctx, n, (const float *)inv_h3, (float *)v_next, (const float *)v_curr, (const float *)neg_h1, (const float *)w_curr,
+                                  (const float *)neg_h0, (const float *)w_prev, (const float *)inv_h2, (float *)w_next, (const float *)rhs0, (float *)x);
+}
+
+// ---- mik_bicgstab_mr_update: the complex sibling of k_bicg_mr -- src/bicgstabl.jl:126-131 --------------------------------------------
+//   us_0 += sum_{j=1..l} tn_j us_j;  x += sum_{j=0..l-1} tp_{j+1} rs_j;  rs_0 += sum_{j=1..l} tn_j rs_j;  segment sums of |rs_0|^2
+// tn_j = (-1 + 0 i) gamma_j and tp_j = (1 + 0 i) gamma_j are formed on the host, as mik_gemv_n forms alpha c_j: the per-element operations
+// and their order are those of the three mik_gemv_n calls; x reads rs_0 before its update.
+template <typename R> struct CBicgGamma { R tn[16], tp[16]; };           // l <= 8 complex coefficients each
+
+template <typename R, bool VEC>
+__global__ __launch_bounds__(MIK_BLOCK) void k_cbicg_mr(int64_t n2, int64_t nseg, int l, R *__restrict__ us, int64_t ldu2, R *__restrict__ rs, int64_t ldr2,
+                                                        R *__restrict__ x, CBicgGamma<R> gm, R *__restrict__ seg_out)
+{
+    constexpr int64_t SEG = (int64_t)MIK_BLOCK * SEG_REGS<R>;
+    __shared__ R lds4[4];
+    for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const int64_t base = s * SEG + (int64_t)VT<R>::W * threadIdx.x;
+        R u0[SEG_REGS<R>], r0[SEG_REGS<R>], xx[SEG_REGS<R>];
+        seg_load<R, VEC>(us, base, n2, 0, u0);
+        seg_load<R, VEC>(rs, base, n2, 0, r0);
+        seg_load<R, VEC>(x, base, n2, 0, xx);
+#pragma unroll
+        for (int q = 0; q < SEG_REGS<R>; q += 2) {                         // x += gamma_1 rs_0 (the not yet updated residual)
+            const CxVal<R> p = cx_mul(gm.tp[0], gm.tp[1], r0[q], r0[q + 1]);
+            xx[q] = xx[q] + p.re;
+            xx[q + 1] = xx[q + 1] + p.im;
+        }
+        for (int j = 1; j <= l; ++j) {
+            R uj[SEG_REGS<R>], rj[SEG_REGS<R>];
+            seg_load<R, VEC>(us + (int64_t)j * ldu2, base, n2, 0, uj);
+            seg_load<R, VEC>(rs + (int64_t)j * ldr2, base, n2, 0, rj);
+            const R nr = gm.tn[2 * (j - 1)], ni = gm.tn[2 * (j - 1) + 1];
+#pragma unroll
+            for (int q = 0; q < SEG_REGS<R>; q += 2) {
+                const CxVal<R> p = cx_mul(nr, ni, uj[q], uj[q + 1]);
+                u0[q] = u0[q] + p.re;
+                u0[q + 1] = u0[q + 1] + p.im;
+                const CxVal<R> t = cx_mul(nr, ni, rj[q], rj[q + 1]);
+                r0[q] = r0[q] + t.re;
+                r0[q + 1] = r0[q + 1] + t.im;
+            }
+            if (j < l) {
+                const R pr = gm.tp[2 * j], pi = gm.tp[2 * j + 1];
+#pragma unroll
+                for (int q = 0; q < SEG_REGS<R>; q += 2) {
+                    const CxVal<R> p = cx_mul(pr, pi, rj[q], rj[q + 1]);
+                    xx[q] = xx[q] + p.re;
+                    xx[q + 1] = xx[q + 1] + p.im;
+                }
+            }
+        }
+        seg_store<R, VEC>(us, base, n2, u0);
+        seg_store<R, VEC>(rs, base, n2, r0);
+        seg_store<R, VEC>(x, base, n2, xx);
+        const R tot = block_tree_256(cseg_sumsq<R>(r0, base, n2), lds4);
+        if (threadIdx.x == 0) seg_out[s] = tot;
+    }
+}
+
+template <typename R> static int c_bicg_mr(mik_ctx *ctx, int64_t n, int l, R *us, int64_t ldu, R *rs, int64_t ldr, R *x, const R *gamma, R *out)
+{
+    const int64_t nseg = mik_nseg<R>(2 * n);
+    if (nseg == 0) { *out = R(0); return MIK_OK; }
+    MIK_TRY(mik_ensure_partials(ctx, sizeof(R) * (size_t)nseg));
+    CBicgGamma<R> gm{};
+    for (int j = 0; j < l; ++j) {
+        const CxVal<R> tn = cx_mul(R(-1), R(0), gamma[2 * j], gamma[2 * j + 1]), tp = cx_mul(R(1), R(0), gamma[2 * j], gamma[2 * j + 1]);
+        gm.tn[2 * j] = tn.re; gm.tn[2 * j + 1] = tn.im;
+        gm.tp[2 * j] = tp.re; gm.tp[2 * j + 1] = tp.im;
+    }
+    const bool vec = mik_aligned16(us) && mik_aligned16(rs) && mik_aligned16(x) && (2 * ldu) % VT<R>::W == 0 && (2 * ldr) % VT<R>::W == 0;
+    MIK_TRY((launch_segments<R>(ctx, 2 * n, vec, 0, [&](auto v, int grid, int64_t ns) {
+        hipLaunchKernelGGL((k_cbicg_mr<R, decltype(v)::value>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, 2 * n, ns, l, us, 2 * ldu, rs, 2 * ldr, x, gm,
+                           (R *)ctx->partials);
+    })));
+    MIK_TRY(c_finalize<R>(ctx, nseg, 1, (R *)ctx->coef));
+    R ss;
+    MIK_TRY(mik_read_scalars<R>(ctx, (const R *)ctx->coef, 1, &ss));
+    if (mik_nrm_in_range(ss)) { *out = (R)std::sqrt(ss); return MIK_OK; }
+    return mik_safe_norm_slow<R>(ctx, 2 * n, rs, out);                      // norm(rs[:, 1]) of a badly scaled residual
+}
+
+int mik_c_bicgstab_mr_update(mik_ctx *ctx, int dtype, int64_t n, int l, void *us, int64_t ldu, void *rs, int64_t ldr, void *x, const void *gamma, void *out)
+{
+    return dtype == MIK_C64 ? c_bicg_mr<double>(ctx, n, l, (double *)us, ldu, (double *)rs, ldr, (double *)x, (const double *)gamma, (double *)out)
+                            : c_bicg_mr<float>(ctx, n, l, (float *)us, ldu, (float *)rs, ldr, (float *)x, (const float *)gamma, (float *)out);
+}
+
+// ---- host: complex LU with partial pivoting -- lu!(view(M, L, L)); ldiv!(gamma, F, view(M, L, 1)), src/bicgstabl.jl:123-125 ------------
+// LAPACK getrf's pivot rule (izamax: the first maximum of |re| + |im|); divisions by Smith's scaling (hc_div)
+template <typename R> static int c_lu_solve(HC<R> *A, int64_t lda, int n, HC<R> *b)
+{
+    auto at = [&](int i, int j) -> HC<R> & { return A[(size_t)j * lda + i]; };
+    auto cabs1 = [](HC<R> z) { return std::fabs(z.re) + std::fabs(z.im); };
+    auto sub = [](HC<R> z, HC<R> w) { return HC<R>{z.re - w.re, z.im - w.im}; };
+    for (int j = 0; j < n; ++j) {
+        int p = j;
+        R best = cabs1(at(j, j));
+        for (int i = j + 1; i < n; ++i) { const R a = cabs1(at(i, j)); if (a > best) { best = a; p = i; } }
+        if (best == R(0)) return MIK_ERR_SINGULAR;
+        if (p != j) {
+            for (int c = 0; c < n; ++c) std::swap(at(j, c), at(p, c));
+            std::swap(b[j], b[p]);
+        }
+        const HC<R> piv = at(j, j);
+        for (int i = j + 1; i < n; ++i) {
+            const HC<R> m = hc_div(at(i, j), piv);
+            at(i, j) = m;
+            for (int c = j + 1; c < n; ++c) at(i, c) = sub(at(i, c), hc_mul(m, at(j, c)));
+            b[i] = sub(b[i], hc_mul(m, b[j]));
+        }
+    }
+    for (int j = n - 1; j >= 0; --j) {
+        b[j] = hc_div(b[j], at(j, j));
+        const HC<R> t = b[j];
+        for (int i = 0; i < j; ++i) b[i] = sub(b[i], hc_mul(t, at(i, j)));
+    }
+    return MIK_OK;
+}
+
+int mik_c_lu_solve(int dtype, void *A, int64_t lda, int n, void *b)
+{
+    return dtype == MIK_C64 ? c_lu_solve<double>((HC<double> *)A, lda, n, (HC<double> *)b) : c_lu_solve<float>((HC<float> *)A, lda, n, (HC<float> *)b);
 }

@@ -1996,6 +1996,13 @@ extern "C" int mik_axpy_dot(mik_ctx *ctx, int dtype, int64_t n, const void *alph
                             int hints)
 {
     if (!ctx || n < 0 || !out || (x && !alpha) || (n && !y)) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype & ~MIK_SCALAR_REAL)) {
+        const int cd = dtype & ~MIK_SCALAR_REAL;
+        const bool real_alpha = (dtype & MIK_SCALAR_REAL) != 0;
+        // norm(y) after a real alpha (or no update at all): the real entry over the 2 n interleaved reals
+        if (!z && (real_alpha || !x)) return mik_axpy_dot(ctx, mik_real_dtype(cd), 2 * n, alpha, x, y, nullptr, out, hints);
+        return mik_c_axpy_dot(ctx, cd, n, real_alpha, alpha, x, y, z, out);
+    }
     if (dtype == MIK_F64) return axpy_dot_impl<double>(ctx, n, alpha, x, y, z, out, hints);
     if (dtype == MIK_F32) return axpy_dot_impl<float>(ctx, n, alpha, x, y, z, out, hints);
     return MIK_ERR_INVALID;
@@ -2017,6 +2024,9 @@ extern "C" int mik_axpy2_nrm2(mik_ctx *ctx, int dtype, int64_t n, const void *al
                               void *out, int hints)
 {
     if (!ctx || n < 0 || !out || !alpha || (n && (!u || !x || !c || !r))) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_axpy2_nrm2: a complex dtype needs MIK_SCALAR_REAL (src/chebyshev.jl has real scalars only)");
+    if (mik_is_complex(dtype & ~MIK_SCALAR_REAL))      // real alpha: the real sweep (and the real norm) over the 2 n interleaved reals
+        return mik_axpy2_nrm2(ctx, mik_real_dtype(dtype & ~MIK_SCALAR_REAL), 2 * n, alpha, u, x, c, r, out, hints);
     if (dtype == MIK_F64) return axpy2_nrm2_impl<double>(ctx, n, alpha, u, x, c, r, out, hints);
     if (dtype == MIK_F32) return axpy2_nrm2_impl<float>(ctx, n, alpha, u, x, c, r, out, hints);
     return MIK_ERR_INVALID;
@@ -2137,6 +2147,11 @@ extern "C" int mik_cheb_direction(mik_ctx *ctx, int dtype, int64_t n, const void
                                   void *u)
 {
     if (!ctx || n < 0 || (!first && !beta) || (n && (!r || !u))) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype & ~MIK_SCALAR_REAL)) {
+        if (pl_diag) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_cheb_direction: the diagonal preconditioner is not implemented for complex element types (no complex division on the device)");
+        if (!(dtype & MIK_SCALAR_REAL)) return mik_fail(ctx, MIK_ERR_INVALID, "mik_cheb_direction: a complex dtype needs MIK_SCALAR_REAL (src/chebyshev.jl has real scalars only)");
+        return mik_cheb_direction(ctx, mik_real_dtype(dtype & ~MIK_SCALAR_REAL), 2 * n, r, nullptr, beta, first, u);
+    }
     const bool vec = mik_aligned16(r) && mik_aligned16(u) && (!pl_diag || mik_aligned16(pl_diag));
     if (dtype == MIK_F64) {
         OpChebDirection<double> op{(const double *)r, (const double *)pl_diag, (double *)u, first ? 0.0 : *(const double *)beta, first};
@@ -2169,6 +2184,11 @@ extern "C" int mik_minres_update(mik_ctx *ctx, int dtype, int64_t n, const void 
     if (!ctx || n < 0 || !inv_h3 || !inv_h2 || !rhs0 || (w_curr && !neg_h1) || (w_prev && !neg_h0) ||
         (n && (!v_next || !v_curr || !w_next || !x)))
         return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype & ~MIK_SCALAR_REAL)) {      // five real scalars (Hermitian): the real sweep over 2 n; five complex ones (skew-Hermitian): k_cminres_update
+        if (dtype & MIK_SCALAR_REAL)
+            return mik_minres_update(ctx, mik_real_dtype(dtype & ~MIK_SCALAR_REAL), 2 * n, inv_h3, v_next, v_curr, neg_h1, w_curr, neg_h0, w_prev, inv_h2, w_next, rhs0, x, hints);
+        return mik_c_minres_update(ctx, dtype, n, inv_h3, v_next, v_curr, neg_h1, w_curr, neg_h0, w_prev, inv_h2, w_next, rhs0, x);
+    }
     if (dtype == MIK_F64) return minres_update_impl<double>(ctx, n, inv_h3, v_next, v_curr, neg_h1, w_curr, neg_h0, w_prev, inv_h2, w_next, rhs0, x, hints);
     if (dtype == MIK_F32) return minres_update_impl<float>(ctx, n, inv_h3, v_next, v_curr, neg_h1, w_curr, neg_h0, w_prev, inv_h2, w_next, rhs0, x, hints);
     return MIK_ERR_INVALID;

@@ -2173,6 +2173,7 @@ template <typename T> static int gemv_t_impl(mik_ctx *ctx, int64_t n, int k, con
 extern "C" int mik_gemv_t(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V, int64_t ldv, const void *w, void *h)
 {
     if (!ctx || n < 0 || k < 0 || (k && (!h || !V || ldv < n)) || (n && k && !w)) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype)) return mik_c_gemv_t(ctx, dtype, n, k, V, ldv, w, h);
     if (dtype == MIK_F64) return gemv_t_impl<double>(ctx, n, k, (const double *)V, ldv, (const double *)w, (double *)h);
     if (dtype == MIK_F32) return gemv_t_impl<float>(ctx, n, k, (const float *)V, ldv, (const float *)w, (float *)h);
     return MIK_ERR_INVALID;
@@ -2203,6 +2204,7 @@ extern "C" int mik_gram(mik_ctx *ctx, int dtype, int64_t n, int k, const void *V
 {
     if (!ctx || n < 0 || k < 1 || !M || (n && (!V || ldv < n))) return MIK_ERR_INVALID;
     if (k > 5) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_gram: k = %d (at most 5 columns; use mik_gemv_t per column)", k);
+    if (mik_is_complex(dtype)) return mik_c_gram(ctx, dtype, n, k, V, ldv, M);
     if (dtype == MIK_F64) return gram_impl<double>(ctx, n, k, (const double *)V, ldv, (double *)M);
     if (dtype == MIK_F32) return gram_impl<float>(ctx, n, k, (const float *)V, ldv, (float *)M);
     return MIK_ERR_INVALID;
@@ -2233,6 +2235,7 @@ extern "C" int mik_bicgstab_mr_update(mik_ctx *ctx, int dtype, int64_t n, int l,
                                       const void *gamma, void *out)
 {
     if (!ctx || n < 0 || l < 1 || l > 8 || !gamma || !out || (n && (!us || !rs || !x || ldu < n || ldr < n))) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype)) return mik_c_bicgstab_mr_update(ctx, dtype, n, l, us, ldu, rs, ldr, x, gamma, out);
     if (dtype == MIK_F64) return bicg_mr_impl<double>(ctx, n, l, (double *)us, ldu, (double *)rs, ldr, (double *)x, (const double *)gamma, (double *)out);
     if (dtype == MIK_F32) return bicg_mr_impl<float>(ctx, n, l, (float *)us, ldu, (float *)rs, ldr, (float *)x, (const float *)gamma, (float *)out);
     return MIK_ERR_INVALID;
@@ -2273,6 +2276,7 @@ template <typename T> static int lu_solve(T *A, int64_t lda, int n, T *b)
 extern "C" int mik_lu_solve(int dtype, void *A, int64_t lda, int n, void *b)
 {
     if (!A || !b || n < 0 || lda < n) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype)) return mik_c_lu_solve(dtype, A, lda, n, b);
     if (dtype == MIK_F64) return lu_solve<double>((double *)A, lda, n, (double *)b);
     if (dtype == MIK_F32) return lu_solve<float>((float *)A, lda, n, (float *)b);
     return MIK_ERR_INVALID;
