@@ -89,6 +89,12 @@ int mik_dev_mgs_resident_shape(int *threads, int *register_rounds, int *lds_roun
  * device.  Any out pointer may be NULL. */
 int mik_dev_spmv_plan(const mik_csr *A, const void *x, int fuse_dot, int rb_begin, int rb_count, int skip_begin, int skip_end, char *kernel_name, int len,
                       int64_t *grid, int *launches, int *pre_longrows, int *post_rowdot);
+/* Runs the request mik_dev_spmv_plan describes (same rb_begin / rb_count / skip_begin / skip_end) on the context's stream: the rows of y of the
+ * request's row-blocks are written, nothing else of y.  fuse_dot: seg_out (device, one element of the operator's dtype per 256-row block of A) takes
+ * the dot(x, y) segment sum of every row-block of the request; else seg_out is not read.  For tests of the row-range launches, which otherwise only
+ * the row-partitioned CG issues. */
+int mik_dev_spmv_run(mik_ctx *ctx, const mik_csr *A, const void *x, void *y, int fuse_dot, void *seg_out, int rb_begin, int rb_count, int skip_begin,
+                     int skip_end);
 /* Host-only: the rule that places a 256-row block's window of x in LDS (k_spmv_rowblock XWIN) on caller-supplied per-block statistics
  * (first / last referenced column, entry count).  win_lo[b] = first column of block b's window (16-byte aligned) or -1 (the block gathers from
  * memory); *span = common window length in elements, 0 = no window table.  Guarantee the tests check: win_lo[b] >= 0 implies

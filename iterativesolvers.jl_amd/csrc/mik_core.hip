@@ -1818,6 +1818,24 @@ template int mik_spmv_launch<float>(mik_ctx *, const mik_csr *, const float *, f
 template int mik_spmv_launch_range<double>(mik_ctx *, const mik_csr *, const double *, double *, bool, double *, const int *, int, int);
 template int mik_spmv_launch_range<float>(mik_ctx *, const mik_csr *, const float *, float *, bool, float *, const int *, int, int);
 
+template <typename T>
+static int dev_spmv_run(mik_ctx *ctx, const mik_csr *A, const void *x, void *y, bool fuse_dot, void *seg_out, int rb_begin, int rb_count, int skip_begin,
+                        int skip_end)
+{
+    if (skip_begin < 0) return mik_spmv_launch_range<T>(ctx, A, (const T *)x, (T *)y, fuse_dot, (T *)seg_out, nullptr, rb_begin, rb_count);
+    return mik_spmv_launch_outside<T>(ctx, A, (const T *)x, (T *)y, fuse_dot, (T *)seg_out, nullptr, skip_begin, skip_end);
+}
+
+extern "C" int mik_dev_spmv_run(mik_ctx *ctx, const mik_csr *A, const void *x, void *y, int fuse_dot, void *seg_out, int rb_begin, int rb_count,
+                                int skip_begin, int skip_end)
+{
+    if (!ctx || !A || !x || !y || (fuse_dot && !seg_out)) return MIK_ERR_INVALID;
+    if (x == y) return mik_fail(ctx, MIK_ERR_INVALID, "mik_dev_spmv_run: x and y must not alias");
+    MIK_REFUSE_COMPLEX(ctx, A, "mik_dev_spmv_run");
+    return A->dtype == MIK_F64 ? dev_spmv_run<double>(ctx, A, x, y, fuse_dot != 0, seg_out, rb_begin, rb_count, skip_begin, skip_end)
+                               : dev_spmv_run<float>(ctx, A, x, y, fuse_dot != 0, seg_out, rb_begin, rb_count, skip_begin, skip_end);
+}
+
 extern "C" int mik_spmv(mik_ctx *ctx, const mik_csr *A, const void *x, void *y)
 {
     if (!ctx || !A || !x || !y) return MIK_ERR_INVALID;

@@ -447,7 +447,21 @@ __global__ __launch_bounds__(MIK_BLOCK) void k_spmv_rowblock(int n, int nb, int 
 // same bits.
 // The tile is filled by global_load_lds_dwordx4 (gfx950 LDS-DMA: HBM -> LDS without passing through VGPRs; 1 KiB per
 // wave-instruction, the LDS image is the memory image), so staging costs no vector registers, no ds_write and no
-// VALU work; the stream is waited for with one vmcnt(0) before the barrier.
+// VALU work.
+//
+// A workgroup's life is a chain of memory round trips; what is in it (DESIGN.md section 7 has the A/B runs):
+//  1. everything the tile loop and the epilogue need from memory -- row bounds, block bounds, the fused dot's x[r], the stop
+//     flag -- is issued back to back and waited for ONCE, and no ordinary load is outstanding when the first DMA is issued;
+//  2. per pass a wave issues its column pieces, then its value pieces, and waits with a counted vmcnt(N) for the columns alone
+//     (N = the value pieces it issued; a wave's LDS-DMA loads retire in issue order); behind a raw s_barrier -- __syncthreads()
+//     would drain the value stream -- every lane reads the first eight columns of its row and issues their gathers of x, which
+//     then travel UNDER the value stream; vmcnt(0), a second barrier, and only then values from LDS, products and sums;
+//  3. a gather slot that no row of the wave reaches is not issued (a 7-point row-block: seven gathers per wave, not eight);
+//  4. further chunks of a row longer than eight, and further passes, find the tile complete.
+// Step 1 alone changed nothing (462.9 us per CG step against 462.7 us); steps 1 + 2 are worth 6 - 9.5 us of the step, step 3
+// another 5 us (256^3 fp64: 460.4 -> 448.3 us per step, the kernel 292.0 -> 278.2 us).  Measured and taken out again: fetching the
+// next workgroup's rowptr lines ahead (+4 us) and the row-block's own x by LDS-DMA beside the tile (slower than the parent) --
+// every added vector-memory instruction cost more than the wait it shortened.
 //
 // Measured at 256^3 fp64 inside the CG loop (round 2, interleaved rounds in one process): k_spmv_rowblock 302 us,
 // this layout staged through registers 299 us, filled by LDS-DMA 291 us (278 us back to back = 6.25 TB/s).  Also
@@ -462,7 +476,6 @@ __global__ __launch_bounds__(MIK_BLOCK, 6) void k_spmv_rowgather(int n, int rb0,
                                                               const T *__restrict__ ep_w = nullptr, const T *__restrict__ ep_c = nullptr,
                                                              const T *__restrict__ ep_z = nullptr)
 {
-    if (done && *done) return;
     constexpr int TILE = MIK_SPMV_TILE;                // entries per pass: 2048 (fp64: 16 KB values + 8 KB columns)
     constexpr int VW = VT<T>::W;
     constexpr int VP = 1024 / (int)sizeof(T);          // entries per 1-KiB DMA piece of val
@@ -471,27 +484,35 @@ __global__ __launch_bounds__(MIK_BLOCK, 6) void k_spmv_rowgather(int n, int rb0,
     __shared__ __attribute__((aligned(16))) int scol[TILE];
     __shared__ T lds4[4];
 
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int t = threadIdx.x, lane = t & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int rb = rb0 + spmv_block_map((int)blockIdx.x, nb, map_mode);   // this launch covers row-blocks [rb0, rb0 + nb)
     const int r0 = rb * MIK_BLOCK;
     const int r = r0 + t;
-    int ks = 0, ke = 0;
-    if (r < n) { ks = rowptr[r]; ke = rowptr[r + 1]; }
-    const int kb = rowptr[r0] & ~3;                    // 16-byte aligned start of both streams
+    // ---- ONE memory round trip before the tile DMA: the row bounds, the block bounds, the fused dot's own x[r] (kept for the
+    // epilogue; it also warms the diagonal line of the gather) and the stop flag are all issued before any of them is waited for;
+    // the empty asm below is their first use, so the single wait stands in front of it.  Nothing is stored before the stop test. ----
+    // Rows past n read the last row's bounds (no branch around a load) and are given an empty range afterwards.  The operator's
+    // pointers ride in the same asm so that their kernel arguments are fetched here too, not in front of the first DMA.
+    const int rl = min(r, n - 1);
+    int ks = rowptr[rl], ke = rowptr[rl + 1];
+    T xr = T(0);
+    if (FUSE_DOT) xr = (ep_z ? ep_z : x)[rl];          // ep_z: dot(z, y) instead of dot(x, y) (BiCGStab(l): z = r_shadow)
+    const int kfirst = rowptr[r0];
     const int kend = rowptr[min(r0 + MIK_BLOCK, n)];
+    const int stop = *(done ? done : rowptr);
+    if (FUSE_DOT) asm volatile("" :: "v"(ks), "v"(ke), "v"(xr), "s"(kfirst), "s"(kend), "s"(stop), "s"(col), "s"(val), "s"(x), "s"(y));
+    else asm volatile("" :: "v"(ks), "v"(ke), "s"(kfirst), "s"(kend), "s"(stop), "s"(col), "s"(val), "s"(x), "s"(y));
+    if (done && stop) return;
+    if (r >= n) ks = ke = 0;
+    const int kb = kfirst & ~3;                        // 16-byte aligned start of both streams
 
     T acc = T(0);
     for (int kc = kb; kc < kend; kc += TILE) {
         const int cnt = min(TILE, kend - kc);
         // wave wv issues pieces wv, wv + 4, ...; a piece is issued iff it holds an entry < cnt (wave-uniform);
-        // reads past kend stay inside the padded allocation
-#pragma unroll
-        for (int p = 0; p < TILE / VP / 4; ++p) {
-            const int piece = wv + 4 * p;
-            if (piece * VP < cnt)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(val + kc + piece * VP + lane * VW),
-                                                 (__attribute__((address_space(3))) void *)(sval + piece * VP), 16, 0, NT ? 2 : 0);
-        }
+        // reads past kend stay inside the padded allocation.  The columns go first: a wave's LDS-DMA loads retire in the order
+        // of their issue, so once all but its nv value pieces have, its column pieces are in LDS.
 #pragma unroll
         for (int p = 0; p < TILE / CP / 4; ++p) {
             const int piece = wv + 4 * p;
@@ -499,12 +520,58 @@ __global__ __launch_bounds__(MIK_BLOCK, 6) void k_spmv_rowgather(int n, int rb0,
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(col + kc + piece * CP + lane * 4),
                                                  (__attribute__((address_space(3))) void *)(scol + piece * CP), 16, 0, NT ? 2 : 0);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        int nv = 0;                                    // value pieces of this wave and pass: 0 .. 4 (fp32: 0 .. 2)
+#pragma unroll
+        for (int p = 0; p < TILE / VP / 4; ++p) {
+            const int piece = wv + 4 * p;
+            if (piece * VP < cnt) {
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(val + kc + piece * VP + lane * VW),
+                                                 (__attribute__((address_space(3))) void *)(sval + piece * VP), 16, 0, NT ? 2 : 0);
+                ++nv;
+            }
+        }
+        // The gather of x travels UNDER the value stream: the columns are waited for alone (the count is an immediate, hence the
+        // branch), a raw barrier lets the value pieces stay in flight (__syncthreads() would drain them), every lane reads the first
+        // eight columns of its row and issues their gathers, and only then does everything land.
+        if (nv >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else if (nv == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        else if (nv == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        else if (nv == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
         // ---- this lane's row, ascending column order ----
         int a = max(ks, kc) - kc;
         int len = min(ke, kc + cnt) - kc - a;
-        while (len > 0) {
+        {
+            T q[8], xv[8];
+            int cc[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) cc[i] = scol[min(a + i, TILE - 1)];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                // a slot that no row of this wave reaches is not gathered at all (7-point rows: seven gathers, not eight);
+                // in a slot that is, lanes past their row gather a valid address
+                xv[i] = T(0);
+                if (__builtin_amdgcn_ballot_w64(i < len) != 0) xv[i] = x[i < len ? cc[i] : 0];
+            }
+            // the value pieces and the gathers have landed; the gathered x are operands so that their loads stay above this wait
+            asm volatile("s_waitcnt vmcnt(0)"
+                         : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]), "+v"(xv[4]), "+v"(xv[5]), "+v"(xv[6]), "+v"(xv[7])
+                         :: "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int i = 0; i < 8; ++i) q[i] = sval[min(a + i, TILE - 1)] * xv[i];
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                if (i < len) acc = acc + q[i];
+            a += 8;
+            len -= 8;
+        }
+        while (len > 0) {                              // rows longer than eight: the tile is complete by now
             T q[8];
             int cc[8];
 #pragma unroll
@@ -531,7 +598,7 @@ __global__ __launch_bounds__(MIK_BLOCK, 6) void k_spmv_rowgather(int n, int rb0,
     else if (r < n) st_stream<NT>(y + r, acc);
     if (FUSE_DOT) {
         T p = T(0);
-        if (r < n) p = (ep_z ? ep_z[r] : x[r]) * acc;       // ep_z: dot(z, y) instead of dot(x, y) (BiCGStab(l): z = r_shadow)
+        if (r < n) p = xr * acc;
         T tot = block_tree_256(p, lds4);
         if (t == 0) seg_out[rb] = tot;
     }
