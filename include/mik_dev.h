@@ -95,6 +95,10 @@ int mik_dev_spmv_plan(const mik_csr *A, const void *x, int fuse_dot, int rb_begi
  * the row-partitioned CG issues. */
 int mik_dev_spmv_run(mik_ctx *ctx, const mik_csr *A, const void *x, void *y, int fuse_dot, void *seg_out, int rb_begin, int rb_count, int skip_begin,
                      int skip_end);
+/* The exclusive scan of the device-side upload (csrc/mik_upload.hip: row pointer, slot pointer and slice pointer all come from it) on its own.
+ * data (device, n + 1 ints): data[0..n) -> exclusive prefix sums in place, data[n] = total.  Allocates its own scratch, by the rule the
+ * upload sizes its own with; returns when the result is in place.  For tests. */
+int mik_dev_exclusive_scan(mik_ctx *ctx, int *data, int64_t n);
 /* Host-only: the rule that places a 256-row block's window of x in LDS (k_spmv_rowblock XWIN) on caller-supplied per-block statistics
  * (first / last referenced column, entry count).  win_lo[b] = first column of block b's window (16-byte aligned) or -1 (the block gathers from
  * memory); *span = common window length in elements, 0 = no window table.  Guarantee the tests check: win_lo[b] >= 0 implies

@@ -90,6 +90,7 @@ SIGNATURES = {
     "mik_dev_mgs_resident_shape": (C.c_int, [_ip, _ip, _ip]),
     "mik_dev_spmv_plan": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, _i64p, _ip, _ip, _ip]),
     "mik_dev_spmv_run": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mik_dev_exclusive_scan": (C.c_int, [_vp, _vp, _i64]),
     "mik_ctx_set_stream": (C.c_int, [_vp, _vp]),
     "mik_ctx_synchronize": (C.c_int, [_vp]),
     "mik_last_error": (C.c_char_p, [_vp]),

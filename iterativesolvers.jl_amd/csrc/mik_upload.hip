@@ -73,7 +73,12 @@ __global__ __launch_bounds__(MIK_BLOCK) void k_scan_add(int *__restrict__ data, 
         if (base + i < n) data[base + i] += o;
 }
 
-// data[0..n) -> exclusive prefix sums; data[n] (must be allocated) = total.  scratch: >= n / 2048 + n / 2048^2 + 8 ints
+// ints of scratch device_exclusive_scan(.., n, ..) may be handed: level k of the recursion keeps its ceil(n / 2048^k) tile sums and the
+// slot of their total, and the levels lie one behind the other -- n / 2048 + n / 2048^2 + ... + one or two ints per level, which
+// 2 * (n / 2048 + 1) + 64 covers at every n
+static size_t scan_scratch_ints(long long n) { return (size_t)((n > 0 ? n : 0) / SCAN_TILE + 1) * 2 + 64; }
+
+// data[0..n) -> exclusive prefix sums; data[n] (must be allocated) = total.  scratch: >= scan_scratch_ints(n) ints
 static hipError_t device_exclusive_scan(hipStream_t st, int *data, long long n, int *scratch)
 {
     if (n <= 0) return hipMemsetAsync(data, 0, sizeof(int), st);
@@ -363,7 +368,7 @@ int upload_device_t(mik_ctx *ctx, mik_csr *A, int64_t n_rows, int64_t n_cols, in
     UploadStats *d_st = nullptr;
     int *cursor = nullptr, *scan_tmp = nullptr;
     const size_t pad = 2 * MIK_SPMV_TILE;          // slack so tile-granular reads never leave the allocation
-    const size_t scan_ints = (size_t)(std::max<int64_t>(n_rows, nb) / SCAN_TILE + 1) * 2 + 64;
+    const size_t scan_ints = scan_scratch_ints(std::max<int64_t>(n_rows, nb));          // the row-pointer scan and the slot-pointer scan share it
 #define UP_TRY(call) do { if ((e = (call)) != hipSuccess) goto hip_fail; } while (0)
     UploadStats hs;
     int long_row;
@@ -720,6 +725,22 @@ template <typename T> static int build_sdiaw_device_t(mik_ctx *ctx, mik_csr *A)
     return MIK_OK;
 }
 
+// development entry (include/mik_dev.h): the scan of the upload on its own, with the scratch the upload would give it
+extern "C" int mik_dev_exclusive_scan(mik_ctx *ctx, int *data, int64_t n)
+{
+    if (!ctx) return MIK_ERR_INVALID;
+    if (!data || n < 0) return mik_fail(ctx, MIK_ERR_INVALID, "mik_dev_exclusive_scan: NULL array or negative length");
+    if (n >= (int64_t)INT32_MAX - MIK_BLOCK) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_dev_exclusive_scan: more elements than mik_csr_create admits rows");
+    MIK_HIP(ctx, hipSetDevice(ctx->device));
+    Scratch S;
+    int *scan_tmp = nullptr;
+    MIK_HIP(ctx, S.alloc(&scan_tmp, sizeof(int) * scan_scratch_ints(n)));
+    MIK_HIP(ctx, device_exclusive_scan(ctx->stream, data, n, scan_tmp));
+    MIK_HIP(ctx, hipGetLastError());
+    MIK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MIK_OK;
+}
+
 int mik_build_sdiaw_device(mik_ctx *ctx, mik_csr *A)
 {
     if (!A->rowptr || A->n_long || A->sdia_val || A->sdia_pats || A->nnz <= 0 || (ctx->tuning[MIK_KNOB_LAYOUTS] & 1) != 0 || (ctx->tuning[MIK_KNOB_LAYOUTS] & 4) != 0) return MIK_OK;
@@ -743,7 +764,7 @@ template <typename T> static int build_jds_device_t(mik_ctx *ctx, mik_csr *A)
     JD_TRY(S.alloc(&jptr, sizeof(int) * ((size_t)nsl + 8)));
     JD_TRY(S.alloc(&jlen, sizeof(unsigned short) * (size_t)n_rows));
     JD_TRY(S.alloc(&d_st, sizeof(JdsStats)));
-    JD_TRY(S.alloc(&scan_tmp, sizeof(int) * ((size_t)(nsl / SCAN_TILE + 1) * 2 + 64)));
+    JD_TRY(S.alloc(&scan_tmp, sizeof(int) * scan_scratch_ints(nsl)));
     JD_TRY(hipMemsetAsync(d_st, 0, sizeof(JdsStats), st));
     hipLaunchKernelGGL((k_up_jds_count<W>), dim3((unsigned)((nsl + 3) / 4)), dim3(MIK_BLOCK), 0, st, A->rowptr, (long long)n_rows, (long long)nsl, jptr, jlen, d_st);
     JD_TRY(device_exclusive_scan(st, jptr, nsl, scan_tmp));

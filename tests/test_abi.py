@@ -76,7 +76,7 @@ def test_development_queries_are_declared_in_the_development_header_only_and_bou
     boundary = open(HEADER).read()
     dev = re.sub(r"/\*.*?\*/", "", open(DEV_HEADER).read(), flags=re.S)
     names = sorted(n for n in pkg._lib.SIGNATURES if n.startswith("mik_dev_"))
-    assert "mik_dev_gmres_form" in names and "mik_dev_dense_plan" in names
+    assert "mik_dev_gmres_form" in names and "mik_dev_dense_plan" in names and "mik_dev_exclusive_scan" in names
     for name in names:
         assert name not in boundary, name
         decl = re.search(rf"\bint {name}\(([^;]*)\);", dev)
