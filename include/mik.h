@@ -762,27 +762,41 @@ int mik_svdl_reorth(mik_ctx *ctx, int dtype, int64_t n, int k, const void *Q, in
                     int *passes_out);
 
 /* ---- lobpcg: the block sweeps of the Locally Optimal Block Preconditioned Conjugate Gradient method (src/lobpcg.jl) ---------
- * Every sweep of LOBPCG works on a block of vectors.  Four entries (added without a version bump, additive); real MIK_F64 / MIK_F32.
+ * Every sweep of LOBPCG works on a block of vectors.  Four entries (added without a version bump, additive): MIK_F64 / MIK_F32 and, added
+ * later in the same way, MIK_C64 / MIK_C32 (interleaved re, im; the complex definitions follow each entry and the paragraph below).
  * Blocks: DEVICE, column-major, leading dimension in elements; small matrices: HOST, column-major, of `dtype`, read before the call
  * returns.  A block is at most 32 columns wide, else MIK_ERR_NOTIMPL.  No FMA, no matrix cores: every product and every sum is rounded
  * on its own.  The residual columns and their norms, the gather of the active columns, the constraint and the preconditioner are
- * composed from the vector entries above (mik_axpy_dot, mik_nrm2, mik_copy, mik_gemv_n, mik_divide). */
+ * composed from the vector entries above (mik_axpy_dot, mik_nrm2, mik_copy, mik_gemv_n, mik_divide).
+ * Complex blocks: leading dimensions count ELEMENTS, element alignment (8 bytes) suffices, small host matrices are interleaved complex.
+ * z * w = (zr wr - zi wi) + (zr wi + zi wr) i with every product and every sum rounded on its own, sums componentwise, re and im each
+ * their own chain, nothing contracted; there is no complex division on the device. */
 /* Y[:, j] = A * X[:, j] for j < b -- mul!(AX, A, X), :124-139.  Column j of Y equals mik_spmv(A, X[:, j]) bit for bit, whatever layout
  * the operator runs on.  An operator that still holds its CSR arrays and has no row longer than mik_spmv_long_row is swept by one kernel
  * on those arrays, one lane per row: the operator's tile is read once per block of 8 columns instead of once per column, each column's
  * row sum serial in ascending column order from +0.  An operator with long rows, or one whose CSR arrays were released by
  * mik_csr_compact, runs mik_spmv column by column.  ldx >= columns of A, ldy >= rows of A; Y must not overlap X (MIK_ERR_INVALID).
+ * A complex operator (MIK_C64 / MIK_C32): column j of Y equals the complex mik_spmv(A, X[:, j]) bit for bit -- a row's products
+ * val * x[col] added from (+0, +0) in ascending entry order, re and im separately; the operator's values and columns are read once per
+ * block of 4 columns; an operator with a row longer than mik_spmv_long_row runs mik_spmv column by column.
  * Asynchronous on the ctx stream. */
 int mik_spmm(mik_ctx *ctx, const mik_csr *A, int b, const void *X, int64_t ldx, void *Y, int64_t ldy);
 /* G = X[:, 0:p]' * Y[:, 0:q], a p x q HOST matrix with leading dimension ldg -- every mul!(G, adjoint(X), Y) of :262-270, :217, :375.
  * G[i, j] equals mik_dot(X[:, i], Y[:, j]) bit for bit: the fixed tree of mik_reduce_shape ("Reduction semantics"), the segment sums
  * through the same finaliser.  One launch sweeps both blocks, 4 columns of X against 4 columns of Y per workgroup (a column is read
- * ceil(q / 4) resp. ceil(p / 4) times instead of q resp. p times).  X == Y is allowed.  Synchronises. */
+ * ceil(q / 4) resp. ceil(p / 4) times instead of q resp. p times).  X == Y is allowed.  Synchronises.
+ * Complex: G[i, j] equals the complex mik_dot(X[:, i], Y[:, j]) = sum conj(x) y bit for bit (per element re = xr yr + xi yi,
+ * im = xr yi - xi yr, one tree of mik_reduce_shape(dtype) for re and one for im); no symmetry is assumed; ldg counts elements. */
 int mik_block_gram(mik_ctx *ctx, int dtype, int64_t n, int p, int q, const void *X, int64_t ldx, const void *Y, int64_t ldy, void *G,
                    int64_t ldg);
 /* X <- X * inv(R) in place, R: HOST s x s, upper triangular (the strict lower triangle is not read) -- rdiv!, :345-355.  Exactly
  *   for i = 0 .. s-1:  for j = 0 .. i-1:  X[:, i] = X[:, i] - X[:, j] * R[j, i];   then  X[:, i] = X[:, i] / R[i, i]
  * every operation rounded on its own.  A row depends on itself only: a lane keeps its row's s values in registers and makes one pass.
+ * Complex: X[:, i] = X[:, i] - X[:, j] * R[j, i] with the complex product above and a componentwise subtraction, then
+ * X[:, i] = (re / d, im / d) with d = real(R[i, i]) -- two real divisions.  This differs from Julia's rdiv!, which divides complex by
+ * complex (CholQR's factor has a real diagonal, src/lobpcg.jl:357-363,379): a diagonal entry whose imaginary part is not +-0 is
+ * MIK_ERR_INVALID with a message naming the column, checked before anything is launched.  A lane works through its row in panels of 8
+ * columns and re-reads the finished columns before each later panel; the result does not depend on the panel width.
  * Asynchronous on the ctx stream. */
 int mik_block_rdiv(mik_ctx *ctx, int dtype, int64_t n, int s, const void *R, int64_t ldr, void *X, int64_t ldx);
 /* The Ritz update of one block triple -- the body of update_X_P!, :629-690.  X: n x sx, R: n x b1, P: n x b2, V: HOST (sx + b1 + b2) x sx,
@@ -790,6 +804,8 @@ int mik_block_rdiv(mik_ctx *ctx, int dtype, int64_t n, int s, const void *R, int
  *   b1 > 0:  Pout = rot(R, Vr);   b2 > 0:  Pout = Pout + rot(P, Vp);   Xout = rot(X, Vx) + Pout   (b1 == 0: Xout = rot(X, Vx))
  * With b1 == 0 Pout is not written (and b2 must be 0).  0 <= b1, b2 <= sx <= 32, else MIK_ERR_NOTIMPL.  One pass: X, R and P are read
  * once, Xout (n x sx) and Pout (n x sx) written once.  No output may overlap an input or the other output (MIK_ERR_INVALID).
+ * Complex: rot opens a sum with the complex product W[row, 0] * F[0, jj] and adds W[row, c] * F[c, jj] componentwise, c ascending; V is a
+ * host complex matrix.  The output columns run in panels (8 at ComplexF64, 16 at ComplexF32) and X, R and P are read once per panel.
  * Asynchronous on the ctx stream. */
 int mik_block_update(mik_ctx *ctx, int dtype, int64_t n, int sx, int b1, int b2, const void *X, int64_t ldx, const void *R, int64_t ldr,
                      const void *P, int64_t ldp, const void *V, int64_t ldv, void *Xout, int64_t ldxo, void *Pout, int64_t ldpo);

@@ -300,7 +300,7 @@ def dtype_code(dtype) -> int:
         return MIK_F64
     if dtype == np.float32:
         return MIK_F32
-    if dtype == np.complex128:             # the five solver rows and the L1 / L2 entries under them (DESIGN.md sections 17 - 19)
+    if dtype == np.complex128:             # the five solver rows, lobpcg on CSR and the entries under them (DESIGN.md sections 17 - 20)
         return MIK_C64
     if dtype == np.complex64:
         return MIK_C32
@@ -308,10 +308,10 @@ def dtype_code(dtype) -> int:
 
 
 def real_dtype_code(dtype, who: str) -> int:
-    """``dtype_code`` for what stays real: svdl, lobpcg, the stationary methods and the extras."""
+    """``dtype_code`` for what stays real: svdl, the stationary methods and the extras."""
     if np.dtype(dtype).kind == "c":
-        raise TypeError(f"{who} is not offered for complex element types (DESIGN.md sections 17 - 19: cg, gmres, bicgstabl, minres and chebyshev "
-                        "on a CSR or dense operator are)")
+        raise TypeError(f"{who} is not offered for complex element types (DESIGN.md sections 17 - 20: cg, gmres, bicgstabl, minres and chebyshev "
+                        "on a CSR or dense operator are, and lobpcg on a CSR operator)")
     return dtype_code(dtype)
 
 

@@ -387,7 +387,7 @@ class HipMatrix:
     def _refuse_complex_block(self, who: str) -> None:
         """The block product is real only (``mik_dense_mm`` answers a complex handle with MIK_ERR_NOTIMPL): say so before the library does."""
         if _is_complex(self.dtype):
-            raise TypeError(f"HipMatrix.{who}: the block product is not offered for a {self.dtype} matrix (lobpcg stays real; mul_ and A.adj serve it)")
+            raise TypeError(f"HipMatrix.{who}: the block product is not offered for a {self.dtype} matrix (lobpcg on a dense operator stays real; mul_ and A.adj serve it)")
 
     def __del__(self):
         try:

@@ -42,3 +42,40 @@ int mik_c_bicgstab_mr_update(mik_ctx *ctx, int dtype, int64_t n, int l, void *us
 int mik_c_lu_solve(int dtype, void *A, int64_t lda, int n, void *b);
 int mik_c_givens(int dtype, const void *f, const void *g, void *out);
 int mik_c_hessenberg_ldiv(int dtype, void *H, int64_t ldh, int width, void *rhs);
+
+#ifdef __HIPCC__
+#include "mik_kernels.h"
+
+// What the complex kernels of csrc/mik_complex.hip and the complex block kernels of csrc/mik_lobpcg_complex.h share.
+// The thread's share of dot(a, b) = sum conj(a_i) b_i over one segment held in registers: the products, the order (l ascending, then the
+// elements of a 16-byte group) and the two accumulators of OpCDot.
+template <typename R>
+__device__ __forceinline__ void cseg_dot(const R (&a)[SEG_REGS<R>], const R (&b)[SEG_REGS<R>], int64_t base, int64_t n2, R &re, R &im)
+{
+    constexpr int W = VT<R>::W;
+    R a0 = R(0), a1 = R(0);
+#pragma unroll
+    for (int l = 0; l < MIK_RED_L; ++l)
+#pragma unroll
+        for (int e = 0; e < W; e += 2) {
+            const int q = l * W + e;
+            if (base + (int64_t)l * MIK_BLOCK * W + e < n2) {
+                const R p = a[q] * b[q], r = a[q + 1] * b[q + 1], s = a[q] * b[q + 1], t = a[q + 1] * b[q];
+                const R vr = p + r, vi = s - t;
+                a0 = a0 + vr;
+                a1 = a1 + vi;
+            }
+        }
+    re = a0;
+    im = a1;
+}
+
+// level 2 of `cols` reductions whose segment sums sit in ctx->partials as [cols][nseg] -> out_dev[0 .. cols)
+template <typename R> static inline int c_finalize(mik_ctx *ctx, int64_t nseg, int cols, R *out_dev)
+{
+    hipLaunchKernelGGL((k_finalize_store<R>), dim3(cols), dim3(MIK_FIN_THREADS), 0, ctx->stream, (const R *)ctx->partials, nseg, nseg, out_dev,
+                       (const int *)nullptr);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+#endif  // __HIPCC__

@@ -17,7 +17,8 @@ on the device inside the iteration loop.
 Differences from the reference, all deliberate:
   * ``A`` and ``B`` are ``HipCSR``, or -- with ``dense=True`` -- each a ``HipCSR`` or a square ``HipMatrix`` (the two may differ).  Without the
     keyword a ``HipMatrix`` is refused as it always was: that refusal is behaviour callers and the suite rely on, so the dense route is asked for;
-    real float32 / float64; a block is at most 32 columns wide (the width of the device entries);
+    real float32 / float64 -- and, for ``HipCSR`` operators, complex64 / complex128 (Hermitian ``A``, Hermitian positive definite ``B``;
+    DESIGN.md section 20); a block is at most 32 columns wide (the width of the device entries);
   * where the reference calls ``rand`` the functions take ``rng=`` (a ``numpy.random.Generator``), so that runs repeat;
   * ``results.X`` stays on the device (a ``HipMatrix``); ``X0`` and ``C`` are ``HipMatrix`` or numpy arrays and are copied;
   * a Cholesky factorisation that fails (a block that lost rank, a ``B`` that is not positive definite) raises ``LobpcgCholeskyError``,
@@ -27,6 +28,9 @@ Differences from the reference, all deliberate:
     the device's ``norm`` of the stored column instead of a serial sum of squares (:538-545);
   * the constraint subtracts ``Y * tmp`` one column of Y at a time (``X[:, j] += (-tmp[i, j]) * Y[:, i]``, i ascending) instead of forming
     the product first (:220-221);
+  * complex element types: ``rdiv!`` (:345-355) divides a column by ``R[i, i]``, a complex number whose imaginary part ``realdiag!``
+    (:357-363) has set to zero; ``mik_block_rdiv`` divides re and im by ``real(R[i, i])`` -- two real divisions, no complex division on the
+    device -- and refuses a factor whose diagonal is not real.  A complex ``HipMatrix`` and ``JacobiPrec`` on complex vectors stay refused;
   * every call of ``lobpcg_`` starts a trace of its own; the reference keeps pushing into the one vector the iterator owns (:883), so the
     batches of the multi-batch driver would share one growing trace.
 """
@@ -36,7 +40,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import MikError, check, dtype_code, lib, real_dtype_code
+from ._lib import MikError, check, dtype_code, lib
 from .api import HipCSR, HipMatrix, Identity, JacobiPrec
 
 _vp = C.c_void_p
@@ -79,10 +83,22 @@ class LOBPCGResults:
                 f"   * Iterations: {self.iterations}\n   * Converged: {bool(np.all(self.converged))}\n   * Iterations limit: {self.maxiter}\n")
 
 
+def _real_dtype(dtype):
+    """``real(T)``: the type of a residual norm and of the tolerance."""
+    return np.zeros(0, dtype).real.dtype
+
+
+def _rand(rng, shape, dtype):
+    """``rand(T, shape...)`` from ``rng``: a complex type draws re and im."""
+    if np.dtype(dtype).kind == "c":
+        return rng.random(shape) + 1j * rng.random(shape)
+    return rng.random(shape)
+
+
 def _empty_results(ops, blocksize, k, tolerance, maxiter):
     """``EmptyLOBPCGResults`` (:66-77)."""
     lam = np.zeros(k, ops.dtype)
-    return LOBPCGResults(lam, ops.matrix(ops.n, k), tolerance, lam.copy(), np.zeros(-(-k // blocksize), np.int64), maxiter, np.zeros(k, bool),
+    return LOBPCGResults(lam, ops.matrix(ops.n, k), tolerance, np.zeros(k, _real_dtype(ops.dtype)), np.zeros(-(-k // blocksize), np.int64), maxiter, np.zeros(k, bool),
                          [[] for _ in range(k // blocksize + 1)])
 
 
@@ -117,9 +133,9 @@ class DeviceOps:
         if A.n_rows != A.n_cols or (B is not None and (B.n_rows, B.n_cols, np.dtype(B.dtype)) != (A.n_rows, A.n_cols, np.dtype(A.dtype))):
             raise ValueError("DimensionMismatch: lobpcg needs square A and B of one size and element type")
         self.ctx, self.dtype, self.n = A.ctx, np.dtype(A.dtype), A.n_rows
-        if isinstance(A, HipMatrix) and self.dtype.kind == "c":
+        if self.dtype.kind == "c" and (isinstance(A, HipMatrix) or isinstance(B, HipMatrix)):
             raise TypeError(f"lobpcg is not offered for a {self.dtype} HipMatrix (the block product mik_dense_mm is real only)")
-        self.code = real_dtype_code(self.dtype, "lobpcg")
+        self.code = dtype_code(self.dtype)                               # complex: the complex instances of the four block entries
         for M in (A, B):
             if isinstance(M, HipMatrix):
                 M.reserve_block_()                                       # the partials of mik_dense_mm: allocated here, not in the loop
@@ -171,7 +187,8 @@ class DeviceOps:
     # -- composed from the vector entries ---------------------------------------------------------
     def residuals(self, AX, BX, lam, R, sx):                             # residuals!, :533-547
         from . import api
-        out = np.zeros(sx, self.dtype)
+        out = np.zeros(sx, _real_dtype(self.dtype))
+        lam = np.real(lam)                                               # Ritz values are real: real x complex on a complex block
         for j in range(sx):
             r = R.col(j)
             r.copyto_(AX.col(j))
@@ -207,23 +224,37 @@ class DeviceOps:
 # host helpers: Hermitian(.) reads the upper triangle; the factorisations in the element type
 # ==============================================================================================
 def _hermitian(G):
+    """``Hermitian(G)``: the upper triangle, its conjugate below, a real diagonal.  (The real path is the code it always was.)"""
     U = np.triu(G)
-    return U + np.triu(G, 1).T
+    if not np.iscomplexobj(G):
+        return U + np.triu(G, 1).T
+    H = U + np.triu(G, 1).conj().T
+    np.fill_diagonal(H, np.diagonal(H).real)
+    return H
+
+
+def _adjoint(M):
+    return M.conj().T if np.iscomplexobj(M) else M.T
 
 
 def _cholesky_upper(G, what):
-    """``cholesky!(Hermitian(G)).factors``: the upper factor R with R'R = G."""
+    """``cholesky!(Hermitian(G)).factors``: the upper factor R with R'R = G; complex: the diagonal made real, as ``realdiag!`` (:357-363)."""
     try:
-        return np.ascontiguousarray(np.linalg.cholesky(_hermitian(G)).T)
+        R = np.ascontiguousarray(_adjoint(np.linalg.cholesky(_hermitian(G))))
     except np.linalg.LinAlgError as e:
         raise LobpcgCholeskyError(8, "lobpcg", f"{what} is not positive definite ({e})") from None
+    if np.iscomplexobj(R):
+        np.fill_diagonal(R, np.diagonal(R).real)
+    return R
 
 
 def _solve_upper_t(R, b):
-    """x with R' x = b, R upper triangular; columns of b one after another, forward substitution in the element type."""
+    """x with R' x = b (R' the conjugate transpose), R upper triangular; columns of b one after another, forward substitution in the
+    element type."""
     x = np.array(b, dtype=R.dtype, copy=True)
+    Rc = R.conj() if np.iscomplexobj(R) else R
     for i in range(R.shape[0]):
-        x[i] = (x[i] - R[:i, i] @ x[:i]) / R[i, i]
+        x[i] = (x[i] - Rc[:i, i] @ x[:i]) / Rc[i, i]
     return x
 
 
@@ -360,7 +391,7 @@ class LOBPCGIterator:
         self.ritz_values = np.zeros(3 * sizeX, T)                        # :473-479
         self.lam = np.zeros(sizeX, T)
         self.V = np.zeros((3 * sizeX, 3 * sizeX), T)
-        self.residuals = np.full(sizeX, np.nan, T)
+        self.residuals = np.full(sizeX, np.nan, _real_dtype(T))
         self.iteration = 1
         self.currentBlockSize = sizeX
         self.gramA = np.zeros((3 * sizeX, 3 * sizeX), T)                 # :486-487
@@ -421,11 +452,12 @@ class LOBPCGIterator:
         else:
             GA, GB = _hermitian(self.gramA[:subdim, :subdim]), self.gramB[:subdim, :subdim]
             Rb = _cholesky_upper(GB, "the Rayleigh-Ritz Gram matrix of B")       # GB = Rb' Rb
-            Cm = _solve_upper_t(Rb, _solve_upper_t(Rb, GA).T).T          # inv(Rb') GA inv(Rb)
+            Cm = _adjoint(_solve_upper_t(Rb, _adjoint(_solve_upper_t(Rb, GA))))      # inv(Rb') GA inv(Rb)
             values, Z = np.linalg.eigh(_hermitian(Cm))
             vectors = _solve_upper(Rb, Z)                                # :620: vectors' GB vectors = I
         values = values.astype(self.ops.dtype)
-        perm = np.argsort(-values if self.largest else values, kind="stable")[:sx]     # :623
+        key = values.real if np.iscomplexobj(values) else values         # Ritz values are real (eigh), stored in the element type
+        perm = np.argsort(-key if self.largest else key, kind="stable")[:sx]       # :623
         self.ritz_values[:sx] = values[perm]                             # :624
         self.V[:subdim, :sx] = vectors[:, perm]                          # :625
 
@@ -469,7 +501,7 @@ class LOBPCGIterator:
 
 def default_tolerance(dtype):
     """``eps(real(T))^(real(T)(3)/10)`` (:751)."""
-    T = np.dtype(dtype).type
+    T = _real_dtype(dtype).type
     return T(np.finfo(T).eps) ** (T(3) / T(10))
 
 
@@ -486,7 +518,7 @@ def lobpcg_(iterator, *, log=False, maxiter=200, not_zeros=False, tol=None, rng=
         rng = np.random.default_rng() if rng is None else rng
         for j in range(sx):
             if not np.any(Xh[:, j]):
-                ops.upload(iterator.X, rng.random((ops.n, 1)), j)
+                ops.upload(iterator.X, _rand(rng, (ops.n, 1), ops.dtype), j)
         iterator.constr(iterator.X, sx)
     iterator.iteration = 1                                               # :879
     iterator.trace = []
@@ -525,7 +557,7 @@ def lobpcg(A, *args, not_zeros=False, log=False, P=None, maxiter=200, C=None, to
     tol = default_tolerance(ops.dtype) if tol is None else tol
     rng = np.random.default_rng() if rng is None else rng
     if len(rest) == 1 and isinstance(rest[0], (int, np.integer)):        # :790-792
-        X0, not_zeros = rng.random((n, int(rest[0]))).astype(ops.dtype), True
+        X0, not_zeros = _rand(rng, (n, int(rest[0])), ops.dtype).astype(ops.dtype), True
         rest = (X0,)
     if len(rest) == 1:                                                   # :827-839
         Xh = np.asarray(_host(rest[0]), ops.dtype)
@@ -559,13 +591,13 @@ def lobpcg(A, *args, not_zeros=False, log=False, P=None, maxiter=200, C=None, to
             cutoff = sizeX - (nev - converged_x)
             iterator.constr.update_(X.block, X.B_block, cutoff)          # :947
             ops.copy_cols(X.block, 0, X.block, cutoff, sizeX - cutoff)   # :948
-            ops.upload(X.block, rng.random((n, sizeX - cutoff)), cutoff)             # :949
+            ops.upload(X.block, _rand(rng, (n, sizeX - cutoff), ops.dtype), cutoff)  # :949
             rnext = lobpcg_(iterator, log=log, tol=tol, maxiter=maxiter, not_zeros=True, rng=rng)
             _append(ops, r, rnext, converged_x, sizeX - cutoff)
             converged_x += sizeX - cutoff
         else:
             iterator.constr.update_(X.block, X.B_block, sizeX)           # :954
-            ops.upload(X.block, rng.random((n, sizeX)))                  # :955
+            ops.upload(X.block, _rand(rng, (n, sizeX), ops.dtype))       # :955
             rnext = lobpcg_(iterator, log=log, tol=tol, maxiter=maxiter, not_zeros=True, rng=rng)
             _append(ops, r, rnext, converged_x)
             converged_x += sizeX
