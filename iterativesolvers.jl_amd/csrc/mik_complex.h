@@ -20,7 +20,6 @@ int mik_c_csr_create(mik_ctx *ctx, int dtype, int64_t n_rows, int64_t n_cols, in
 int mik_c_spmv(mik_ctx *ctx, const mik_csr *A, const void *x, void *y);
 const char *mik_c_spmv_kernel_name(const mik_csr *A);
 int64_t mik_c_stored_bytes(const mik_csr *A);
-int mik_c_time_spmv(mik_ctx *ctx, const mik_csr *A, const void *x, void *y, int reps, double *avg_ms);
 
 int mik_c_dot(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void *y, void *out);
 int mik_c_fill(mik_ctx *ctx, int dtype, int64_t n, const void *value, void *x);
@@ -46,9 +45,53 @@ int mik_c_hessenberg_ldiv(int dtype, void *H, int64_t ldh, int width, void *rhs)
 #ifdef __HIPCC__
 #include "mik_kernels.h"
 
-// What the complex kernels of csrc/mik_complex.hip and the complex block kernels of csrc/mik_lobpcg_complex.h share.
-// The thread's share of dot(a, b) = sum conj(a_i) b_i over one segment held in registers: the products, the order (l ascending, then the
-// elements of a 16-byte group) and the two accumulators of OpCDot.
+// ---- the complex segment toolkit: what the kernels of csrc/mik_complex.hip, csrc/mik_dense_cmul.h and csrc/mik_lobpcg_complex.h share ----
+// Element operations.  Each rounding sequence is written here once; the C checkers under tests/complex_ref/ restate exactly these.
+// (a0 + a1 i) += conj(a) b: re = ar br + ai bi, im = ar bi - ai br, every product rounded, the two terms added, one accumulator each
+template <typename R> __device__ __forceinline__ void cx_dot_acc(R ar, R ai, R br, R bi, R &a0, R &a1)
+{
+    const R p = ar * br, q = ai * bi, s = ar * bi, t = ai * br;
+    const R re = p + q, im = s - t;
+    a0 = a0 + re;
+    a1 = a1 + im;
+}
+// a0 += v^2 for one real: the rounded square, then the rounded add
+template <typename R> __device__ __forceinline__ void cx_sq_acc(R v, R &a0)
+{
+    const R p = v * v;
+    a0 = a0 + p;
+}
+// a0 += yr^2, then yi^2: memory order into one accumulator -- the bits mik_nrm2 squares over the 2 n reals
+template <typename R> __device__ __forceinline__ void cx_sumsq_acc(R yr, R yi, R &a0)
+{
+    cx_sq_acc(yr, a0);
+    cx_sq_acc(yi, a0);
+}
+// y += t x and y -= h x: the rounded product (cx_mul), then one rounded add / subtract per component
+template <typename R> __device__ __forceinline__ void cx_madd(R tr, R ti, R xr, R xi, R &yr, R &yi)
+{
+    const CxVal<R> p = cx_mul(tr, ti, xr, xi);
+    yr = yr + p.re;
+    yi = yi + p.im;
+}
+template <typename R> __device__ __forceinline__ void cx_msub(R hr, R hi, R xr, R xi, R &yr, R &yi)
+{
+    const CxVal<R> p = cx_mul(hr, hi, xr, xi);
+    yr = yr - p.re;
+    yi = yi - p.im;
+}
+// y += a x with a real a (real x complex: a xr, a xi)
+template <typename R> __device__ __forceinline__ void cx_madd_real(R a, R xr, R xi, R &yr, R &yi)
+{
+    const R p = a * xr, q = a * xi;
+    yr = yr + p;
+    yi = yi + q;
+}
+
+// Operations on one segment held in registers (register q = 2 p: re, q = 2 p + 1: im of the thread's p-th element); the order is l
+// ascending, then the elements of a 16-byte group.  The reducing forms skip the elements at or past n2; the others run over every register:
+// lanes past n hold the zeros seg_load left and are never stored.
+// the thread's share of dot(a, b) = sum conj(a_i) b_i
 template <typename R>
 __device__ __forceinline__ void cseg_dot(const R (&a)[SEG_REGS<R>], const R (&b)[SEG_REGS<R>], int64_t base, int64_t n2, R &re, R &im)
 {
@@ -59,15 +102,38 @@ __device__ __forceinline__ void cseg_dot(const R (&a)[SEG_REGS<R>], const R (&b)
 #pragma unroll
         for (int e = 0; e < W; e += 2) {
             const int q = l * W + e;
-            if (base + (int64_t)l * MIK_BLOCK * W + e < n2) {
-                const R p = a[q] * b[q], r = a[q + 1] * b[q + 1], s = a[q] * b[q + 1], t = a[q + 1] * b[q];
-                const R vr = p + r, vi = s - t;
-                a0 = a0 + vr;
-                a1 = a1 + vi;
-            }
+            if (base + (int64_t)l * MIK_BLOCK * W + e < n2) cx_dot_acc(a[q], a[q + 1], b[q], b[q + 1], a0, a1);
         }
     re = a0;
     im = a1;
+}
+// the thread's share of the sum of squares of a (every real guarded on its own)
+template <typename R> __device__ __forceinline__ R cseg_sumsq(const R (&a)[SEG_REGS<R>], int64_t base, int64_t n2)
+{
+    constexpr int W = VT<R>::W;
+    R acc = R(0);
+#pragma unroll
+    for (int l = 0; l < MIK_RED_L; ++l)
+#pragma unroll
+        for (int e = 0; e < W; ++e)
+            if (base + (int64_t)l * MIK_BLOCK * W + e < n2) cx_sq_acc(a[l * W + e], acc);
+    return acc;
+}
+// y += (tr + ti i) v
+template <typename R> __device__ __forceinline__ void cseg_madd(R tr, R ti, const R (&v)[SEG_REGS<R>], R (&y)[SEG_REGS<R>])
+{
+#pragma unroll
+    for (int q = 0; q < SEG_REGS<R>; q += 2) cx_madd(tr, ti, v[q], v[q + 1], y[q], y[q + 1]);
+}
+// w = w (cr + ci i)
+template <typename R> __device__ __forceinline__ void cseg_scale(R (&w)[SEG_REGS<R>], R cr, R ci)
+{
+#pragma unroll
+    for (int q = 0; q < SEG_REGS<R>; q += 2) {
+        const CxVal<R> p = cx_mul(w[q], w[q + 1], cr, ci);
+        w[q] = p.re;
+        w[q + 1] = p.im;
+    }
 }
 
 // level 2 of `cols` reductions whose segment sums sit in ctx->partials as [cols][nseg] -> out_dev[0 .. cols)

@@ -1845,19 +1845,14 @@ extern "C" int mik_spmv(mik_ctx *ctx, const mik_csr *A, const void *x, void *y)
                                : mik_spmv_launch<float>(ctx, A, (const float *)x, (float *)y, false, nullptr, nullptr);
 }
 
-template <typename T>
-static int time_spmv_impl(mik_ctx *ctx, const mik_csr *A, const void *x, void *y, int fused, int reps, double *avg_ms)
+// average milliseconds of `reps` back-to-back calls of launch() between two events on ctx->stream
+template <typename F> static int time_spmv_impl(mik_ctx *ctx, int reps, double *avg_ms, F &&launch)
 {
-    int rc = mik_ensure_partials(ctx, sizeof(T) * (size_t)std::max<int64_t>((A->n_rows + MIK_BLOCK - 1) / MIK_BLOCK, 1));
-    if (rc) return rc;
     hipEvent_t e0, e1;
     MIK_HIP(ctx, hipEventCreate(&e0));
     MIK_HIP(ctx, hipEventCreate(&e1));
     MIK_HIP(ctx, hipEventRecord(e0, ctx->stream));
-    for (int i = 0; i < reps; ++i) {
-        rc = mik_spmv_launch<T>(ctx, A, (const T *)x, (T *)y, fused != 0, (T *)ctx->partials, nullptr);
-        if (rc) return rc;
-    }
+    for (int i = 0; i < reps; ++i) MIK_TRY(launch());
     MIK_HIP(ctx, hipEventRecord(e1, ctx->stream));
     MIK_HIP(ctx, hipEventSynchronize(e1));
     float ms = 0.f;
@@ -1871,9 +1866,13 @@ static int time_spmv_impl(mik_ctx *ctx, const mik_csr *A, const void *x, void *y
 extern "C" int mik_time_spmv(mik_ctx *ctx, const mik_csr *A, const void *x, void *y, int fused_dot, int reps, double *avg_ms)
 {
     if (!ctx || !A || !x || !y || reps <= 0 || !avg_ms) return MIK_ERR_INVALID;
-    if (mik_is_complex(A->dtype)) return mik_c_time_spmv(ctx, A, x, y, reps, avg_ms);        // (no fused dot for complex operators)
-    return A->dtype == MIK_F64 ? time_spmv_impl<double>(ctx, A, x, y, fused_dot, reps, avg_ms)
-                               : time_spmv_impl<float>(ctx, A, x, y, fused_dot, reps, avg_ms);
+    if (mik_is_complex(A->dtype)) return time_spmv_impl(ctx, reps, avg_ms, [&] { return mik_c_spmv(ctx, A, x, y); });   // (no fused dot for complex operators)
+    auto real = [&](auto t) {
+        using T = decltype(t);
+        MIK_TRY(mik_ensure_partials(ctx, sizeof(T) * (size_t)std::max<int64_t>((A->n_rows + MIK_BLOCK - 1) / MIK_BLOCK, 1)));
+        return time_spmv_impl(ctx, reps, avg_ms, [&] { return mik_spmv_launch<T>(ctx, A, (const T *)x, (T *)y, fused_dot != 0, (T *)ctx->partials, nullptr); });
+    };
+    return A->dtype == MIK_F64 ? real(double{}) : real(float{});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1887,14 +1886,6 @@ template <typename T> static int reduce_to_host(mik_ctx *ctx, int64_t n, T *out)
                        (int64_t)0, (T *)ctx->coef, (const int *)nullptr);
     MIK_LAUNCH_CHECK(ctx);
     return mik_read_scalars<T>(ctx, (const T *)ctx->coef, 1, out);
-}
-
-// norm(x) from the sum of squares t the caller has just reduced: sqrt(t) (host sqrt: IEEE correctly rounded) when t
-// is inside the safe range, the scaled recomputation otherwise (include/mik.h "Norms").
-template <typename T> static int norm_from_sumsq(mik_ctx *ctx, int64_t n, const T *x, T t, T *out)
-{
-    if (mik_nrm_in_range(t)) { *out = (T)std::sqrt(t); return MIK_OK; }
-    return mik_safe_norm_slow<T>(ctx, n, x, out);
 }
 
 template <typename T> int mik_safe_norm_slow(mik_ctx *ctx, int64_t n, const T *x, T *out)
@@ -1934,7 +1925,7 @@ template <typename T> static int dot_impl(mik_ctx *ctx, int64_t n, const void *x
     T v;
     MIK_TRY(reduce_to_host<T>(ctx, n, &v));
     if (!nrm) { *(T *)out = v; return MIK_OK; }
-    return norm_from_sumsq<T>(ctx, n, (const T *)x, v, (T *)out);
+    return mik_norm_from_sumsq<T>(ctx, n, (const T *)x, v, (T *)out);
 }
 
 extern "C" int mik_dot(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void *y, void *out)
@@ -2007,7 +1998,7 @@ static int axpy_dot_impl(mik_ctx *ctx, int64_t n, const void *alpha, const void 
     T v;
     MIK_TRY(reduce_to_host<T>(ctx, n, &v));
     if (z) { *(T *)out = v; return MIK_OK; }
-    return norm_from_sumsq<T>(ctx, n, (const T *)y, v, (T *)out);           // norm(y)
+    return mik_norm_from_sumsq<T>(ctx, n, (const T *)y, v, (T *)out);           // norm(y)
 }
 
 extern "C" int mik_axpy_dot(mik_ctx *ctx, int dtype, int64_t n, const void *alpha, const void *x, void *y, const void *z, void *out,
@@ -2035,7 +2026,7 @@ static int axpy2_nrm2_impl(mik_ctx *ctx, int64_t n, const void *alpha, const voi
     MIK_TRY((launch_map<T>(ctx, n, op, vec, (T *)ctx->partials, nullptr)));
     T v;
     MIK_TRY(reduce_to_host<T>(ctx, n, &v));
-    return norm_from_sumsq<T>(ctx, n, (const T *)r, v, (T *)out);           // norm(r)
+    return mik_norm_from_sumsq<T>(ctx, n, (const T *)r, v, (T *)out);           // norm(r)
 }
 
 extern "C" int mik_axpy2_nrm2(mik_ctx *ctx, int dtype, int64_t n, const void *alpha, const void *u, void *x, const void *c, void *r,
@@ -2057,7 +2048,7 @@ template <typename T> static int xpby_nrm2_impl(mik_ctx *ctx, int64_t n, const v
     MIK_TRY((launch_map<T>(ctx, n, op, mik_aligned16(x) && mik_aligned16(y), (T *)ctx->partials, nullptr)));
     T v;
     MIK_TRY(reduce_to_host<T>(ctx, n, &v));
-    return norm_from_sumsq<T>(ctx, n, (const T *)y, v, (T *)out);           // norm(y)
+    return mik_norm_from_sumsq<T>(ctx, n, (const T *)y, v, (T *)out);           // norm(y)
 }
 
 extern "C" int mik_xpby_nrm2(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void *beta, void *y, void *out)
@@ -2104,7 +2095,7 @@ template <typename T> static int lsmr_update_impl(mik_ctx *ctx, int64_t n, const
     MIK_TRY((launch_map<T>(ctx, n, op, mik_aligned16(hbar) && mik_aligned16(h) && mik_aligned16(x) && mik_aligned16(v), (T *)ctx->partials, nullptr)));
     T s;
     MIK_TRY(reduce_to_host<T>(ctx, n, &s));
-    return norm_from_sumsq<T>(ctx, n, (const T *)x, s, (T *)out);           // norm(x)
+    return mik_norm_from_sumsq<T>(ctx, n, (const T *)x, s, (T *)out);           // norm(x)
 }
 
 extern "C" int mik_lsmr_update(mik_ctx *ctx, int dtype, int64_t n, const void *c1, const void *c2, const void *c3, void *hbar, void *h, void *x, const void *v, void *out)

@@ -7,7 +7,7 @@
 //   N form  y = A x:   chunks of MIK_DM_C columns; p_c[i] = serial sum from (+0, +0) over the chunk's columns ascending of
 //                      cx_mul(A[i, j], x[j]), re and im each their own chain; y[i] = ((p_0[i] + p_1[i]) + p_2[i]) + ... componentwise -- the
 //                      partials are [chunk][row] complex elements, which k_dense_n_combine<R> sums as 2 m reals.
-//   T form  y = A' x:  y[j] = mik_dot(A[:, j], x) of the complex mik_dot (OpCDot in csrc/mik_complex.hip): per element
+//   T form  y = A' x:  y[j] = mik_dot(A[:, j], x) of the complex mik_dot (cx_dot_acc in csrc/mik_complex.h): per element
 //                      re = ar xr + ai xi, im = ar xi - ai xr, one tree for re and one for im (pair_put / pair_total = block_tree_256,
 //                      then k_finalize_store<R> over [column][re, im][segment]).
 #pragma once
@@ -48,11 +48,7 @@ template <typename R>
 __device__ __forceinline__ void cdm_madd(const R (&a)[VT<R>::W], R xr, R xi, R (&acc)[VT<R>::W])
 {
 #pragma unroll
-    for (int e = 0; e < VT<R>::W / 2; ++e) {
-        const CxVal<R> p = cx_mul(a[2 * e], a[2 * e + 1], xr, xi);
-        acc[2 * e] = acc[2 * e] + p.re;
-        acc[2 * e + 1] = acc[2 * e + 1] + p.im;
-    }
+    for (int e = 0; e < VT<R>::W; e += 2) cx_madd(a[e], a[e + 1], xr, xi, acc[e], acc[e + 1]);
 }
 
 // p_c of one chunk for the rows of one lane: U columns are requested before the first is consumed, the consumption order is the column
@@ -131,17 +127,9 @@ __global__ __launch_bounds__(MIK_BLOCK) void k_cdense_n(int64_t m, int64_t n, co
 }
 
 // ---- T form ---------------------------------------------------------------------------------------------------------------------
-// One complex element of dot(a, x): the order of OpCDot
-template <typename R> __device__ __forceinline__ void cdm_dot_elem(R ar, R ai, R xr, R xi, R &a0, R &a1)
-{
-    const R p = ar * xr, q = ai * xi, s = ar * xi, t = ai * xr;
-    const R re = p + q, im = s - t;
-    a0 = a0 + re;
-    a1 = a1 + im;
-}
-
 // The thread sums (re, im) of Q columns against a segment that lies wholly inside the 2 m reals, 16-byte aligned: l ascending, then the
-// elements of a 16-byte group ascending, as k_cvec walks them; the Q x L loads are requested before the first is consumed.
+// elements of a 16-byte group ascending, as k_cvec walks them, each element by cx_dot_acc; the Q x L loads are requested before the
+// first is consumed.
 template <typename R, bool NT, int Q>
 __device__ __forceinline__ void cdm_dot_cols_full(const R *__restrict__ A0, int64_t lda2, int64_t base, const R (&w)[SEG_REGS<R>], R (&re)[Q], R (&im)[Q])
 {
@@ -160,7 +148,7 @@ __device__ __forceinline__ void cdm_dot_cols_full(const R *__restrict__ A0, int6
 #pragma unroll
         for (int l = 0; l < MIK_RED_L; ++l)
 #pragma unroll
-            for (int e = 0; e < W; e += 2) cdm_dot_elem(el<R>(cv[q][l], e), el<R>(cv[q][l], e + 1), w[l * W + e], w[l * W + e + 1], a0, a1);
+            for (int e = 0; e < W; e += 2) cx_dot_acc(el<R>(cv[q][l], e), el<R>(cv[q][l], e + 1), w[l * W + e], w[l * W + e + 1], a0, a1);
         re[q] = a0;
         im[q] = a1;
     }
@@ -178,11 +166,11 @@ __device__ __forceinline__ void cdm_dot_col(const R *__restrict__ col, int64_t b
         if (VEC && i + W <= n2) {
             auto cv = vload(col + i);
 #pragma unroll
-            for (int e = 0; e < W; e += 2) cdm_dot_elem(el<R>(cv, e), el<R>(cv, e + 1), w[l * W + e], w[l * W + e + 1], a0, a1);
+            for (int e = 0; e < W; e += 2) cx_dot_acc(el<R>(cv, e), el<R>(cv, e + 1), w[l * W + e], w[l * W + e + 1], a0, a1);
         } else {
 #pragma unroll
             for (int e = 0; e < W; e += 2)
-                if (i + e < n2) cdm_dot_elem(col[i + e], col[i + e + 1], w[l * W + e], w[l * W + e + 1], a0, a1);
+                if (i + e < n2) cx_dot_acc(col[i + e], col[i + e + 1], w[l * W + e], w[l * W + e + 1], a0, a1);
         }
     }
     re = a0;

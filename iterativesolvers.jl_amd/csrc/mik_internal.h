@@ -166,6 +166,13 @@ template <typename T> static inline bool mik_nrm_scale(T amax, T &s, T &sinv)
 // Over-/underflow-safe norm of a device n-vector (amax pass, exact power-of-two scaling, the same fixed-shape
 // tree over the scaled squares); *out is a host scalar.  Uses ctx->partials and the tail of ctx->coef; synchronises.
 template <typename T> int mik_safe_norm_slow(mik_ctx *ctx, int64_t n, const T *x, T *out);
+// norm(x) from the sum of squares t the caller has just reduced: sqrt(t) (host sqrt: IEEE correctly rounded) when t
+// is inside the safe range, the scaled recomputation otherwise.
+template <typename T> static inline int mik_norm_from_sumsq(mik_ctx *ctx, int64_t n, const T *x, T t, T *out)
+{
+    if (mik_nrm_in_range(t)) { *out = (T)std::sqrt(t); return MIK_OK; }
+    return mik_safe_norm_slow<T>(ctx, n, x, out);
+}
 
 extern thread_local std::string g_mik_create_error;
 extern int g_mik_tuning[MIK_KNOB_COUNT];  // DEFAULTS of the development knobs (what a new context starts with; mik_set_tuning also writes every live context)

@@ -38,8 +38,7 @@ template <typename T> int sumsq_to_norm(mik_ctx *ctx, int64_t n, const T *x, con
 {
     T t;
     MIK_TRY(mik_read_scalars<T>(ctx, dev, 1, &t));
-    if (mik_nrm_in_range(t)) { *out = (T)std::sqrt(t); return MIK_OK; }
-    return mik_safe_norm_slow<T>(ctx, n, x, out);           // include/mik.h "Norms" (uses ctx->partials and the tail of ctx->coef)
+    return mik_norm_from_sumsq<T>(ctx, n, x, t, out);       // include/mik.h "Norms" (may use ctx->partials and the tail of ctx->coef)
 }
 
 // Coefficient area (elements of T): [0, k) = h = Q' q, [k] = sum of squares of q before the pass, [k + 1] = after the update.

@@ -109,6 +109,14 @@ def test_norm_outside_the_safe_range_and_unaligned_vectors(pkg, ctx, ref, T):
     ref.axpy(T(1 - 2j), xh, want)
     uy.axpy_(T(1 - 2j), ux)
     assert np.array_equal(uy.to_numpy(), want)
+    ref.xpby(xh, T(0.5 + 3j), want)
+    uy.xpby_(ux, T(0.5 + 3j))
+    assert np.array_equal(uy.to_numpy(), want)
+    ref.scal(T(-0.25 + 1.5j), want)
+    uy.scal_(T(-0.25 + 1.5j))
+    assert np.array_equal(uy.to_numpy(), want)
+    uy.fill_(T(2 - 3j))                                                  # re != im: the complex fill, not the real one over 2 n
+    assert np.array_equal(uy.to_numpy(), np.full(n, T(2 - 3j)))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -284,21 +284,44 @@ def test_chebyshev_sweeps_and_refusals(pkg, ctx, sref, T, which):
 # ---------------------------------------------------------------------------------------------
 # the element-wise variants, each alignment term alone; a norm outside the safe range; two passes of the grid-stride loops; specials
 # ---------------------------------------------------------------------------------------------
+def check_mgs_and_gemv_n(pkg, ctx, ref, T, n, ld=None, offset=0, ks=(0, 1, 3)):
+    """Modified Gram-Schmidt and y += alpha V c on a basis with a chosen leading dimension and byte offset.  k = 0 is the norm-only pass,
+    k = 3 runs a first, a middle and a last pass."""
+    shape = ctx.reduce_shape(T)
+    rng = np.random.default_rng(n + 31)
+    V = Block(pkg, ctx, columns(rng, T, n, max(ks)), ld, offset)
+    wh, c, alpha = rnd(rng, T, n), rnd(rng, T, max(ks)), T(0.5 - 0.75j)
+    vec = lambda: Block(pkg, ctx, [wh], None, offset).col(0)
+    for k in ks:
+        w, h, want = vec(), np.zeros(max(k, 1), T), wh.copy()
+        nrm = pkg.orthogonalize_and_normalize_(V, k, w, h)
+        hh, hn = ref.mgs(V.store, V.ld, k, want, shape)
+        assert nrm.dtype == ch.real_of(T) and nrm == hn and np.array_equal(h[:k], hh) and np.array_equal(w.to_numpy(), want), k
+        if k == 0:                                                       # the sum of squares alone: the bits of norm(w)
+            assert nrm == pkg.norm(vec())
+        y, want = vec(), wh.copy()
+        pkg.gemv_n_(y, V, k, c, alpha)
+        ref.gemv_n(V.store, V.ld, k, c, alpha, want)
+        assert np.array_equal(y.to_numpy(), want), k
+
+
 # (an odd leading dimension breaks 16-byte alignment at ComplexF32 only: a ComplexF64 element is 16 bytes)
 @pytest.mark.parametrize("T,term", [(np.complex128, "base+8"), (np.complex128, "ld>n"), (np.complex64, "base+8"), (np.complex64, "ld>n"),
                                     (np.complex64, "odd ld")])
-def test_elementwise_variants(pkg, ctx, sref, T, term):
+def test_elementwise_variants(pkg, ctx, ref, sref, T, term):
     n = size_of(ctx, T, "S+1")
     if term == "base+8":
         check_gemv_t_and_gram(pkg, ctx, sref, T, n, offset=8, ks=(1, 5))
         check_mr_update(pkg, ctx, sref, T, n, offset=8, ls=(2,))
         check_axpy_dot(pkg, ctx, sref, T, n, offset=8)
         check_minres_update(pkg, ctx, sref, T, n, offset=8)
+        check_mgs_and_gemv_n(pkg, ctx, ref, T, n, offset=8)
     else:
         ld = n + 64 + (n % 2) + (term == "odd ld")                        # even and past n; one more: odd
         assert ld > n and (ld % 2 == 1) == (term == "odd ld")
         check_gemv_t_and_gram(pkg, ctx, sref, T, n, ld=ld, ks=(1, 5))
         check_mr_update(pkg, ctx, sref, T, n, ld=ld, ls=(2,))
+        check_mgs_and_gemv_n(pkg, ctx, ref, T, n, ld=ld)
 
 
 @pytest.mark.parametrize("T", CT)
