@@ -665,7 +665,26 @@ int mik_givens(int dtype, const void *f, const void *g, void *out);
  *   mik_backward_sub     the same for j > i DESCENDING
  * The triangular sweeps run a level schedule of the strict triangle built in mik_stationary_create: one launch per level with more
  * than 256 rows, one one-workgroup launch per run of narrower levels (a barrier between its levels).  Their cost is the number of
- * levels: a tridiagonal matrix (one row per level) stays latency-bound.  Asynchronous on the ctx stream. */
+ * levels: a tridiagonal matrix (one row per level) stays latency-bound.  Asynchronous on the ctx stream.
+ *
+ * ComplexF64 / ComplexF32 operators (MIK_C64 / MIK_C32, interleaved re, im; added without a version bump, additive): the same entries, the
+ * same row orders, the same level schedules and launch plans as the real operator of the same pattern.  Element operations, in Julia's
+ * promotion order: every product is (zr wr - zi wi) + (zr wi + zi wr) i with four rounded products, one difference and one sum; every
+ * add / subtract is componentwise; every division is Base's -- 64-bit components: the robust division of Baudin and Smith; 32-bit
+ * components: evaluated in double with mag = 1 / fma(c, c, d d), re = fma(a, c, b d) mag, im = fma(b, c, -(a d)) mag and rounded to float once
+ * per component (the only two FMAs of the library).  Base's branches for infinite divisors are not restated: operators are finite with
+ * non-zero diagonals.  Vectors need alignment to their component only; vectors aligned to their element take one 16- / 8-byte access an
+ * element, with identical results.
+ *   mik_diag_ldiv        y[i] = x[i] / A[i,i] in the data type
+ *   mik_offdiag_mul, mik_gs_multiply   alpha, beta: host COMPLEX scalars of the operator's type; acc += A[i,j] * (alpha * x[j]), two complex
+ *                        products a term; beta == one(T) and iszero(beta) compare both components (either sign of zero), else beta * y[i]
+ *   mik_forward_sub, mik_backward_sub   plain: x[i] -= A[i,j] * x[j] ..., x[i] = x[i] / A[i,i], all in the data type.  Relaxed:
+ *                        scalar_dtype (MIK_F64 / MIK_F32) names the REAL component type E of the evaluation; alpha is a host REAL of E
+ *                        (omega is Real in the reference), beta a host COMPLEX pair (re, im) of E (one(T) - omega, imaginary part +0.0).
+ *                        a = (alpha re(x[i]), alpha im(x[i])) in E; x[i] = T(a / E(A[i,i]) + beta * E(y[i])), one rounding per component at
+ *                        the store: ComplexF32 data with MIK_F64 scalars divides with the 64-bit algorithm, with MIK_F32 scalars with the
+ *                        widened 32-bit one; ComplexF64 data always evaluates in double.  The subtractions stay in the data type.
+ *   mik_stationary_create   a diagonal entry is zero when both components are (either sign). */
 typedef struct mik_stationary mik_stationary;    /* DiagonalIndices + the triangular views of one square operator -- :6-64 */
 /* DiagonalIndices(A) (:6-28) + both level schedules.  Reads A's CSR arrays once (A's layouts are untouched; A must outlive *out).
  * MIK_ERR_SINGULAR with *singular_col = the first 1-based column whose diagonal entry is missing or zero (-0.0 included);

@@ -308,7 +308,7 @@ def dtype_code(dtype) -> int:
 
 
 def real_dtype_code(dtype, who: str) -> int:
-    """``dtype_code`` for what stays real: svdl, the stationary methods and the extras."""
+    """``dtype_code`` for what stays real: svdl, the dense stationary methods and the extras."""
     if np.dtype(dtype).kind == "c":
         raise TypeError(f"{who} is not offered for complex element types (DESIGN.md sections 17 - 20: cg, gmres, bicgstabl, minres and chebyshev "
                         "on a CSR or dense operator are, and lobpcg on a CSR operator)")

@@ -13,6 +13,55 @@ template <typename R> __host__ __device__ __forceinline__ CxVal<R> cx_mul(R zr, 
     return CxVal<R>{a - b, c + d};
 }
 
+// z / w for finite operands and w != 0: Base's two methods, restated.  No contraction except the two fma of the
+// widened form, which are explicit calls; tests/complex_ref/complex_stationary_ref.c restates exactly this.
+//   64-bit components: the robust division of Baudin and Smith (Base's /(::ComplexF64, ::ComplexF64))
+//   32-bit components: evaluated in double -- mag = 1 / fma(c, c, d d), re = fma(a, c, b d) mag, im = fma(b, c, -(a d)) mag -- and
+//                      rounded to float once per component (Base's widened method)
+__host__ __device__ __forceinline__ double cx_div2(double a, double b, double c, double d, double r, double t)
+{
+    if (r != 0.0) {
+        const double br = b * r;
+        if (br != 0.0) return (a + br) * t;
+        const double at = a * t, bt = b * t;
+        return at + bt * r;
+    }
+    const double bc = b / c;
+    return (a + d * bc) * t;
+}
+__host__ __device__ __forceinline__ void cx_div1(double a, double b, double c, double d, double &p, double &q)
+{
+    const double r = d / c;
+    const double t = 1.0 / (c + d * r);
+    p = cx_div2(a, b, c, d, r, t);
+    q = cx_div2(b, -a, c, d, r, t);
+}
+__host__ __device__ __forceinline__ CxVal<double> cx_div(double a, double b, double c, double d)
+{
+    constexpr double HALF_OV = 0x1.fffffffffffffp+1022;      // floatmax / 2
+    constexpr double TWO_UN_EPS = 0x1p-969;                  // floatmin * 2 / eps
+    constexpr double BS = 0x1p+105;                          // 2 / eps^2
+    const double absa = a < 0.0 ? -a : a, absb = b < 0.0 ? -b : b, absc = c < 0.0 ? -c : c, absd = d < 0.0 ? -d : d;
+    const double ab = absa >= absb ? absa : absb, cd = absc >= absd ? absc : absd;
+    double s = 1.0;
+    if (ab >= HALF_OV) { a = a * 0.5; b = b * 0.5; s = s * 2.0; }
+    if (cd >= HALF_OV) { c = c * 0.5; d = d * 0.5; s = s * 0.5; }
+    if (ab <= TWO_UN_EPS) { a = a * BS; b = b * BS; s = s / BS; }
+    if (cd <= TWO_UN_EPS) { c = c * BS; d = d * BS; s = s * BS; }
+    double p, q;
+    if (absd <= absc) cx_div1(a, b, c, d, p, q);
+    else { cx_div1(b, a, d, c, p, q); q = -q; }
+    return CxVal<double>{p * s, q * s};
+}
+__host__ __device__ __forceinline__ CxVal<float> cx_div(float af, float bf, float cf, float df)
+{
+    const double a = (double)af, b = (double)bf, c = (double)cf, d = (double)df;
+    const double dd = d * d, bd = b * d, ad = a * d;
+    const double mag = 1.0 / __builtin_fma(c, c, dd);
+    const double re = __builtin_fma(a, c, bd) * mag, im = __builtin_fma(b, c, -ad) * mag;
+    return CxVal<float>{(float)re, (float)im};
+}
+
 // mik_csr_create with a complex dtype: host transpose + validation, the operator runs on its CSR arrays (rows longer than
 // MIK_LONG_ROW entries are listed as wave segments).  on_device: the three arrays are device memory and are staged on the host.
 int mik_c_csr_create(mik_ctx *ctx, int dtype, int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t *ptr, const int64_t *idx,

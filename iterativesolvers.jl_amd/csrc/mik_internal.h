@@ -260,7 +260,8 @@ int mik_build_rperm_host(mik_ctx *ctx, mik_csr *A, const int *rowptr_host);   //
 // scalar passed with MIK_SCALAR_REAL
 static inline bool mik_is_complex(int dtype) { return dtype == MIK_C64 || dtype == MIK_C32; }
 static inline int mik_real_dtype(int dtype) { return dtype == MIK_C64 ? MIK_F64 : MIK_F32; }
-// a complex operator is served by mik_spmv and the operator queries only: every other entry with a mik_csr argument refuses it
+// a complex operator is served by mik_spmv, mik_spmm, mik_stationary_create and the operator queries: every other entry with a mik_csr
+// argument refuses it
 #define MIK_REFUSE_COMPLEX(ctx, A, who)                                                                                          \
     do {                                                                                                                         \
         if ((A) && mik_is_complex((A)->dtype))                                                                                   \

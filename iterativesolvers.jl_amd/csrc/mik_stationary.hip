@@ -10,8 +10,13 @@
 //   - a launch plan: a level with more than MIK_ST_NARROW rows is one launch; a run of consecutive narrow levels is one launch of one
 //     workgroup that steps through them with a barrier in between.  No workgroup ever waits for another one.
 // The operator's own layouts and upload are untouched.
+//
+// A ComplexF64 / ComplexF32 operator (MIK_C64 / MIK_C32) goes through the same analysis -- it is written over an element size in bytes, and a
+// complex mik_csr keeps every row, long ones included, contiguous in rowptr / col / val (csrc/mik_complex.hip: n_long stays 0), so the
+// read-back takes the plain path -- and through the kernels of csrc/mik_stationary_complex.h.
 #include "mik_internal.h"
 #include "mik_stationary.h"
+#include "mik_stationary_complex.h"
 
 #include <chrono>
 #include <new>
@@ -119,6 +124,8 @@ int st_build_tri(mik_stationary *S, StTri &T, bool upper, const std::vector<int>
 
 bool st_is_zero(const unsigned char *v, int dtype)
 {
+    if (dtype == MIK_C64) { double a[2]; memcpy(a, v, 16); return a[0] == 0.0 && a[1] == 0.0; }     // iszero(z): both parts, either sign
+    if (dtype == MIK_C32) { float a[2]; memcpy(a, v, 8); return a[0] == 0.0f && a[1] == 0.0f; }
     if (dtype == MIK_F64) { double a; memcpy(&a, v, 8); return a == 0.0; }      // -0.0 == 0.0: iszero(-0.0) is true
     float a; memcpy(&a, v, 4); return a == 0.0f;
 }
@@ -223,6 +230,8 @@ int st_tri(mik_stationary *St, const StTri &T_, S alpha, T *x, S beta, const T *
 template <typename T>
 T st_scalar(const void *p) { T v; memcpy(&v, p, sizeof(T)); return v; }
 
+int cst_sub(mik_stationary *St, const StTri &T_, const void *alpha, void *x, const void *beta, const void *y, int scalar_dtype);      // complex, below
+
 int st_sub(mik_stationary *St, bool upper, const void *alpha, void *x, const void *beta, const void *y, int scalar_dtype, const char *who)
 {
     if (!St || !x) return MIK_ERR_INVALID;
@@ -231,6 +240,7 @@ int st_sub(mik_stationary *St, bool upper, const void *alpha, void *x, const voi
     if (y == x) return mik_fail(St->ctx, MIK_ERR_INVALID, "%s: x and y must not alias", who);
     if (St->n == 0) return MIK_OK;
     const StTri &T_ = upper ? St->up : St->lo;
+    if (mik_is_complex(St->dtype)) return cst_sub(St, T_, alpha, x, beta, y, scalar_dtype);
     if (St->dtype == MIK_F64) {
         double *xd = (double *)x;
         if (!y) return st_tri<double, double, false>(St, T_, 0.0, xd, 0.0, nullptr);
@@ -275,6 +285,110 @@ int st_gs(mik_stationary *St, bool upper, const void *alpha, const void *x, cons
     return MIK_OK;
 }
 
+// ---- complex operators: R = the component type, scalars are (re, im) pairs -----------------------------------------------------------
+template <typename R>
+bool cst_aligned(std::initializer_list<const void *> ps)
+{
+    for (const void *p : ps)
+        if (p && (uintptr_t)p % (2 * sizeof(R)) != 0) return false;
+    return true;
+}
+
+template <typename R, typename E, bool RELAX>
+int cst_tri(mik_stationary *St, const StTri &T_, E alpha, R *x, E ber, E bei, const R *y)
+{
+    mik_ctx *ctx = St->ctx;
+    const int vec = cst_aligned<R>({x, y}) ? 1 : 0;
+    for (const StLaunch &L : T_.plan) {
+        if (L.narrow)
+            hipLaunchKernelGGL((k_cst_tri_run<R, E, RELAX>), dim3(1), dim3(MIK_ST_BLOCK), 0, ctx->stream, L.a, L.b, T_.lev, T_.perm, T_.tp, T_.tc,
+                               (const R *)T_.tv, (const R *)St->d, alpha, x, ber, bei, y, vec);
+        else
+            hipLaunchKernelGGL((k_cst_tri_level<R, E, RELAX>), dim3(st_grid(L.b - L.a)), dim3(MIK_ST_BLOCK), 0, ctx->stream, L.a, L.b, T_.perm, T_.tp,
+                               T_.tc, (const R *)T_.tv, (const R *)St->d, alpha, x, ber, bei, y, vec);
+    }
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
+// alpha: a host REAL of scalar_dtype (omega is Real in the reference); beta: a host COMPLEX pair of scalar_dtype (one(T) - omega)
+template <typename E>
+void cst_relax_scalars(const void *alpha, const void *beta, int scalar_dtype, E &a, E &br, E &bi)
+{
+    if (scalar_dtype == MIK_F64) {
+        double b[2]; memcpy(b, beta, sizeof b);
+        a = (E)st_scalar<double>(alpha); br = (E)b[0]; bi = (E)b[1];
+    } else {
+        float b[2]; memcpy(b, beta, sizeof b);
+        a = (E)st_scalar<float>(alpha); br = (E)b[0]; bi = (E)b[1];
+    }
+}
+
+int cst_sub(mik_stationary *St, const StTri &T_, const void *alpha, void *x, const void *beta, const void *y, int scalar_dtype)
+{
+    if (St->dtype == MIK_C64) {       // ComplexF64 data: every omega type evaluates in Float64
+        double *xd = (double *)x;
+        if (!y) return cst_tri<double, double, false>(St, T_, 0.0, xd, 0.0, 0.0, nullptr);
+        double a, br, bi;
+        cst_relax_scalars(alpha, beta, scalar_dtype, a, br, bi);
+        return cst_tri<double, double, true>(St, T_, a, xd, br, bi, (const double *)y);
+    }
+    float *xf = (float *)x;
+    if (!y) return cst_tri<float, float, false>(St, T_, 0.0f, xf, 0.0f, 0.0f, nullptr);
+    if (scalar_dtype == MIK_F64) {    // ComplexF32 data, Float64 omega: the 64-bit division, one rounding per component at the store
+        double a, br, bi;
+        cst_relax_scalars(alpha, beta, scalar_dtype, a, br, bi);
+        return cst_tri<float, double, true>(St, T_, a, xf, br, bi, (const float *)y);
+    }
+    float a, br, bi;
+    cst_relax_scalars(alpha, beta, scalar_dtype, a, br, bi);
+    return cst_tri<float, float, true>(St, T_, a, xf, br, bi, (const float *)y);
+}
+
+template <typename R>
+int cst_diag_ldiv(mik_stationary *St, void *y, const void *x)
+{
+    hipLaunchKernelGGL((k_cst_diag_ldiv<R>), dim3(st_grid(St->n)), dim3(MIK_ST_BLOCK), 0, St->ctx->stream, St->n, (const R *)St->d, (const R *)x, (R *)y,
+                       cst_aligned<R>({x, y}) ? 1 : 0);
+    MIK_LAUNCH_CHECK(St->ctx);
+    return MIK_OK;
+}
+
+template <typename R>
+int cst_offdiag(mik_stationary *St, const void *alpha, const void *x, const void *beta, void *y)
+{
+    R a[2], b[2];
+    memcpy(a, alpha, sizeof a);
+    memcpy(b, beta, sizeof b);
+    const int bmode = (b[0] == R(1) && b[1] == R(0)) ? 1 : ((b[0] == R(0) && b[1] == R(0)) ? 0 : 2);      // beta != one(T); iszero(beta)
+    hipLaunchKernelGGL((k_cst_offdiag<R>), dim3(st_grid(St->n)), dim3(MIK_ST_BLOCK), 0, St->ctx->stream, St->n, St->rp, St->cl, (const R *)St->vl, St->dg,
+                       a[0], a[1], (const R *)x, b[0], b[1], bmode, (R *)y, cst_aligned<R>({x, y}) ? 1 : 0);
+    MIK_LAUNCH_CHECK(St->ctx);
+    return MIK_OK;
+}
+
+template <typename R>
+int cst_gs(mik_stationary *St, bool upper, const void *alpha, const void *x, const void *beta, const void *y, void *z)
+{
+    R a[2], b[2];
+    memcpy(a, alpha, sizeof a);
+    memcpy(b, beta, sizeof b);
+    const R *xs = (const R *)x;
+    if (z == x) {       // as st_gs: every row reads the OLD x
+        MIK_HIP(St->ctx, hipMemcpyAsync(St->tmp, x, 2 * sizeof(R) * (size_t)St->n, hipMemcpyDeviceToDevice, St->ctx->stream));
+        xs = (const R *)St->tmp;
+    }
+    const int vec = cst_aligned<R>({xs, y, z}) ? 1 : 0;
+    if (upper)
+        hipLaunchKernelGGL((k_cst_gs_mul<R, true>), dim3(st_grid(St->n)), dim3(MIK_ST_BLOCK), 0, St->ctx->stream, St->n, St->rp, St->cl, (const R *)St->vl,
+                           St->dg, a[0], a[1], xs, b[0], b[1], (const R *)y, (R *)z, vec);
+    else
+        hipLaunchKernelGGL((k_cst_gs_mul<R, false>), dim3(st_grid(St->n)), dim3(MIK_ST_BLOCK), 0, St->ctx->stream, St->n, St->rp, St->cl, (const R *)St->vl,
+                           St->dg, a[0], a[1], xs, b[0], b[1], (const R *)y, (R *)z, vec);
+    MIK_LAUNCH_CHECK(St->ctx);
+    return MIK_OK;
+}
+
 }  // namespace
 
 extern "C" int mik_stationary_create(mik_ctx *ctx, const mik_csr *A, int64_t *singular_col, mik_stationary **out)
@@ -282,7 +396,6 @@ extern "C" int mik_stationary_create(mik_ctx *ctx, const mik_csr *A, int64_t *si
     if (singular_col) *singular_col = 0;
     if (!ctx || !A || !out) return MIK_ERR_INVALID;
     *out = nullptr;
-    MIK_REFUSE_COMPLEX(ctx, A, "mik_stationary_create");
     if (A->n_rows != A->n_cols)
         return mik_fail(ctx, MIK_ERR_MISMATCH, "mik_stationary_create: the operator is %lld x %lld, not square", (long long)A->n_rows, (long long)A->n_cols);
     if (!A->col || !A->rowptr || !A->val)
@@ -320,6 +433,7 @@ extern "C" int mik_diag_ldiv(mik_stationary *S, void *y, const void *x)
 {
     if (!S || !x || !y) return MIK_ERR_INVALID;
     if (S->n == 0) return MIK_OK;
+    if (mik_is_complex(S->dtype)) return S->dtype == MIK_C64 ? cst_diag_ldiv<double>(S, y, x) : cst_diag_ldiv<float>(S, y, x);
     if (S->dtype == MIK_F64)
         hipLaunchKernelGGL((k_st_diag_ldiv<double>), dim3(st_grid(S->n)), dim3(MIK_ST_BLOCK), 0, S->ctx->stream, S->n, (const double *)S->d, (const double *)x, (double *)y);
     else
@@ -333,6 +447,7 @@ extern "C" int mik_offdiag_mul(mik_stationary *S, const void *alpha, const void 
     if (!S || !alpha || !beta || !x || !y) return MIK_ERR_INVALID;
     if (x == y) return mik_fail(S->ctx, MIK_ERR_INVALID, "mik_offdiag_mul: x and y must not alias");
     if (S->n == 0) return MIK_OK;
+    if (mik_is_complex(S->dtype)) return S->dtype == MIK_C64 ? cst_offdiag<double>(S, alpha, x, beta, y) : cst_offdiag<float>(S, alpha, x, beta, y);
     return S->dtype == MIK_F64 ? st_offdiag<double>(S, alpha, x, beta, y) : st_offdiag<float>(S, alpha, x, beta, y);
 }
 
@@ -340,6 +455,8 @@ extern "C" int mik_gs_multiply(mik_stationary *S, int upper, const void *alpha, 
 {
     if (!S || !alpha || !beta || !x || !y || !z) return MIK_ERR_INVALID;
     if (S->n == 0) return MIK_OK;
+    if (mik_is_complex(S->dtype))
+        return S->dtype == MIK_C64 ? cst_gs<double>(S, upper != 0, alpha, x, beta, y, z) : cst_gs<float>(S, upper != 0, alpha, x, beta, y, z);
     return S->dtype == MIK_F64 ? st_gs<double>(S, upper != 0, alpha, x, beta, y, z) : st_gs<float>(S, upper != 0, alpha, x, beta, y, z);
 }
 

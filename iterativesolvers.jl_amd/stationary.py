@@ -19,6 +19,9 @@ rows are summed in the reference's order, so the iterates are bit-identical to t
 The relaxation parameter keeps Julia's types: a Python ``float`` (or ``np.float64``) is a Float64 omega, an
 ``np.float32`` a Float32 one, an ``int`` an Int (promoted to the element type, as Julia does).  With Float32
 data and a Float64 omega, ``alpha * x / d + beta * y`` runs in Float64 and rounds once at the store.
+
+A ``complex128`` / ``complex64`` operator runs the same statements on ComplexF64 / ComplexF32:
+omega stays real, ``one(T) - omega`` is complex with imaginary part ``+0.0``, and ``-one(T)`` is ``(-1.0, -0.0)``.
 """
 from __future__ import annotations
 
@@ -48,9 +51,20 @@ def _host(dtype, value):
     return a, a.ctypes.data_as(_vp)
 
 
+def _minus_one(T):
+    """``-one(T)``: Julia's unary minus negates both parts, so a complex T gives ``(-1.0, -0.0)``."""
+    return complex(-1.0, -0.0) if np.dtype(T).kind == "c" else -1
+
+
 def _relax_scalars(T, omega):
-    """(alpha, beta, scalar dtype) of forward_sub!(omega, L, x, one(T) - omega, y) with Julia's promotion."""
+    """(alpha, beta, scalar dtype) of forward_sub!(omega, L, x, one(T) - omega, y) with Julia's promotion.  For a complex T the
+    scalar dtype E is the REAL type of promote(real(T), typeof(omega)); alpha is a real of E, beta a complex of E with
+    imaginary part +0.0 (``one(T) - omega`` subtracts a real from the real part only)."""
     T = np.dtype(T)
+    if T.kind == "c":
+        a, _, E = _relax_scalars(T.type(0).real.dtype, omega)
+        CE = np.result_type(E, np.complex64)
+        return a, CE.type(complex(E.type(E.type(1) - a), 0.0)), E
     if isinstance(omega, np.floating):
         S = np.result_type(T, omega.dtype)
     elif isinstance(omega, (bool, np.bool_)) or isinstance(omega, numbers.Integral):
@@ -123,7 +137,7 @@ class StationaryOperator:
             return x
         a, b, S = _relax_scalars(self.dtype, omega)
         _a, pa = _host(S, a)
-        _b, pb = _host(S, b)
+        _b, pb = _host(b.dtype, b)                  # of S, or (complex operator) the complex type over S
         self._check(fn(self.handle, pa, px, pb, self._vec(y, "y"), _lib.dtype_code(S)), where)
         return x
 
@@ -175,8 +189,9 @@ class JacobiIterable(_StationaryIterable):                                      
         self.O, self.x, self.next, self.b, self.maxiter = O, x, next, b, int(maxiter)
 
     def _step(self):                                                                # :225-234
+        m1 = _minus_one(self.x.dtype)                                               # T = eltype(x); -one(T)  
         self.next.copyto_(self.b)                                                   # copyto!(j.next, j.b)
-        self.O.offdiag_mul_(-1, self.x, 1, self.next)                               # mul!(-one(T), j.O, j.x, one(T), j.next)
+        self.O.offdiag_mul_(m1, self.x, 1, self.next)                               # mul!(-one(T), j.O, j.x, one(T), j.next)
         self.O.diag_ldiv_(self.x, self.next)                                        # ldiv!(j.x, j.O.diag, j.next)
 
 
@@ -186,7 +201,8 @@ class GaussSeidelIterable(_StationaryIterable):                                 
         self.x, self.b, self.maxiter = x, b, int(maxiter)
 
     def _step(self):                                                                # :278-288
-        self.U.gs_multiply_(True, -1, self.x, 1, self.b, self.x)                    # gauss_seidel_multiply!(-one(T), g.U, g.x, one(T), g.b, g.x)
+        m1 = _minus_one(self.x.dtype)                                               # T = eltype(x); -one(T)  
+        self.U.gs_multiply_(True, m1, self.x, 1, self.b, self.x)                    # gauss_seidel_multiply!(-one(T), g.U, g.x, one(T), g.b, g.x)
         self.L.forward_sub_(self.x)                                                 # forward_sub!(g.L, g.x)
 
 
@@ -197,7 +213,8 @@ class SORIterable(_StationaryIterable):                                         
         self.x, self.next, self.b, self.maxiter = x, next, b, int(maxiter)
 
     def _step(self):                                                                # :322-336
-        self.U.gs_multiply_(True, -1, self.x, 1, self.b, self.next)                 # next = b - U * x
+        m1 = _minus_one(self.x.dtype)                                               # T = eltype(x); -one(T)  
+        self.U.gs_multiply_(True, m1, self.x, 1, self.b, self.next)                 # next = b - U * x
         self.L.forward_sub_(self.next, self.omega, self.x)                          # next = omega * inv(L) * next + (1 - omega) * x
         self.x, self.next = self.next, self.x                                       # switch current and next iterate
 
@@ -209,9 +226,10 @@ class SSORIterable(_StationaryIterable):                                        
         self.x, self.tmp, self.b, self.maxiter = x, tmp, b, int(maxiter)
 
     def _step(self):                                                                # :392-418
-        self.sU.gs_multiply_(True, -1, self.x, 1, self.b, self.tmp)                 # tmp = b - U * x
+        m1 = _minus_one(self.x.dtype)                                               # T = eltype(x); -one(T)  
+        self.sU.gs_multiply_(True, m1, self.x, 1, self.b, self.tmp)                 # tmp = b - U * x
         self.L.forward_sub_(self.tmp, self.omega, self.x)                           # tmp = omega * inv(L) * tmp + (1 - omega) * x
-        self.sL.gs_multiply_(False, -1, self.tmp, 1, self.b, self.x)                # x = b - L * tmp
+        self.sL.gs_multiply_(False, m1, self.tmp, 1, self.b, self.x)                # x = b - L * tmp
         self.U.backward_sub_(self.x, self.omega, self.tmp)                          # x = omega * inv(U) * x + (1 - omega) * tmp
 
 
