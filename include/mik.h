@@ -379,12 +379,22 @@ int mik_xpby_nrm2(mik_ctx *ctx, int dtype, int64_t n, const void *x, const void 
 int mik_lsqr_update(mik_ctx *ctx, int dtype, int64_t n, const void *t1, const void *t2, const void *inv_rho, void *x, void *w, const void *v, void *out);
 int mik_lsmr_update(mik_ctx *ctx, int dtype, int64_t n, const void *c1, const void *c2, const void *c3, void *hbar, void *h, void *x, const void *v, void *out);
 /* QMR (src/qmr.jl), groups of consecutive statements as single sweeps with the same per-element operations:
- *   mik_axpy2_dot    y .+= a .* x1; y .+= b .* x2 (x2 may be NULL); *out = dot(y, z) (z may be NULL: no reduction, out untouched)
+ *   mik_axpy2_dot    y .+= a .* x1; y .+= b .* x2 (x2 may be NULL); *out = dot(z, y) = sum conj(z[i]) y[i] (z may be NULL: no reduction,
+ *                    out untouched).  z is the conjugated argument: what both callers need -- QMR passes y = w_next, z = v_next for
+ *                    vw = dot(v_next, w_next), IDR(s) y = G[k], z = P[i + 1] for dot(P[i + 1], G[k]); for the real types the order is immaterial
  *                    -- the two axpy! of a Lanczos vector (:70-72 / :76-78) and, for the second vector, vw = dot(v_next, w_next) (:81)
  *   mik_scal2        x .*= a; y .*= b                                                                             (:90-91)
- *   mik_qmr_update   p = v - h1 p_curr - h0 p_prev (either may be NULL), p .*= inv, x .+= g .* p; p is stored at p_out, the next p_curr
- *                    (p_out may be p_prev's storage: the caller rotates names instead of the two copies of :196-197)  (:188-197)
- * Scalars: HOST values of `dtype` (neg_h1 = -H[2], neg_h0 = -H[1]). */
+ *   mik_qmr_update   p = v; p .+= neg_h1 .* p_curr; p .+= neg_h0 .* p_prev (either vector may be NULL), p .*= inv, x .+= g .* p; p is stored at
+ *                    p_out, the next p_curr (p_out may be p_prev's storage: the caller rotates names instead of the two copies of :196-197;
+ *                    p_out == v or p_out == p_curr is MIK_ERR_INVALID)                                             (:188-197)
+ * Scalars: HOST values of `dtype` (neg_h1 = -H[2], neg_h0 = -H[1]).
+ * complex (MIK_C64 / MIK_C32): every scalar is a host complex (re, im) of `dtype`; each axpy is the rounded complex product (zr wr - zi wi,
+ * zr wi + zi wr) followed by one rounded add per component, each scaling the product x * a, in the statement order above, nothing
+ * contracted; *out is one host complex with the bits of the complex mik_dot(z, y) (one tree for re, one for im).  With MIK_SCALAR_REAL
+ * or-ed into dtype EVERY scalar of the call is a host real of the component type that multiplies as real x complex: mik_scal2,
+ * mik_qmr_update and mik_axpy2_dot with z NULL are then the real sweeps over the 2 n interleaved reals (the same bits by construction);
+ * mik_axpy2_dot with z keeps the complex dot.  The 16-byte variant runs when every vector is 16-byte aligned, the element-wise one
+ * otherwise; both give the same bits.  The NULL and aliasing rules are those of the real codes. */
 int mik_axpy2_dot(mik_ctx *ctx, int dtype, int64_t n, const void *a, const void *x1, const void *b, const void *x2, void *y, const void *z, void *out);
 int mik_scal2(mik_ctx *ctx, int dtype, int64_t n, const void *a, void *x, const void *b, void *y);
 int mik_qmr_update(mik_ctx *ctx, int dtype, int64_t n, const void *v, const void *neg_h1, const void *p_curr, const void *neg_h0, const void *p_prev,

@@ -86,6 +86,13 @@ int mik_c_axpy_dot(mik_ctx *ctx, int dtype, int64_t n, int real_alpha, const voi
 int mik_c_minres_update(mik_ctx *ctx, int dtype, int64_t n, const void *inv_h3, void *v_next, const void *v_curr, const void *neg_h1, const void *w_curr,
                         const void *neg_h0, const void *w_prev, const void *inv_h2, void *w_next, const void *rhs0, void *x);
 int mik_c_bicgstab_mr_update(mik_ctx *ctx, int dtype, int64_t n, int l, void *us, int64_t ldu, void *rs, int64_t ldr, void *x, const void *gamma, void *out);
+// the QMR sweeps; scalars: host complex (real_scalars: host reals, only with z != NULL -- the other real-scalar forms
+// are the real entries over 2 n and never come here).  out: one host complex, dot(z, y)
+int mik_c_axpy2_dot(mik_ctx *ctx, int dtype, int64_t n, int real_scalars, const void *a, const void *x1, const void *b, const void *x2, void *y, const void *z,
+                    void *out);
+int mik_c_scal2(mik_ctx *ctx, int dtype, int64_t n, const void *a, void *x, const void *b, void *y);
+int mik_c_qmr_update(mik_ctx *ctx, int dtype, int64_t n, const void *v, const void *neg_h1, const void *p_curr, const void *neg_h0, const void *p_prev,
+                     const void *inv, const void *g, void *x, void *p_out);
 // host
 int mik_c_lu_solve(int dtype, void *A, int64_t lda, int n, void *b);
 int mik_c_givens(int dtype, const void *f, const void *g, void *out);

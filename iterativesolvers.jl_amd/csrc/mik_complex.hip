@@ -950,6 +950,145 @@ int mik_c_bicgstab_mr_update(mik_ctx *ctx, int dtype, int64_t n, int l, void *us
     return c_typed(dtype, [&](auto r) { return c_bicg_mr<decltype(r)>(ctx, n, l, us, ldu, rs, ldr, x, gamma, out); });
 }
 
+// ---- the three QMR sweeps on complex vectors -- src/qmr.jl:70-78, :81, :90-91, :188-197 ---------------------------
+// Complex scalars by value as (re, im); with REAL (MIK_SCALAR_REAL and a reduction) a and b are reals that multiply as real x complex.
+// The operands are not __restrict__: p_out may be p_prev's storage (a thread reads its elements of a segment before it writes them).
+template <typename R> struct CPair { R re, im; };
+
+// y += a x1; y += b x2 (x2 may be NULL); z != NULL: the segment sums of dot(z, y) = sum conj(z_i) y_i, re then im: the bits of mik_dot
+template <typename R, bool VEC, bool REAL>
+__global__ __launch_bounds__(MIK_BLOCK) void k_caxpy2_dot(int64_t n2, int64_t nseg, const R *x1, const R *x2, R *y, const R *z, CPair<R> a, CPair<R> b,
+                                                          R *__restrict__ seg_out)
+{
+    constexpr int64_t SEG = (int64_t)MIK_BLOCK * SEG_REGS<R>;
+    __shared__ R lds4[4];
+    for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const int64_t base = s * SEG + (int64_t)VT<R>::W * threadIdx.x;
+        R yy[SEG_REGS<R>], t[SEG_REGS<R>];
+        seg_load<R, VEC>(y, base, n2, 0, yy);
+        seg_load<R, VEC>(x1, base, n2, 0, t);
+#pragma unroll
+        for (int q = 0; q < SEG_REGS<R>; q += 2) {
+            if (REAL) cx_madd_real(a.re, t[q], t[q + 1], yy[q], yy[q + 1]);
+            else cx_madd(a.re, a.im, t[q], t[q + 1], yy[q], yy[q + 1]);
+        }
+        if (x2) {
+            seg_load<R, VEC>(x2, base, n2, 0, t);
+#pragma unroll
+            for (int q = 0; q < SEG_REGS<R>; q += 2) {
+                if (REAL) cx_madd_real(b.re, t[q], t[q + 1], yy[q], yy[q + 1]);
+                else cx_madd(b.re, b.im, t[q], t[q + 1], yy[q], yy[q + 1]);
+            }
+        }
+        seg_store<R, VEC>(y, base, n2, yy);
+        if (z) {
+            seg_load<R, VEC>(z, base, n2, 0, t);
+            R re, im;
+            cseg_dot<R>(t, yy, base, n2, re, im);
+            const R tre = block_tree_256(re, lds4);
+            if (threadIdx.x == 0) seg_out[s] = tre;
+            const R tim = block_tree_256(im, lds4);
+            if (threadIdx.x == 0) seg_out[nseg + s] = tim;
+        }
+    }
+}
+
+template <typename R>
+static int c_axpy2_dot(mik_ctx *ctx, int64_t n, int real_scalars, const void *av, const void *x1, const void *bv, const void *x2, void *y, const void *z, void *out)
+{
+    const R *ap = (const R *)av, *bp = (const R *)bv;
+    const CPair<R> a{ap[0], real_scalars ? R(0) : ap[1]}, b{x2 ? bp[0] : R(0), (x2 && !real_scalars) ? bp[1] : R(0)};
+    const int64_t nseg = mik_nseg<R>(2 * n);
+    if (nseg == 0) { if (z) { ((R *)out)[0] = R(0); ((R *)out)[1] = R(0); } return MIK_OK; }
+    if (z) MIK_TRY(mik_ensure_partials(ctx, sizeof(R) * 2 * (size_t)nseg));
+    const bool vec = mik_aligned16(y) && mik_aligned16(x1) && (!x2 || mik_aligned16(x2)) && (!z || mik_aligned16(z));
+    MIK_TRY((launch_segments<R>(ctx, 2 * n, vec, 0, [&](auto v, int grid, int64_t ns) {
+        if (real_scalars)
+            hipLaunchKernelGGL((k_caxpy2_dot<R, decltype(v)::value, true>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, 2 * n, ns, (const R *)x1, (const R *)x2, (R *)y,
+                               (const R *)z, a, b, (R *)ctx->partials);
+        else
+            hipLaunchKernelGGL((k_caxpy2_dot<R, decltype(v)::value, false>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, 2 * n, ns, (const R *)x1, (const R *)x2, (R *)y,
+                               (const R *)z, a, b, (R *)ctx->partials);
+    })));
+    if (!z) return MIK_OK;
+    return c_sums_to_host<R>(ctx, nseg, 2, (R *)out);
+}
+
+int mik_c_axpy2_dot(mik_ctx *ctx, int dtype, int64_t n, int real_scalars, const void *a, const void *x1, const void *b, const void *x2, void *y, const void *z,
+                    void *out)
+{
+    return c_typed(dtype, [&](auto r) { return c_axpy2_dot<decltype(r)>(ctx, n, real_scalars, a, x1, b, x2, y, z, out); });
+}
+
+// x *= a; y *= b
+template <typename R, bool VEC>
+__global__ __launch_bounds__(MIK_BLOCK) void k_cscal2(int64_t n2, int64_t nseg, R *x, R *y, CPair<R> a, CPair<R> b)
+{
+    constexpr int64_t SEG = (int64_t)MIK_BLOCK * SEG_REGS<R>;
+    for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const int64_t base = s * SEG + (int64_t)VT<R>::W * threadIdx.x;
+        R xx[SEG_REGS<R>], yy[SEG_REGS<R>];
+        seg_load<R, VEC>(x, base, n2, 0, xx);
+        seg_load<R, VEC>(y, base, n2, 0, yy);
+        cseg_scale<R>(xx, a.re, a.im);
+        cseg_scale<R>(yy, b.re, b.im);
+        seg_store<R, VEC>(x, base, n2, xx);
+        seg_store<R, VEC>(y, base, n2, yy);
+    }
+}
+
+int mik_c_scal2(mik_ctx *ctx, int dtype, int64_t n, const void *a, void *x, const void *b, void *y)
+{
+    return c_typed(dtype, [&](auto r) {
+        using R = decltype(r);
+        const CPair<R> ca{((const R *)a)[0], ((const R *)a)[1]}, cb{((const R *)b)[0], ((const R *)b)[1]};
+        return launch_segments<R>(ctx, 2 * n, mik_aligned16(x) && mik_aligned16(y), 0, [&](auto v, int grid, int64_t ns) {
+            hipLaunchKernelGGL((k_cscal2<R, decltype(v)::value>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, 2 * n, ns, (R *)x, (R *)y, ca, cb);
+        });
+    });
+}
+
+// p = v; p += neg_h1 p_curr (if p_curr); p += neg_h0 p_prev (if p_prev); p *= inv; x += g p; p_out = p
+template <typename R, bool VEC>
+__global__ __launch_bounds__(MIK_BLOCK) void k_cqmr_update(int64_t n2, int64_t nseg, const R *v, const R *p_curr, const R *p_prev, R *p_out, R *x, CPair<R> neg_h1,
+                                                           CPair<R> neg_h0, CPair<R> inv, CPair<R> g)
+{
+    constexpr int64_t SEG = (int64_t)MIK_BLOCK * SEG_REGS<R>;
+    for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const int64_t base = s * SEG + (int64_t)VT<R>::W * threadIdx.x;
+        R p[SEG_REGS<R>], xx[SEG_REGS<R>], t[SEG_REGS<R>];
+        seg_load<R, VEC>(v, base, n2, 0, p);
+        seg_load<R, VEC>(x, base, n2, 0, xx);
+        if (p_curr) {
+            seg_load<R, VEC>(p_curr, base, n2, 0, t);
+            cseg_madd<R>(neg_h1.re, neg_h1.im, t, p);
+        }
+        if (p_prev) {
+            seg_load<R, VEC>(p_prev, base, n2, 0, t);
+            cseg_madd<R>(neg_h0.re, neg_h0.im, t, p);
+        }
+        cseg_scale<R>(p, inv.re, inv.im);
+        cseg_madd<R>(g.re, g.im, p, xx);
+        seg_store<R, VEC>(p_out, base, n2, p);
+        seg_store<R, VEC>(x, base, n2, xx);
+    }
+}
+
+int mik_c_qmr_update(mik_ctx *ctx, int dtype, int64_t n, const void *v, const void *neg_h1, const void *p_curr, const void *neg_h0, const void *p_prev,
+                     const void *inv, const void *g, void *x, void *p_out)
+{
+    return c_typed(dtype, [&](auto r) {
+        using R = decltype(r);
+        auto pair = [](const void *p) { return p ? CPair<R>{((const R *)p)[0], ((const R *)p)[1]} : CPair<R>{R(0), R(0)}; };
+        const CPair<R> h1 = pair(p_curr ? neg_h1 : nullptr), h0 = pair(p_prev ? neg_h0 : nullptr), ci = pair(inv), cg = pair(g);
+        const bool vec = mik_aligned16(v) && mik_aligned16(x) && mik_aligned16(p_out) && (!p_curr || mik_aligned16(p_curr)) && (!p_prev || mik_aligned16(p_prev));
+        return launch_segments<R>(ctx, 2 * n, vec, 0, [&](auto vv, int grid, int64_t ns) {
+            hipLaunchKernelGGL((k_cqmr_update<R, decltype(vv)::value>), dim3(grid), dim3(MIK_BLOCK), 0, ctx->stream, 2 * n, ns, (const R *)v, (const R *)p_curr,
+                               (const R *)p_prev, (R *)p_out, (R *)x, h1, h0, ci, cg);
+        });
+    });
+}
+
 // ---- host: complex LU with partial pivoting -- lu!(view(M, L, L)); ldiv!(gamma, F, view(M, L, 1)), src/bicgstabl.jl:123-125 ------------
 // LAPACK getrf's pivot rule (izamax: the first maximum of |re| + |im|); divisions by Smith's scaling (hc_div)
 template <typename R> static int c_lu_solve(HC<R> *A, int64_t lda, int n, HC<R> *b)

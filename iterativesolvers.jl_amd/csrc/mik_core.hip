@@ -2119,6 +2119,12 @@ template <typename T> static int axpy2_dot_impl(mik_ctx *ctx, int64_t n, const v
 extern "C" int mik_axpy2_dot(mik_ctx *ctx, int dtype, int64_t n, const void *a, const void *x1, const void *b, const void *x2, void *y, const void *z, void *out)
 {
     if (!ctx || n < 0 || !a || (x2 && !b) || (z && !out) || (n && (!x1 || !y))) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype & ~MIK_SCALAR_REAL)) {      // real scalars and no reduction: the real sweep over 2 n; else k_caxpy2_dot
+        const int cd = dtype & ~MIK_SCALAR_REAL;
+        const bool real_scalars = (dtype & MIK_SCALAR_REAL) != 0;
+        if (real_scalars && !z) return mik_axpy2_dot(ctx, mik_real_dtype(cd), 2 * n, a, x1, b, x2, y, nullptr, out);
+        return mik_c_axpy2_dot(ctx, cd, n, real_scalars, a, x1, b, x2, y, z, out);
+    }
     if (dtype == MIK_F64) return axpy2_dot_impl<double>(ctx, n, a, x1, b, x2, y, z, out);
     if (dtype == MIK_F32) return axpy2_dot_impl<float>(ctx, n, a, x1, b, x2, y, z, out);
     return MIK_ERR_INVALID;
@@ -2127,6 +2133,8 @@ extern "C" int mik_axpy2_dot(mik_ctx *ctx, int dtype, int64_t n, const void *a, 
 extern "C" int mik_scal2(mik_ctx *ctx, int dtype, int64_t n, const void *a, void *x, const void *b, void *y)
 {
     if (!ctx || n < 0 || !a || !b || (n && (!x || !y))) return MIK_ERR_INVALID;
+    if (mik_is_complex(dtype & ~MIK_SCALAR_REAL))
+        return (dtype & MIK_SCALAR_REAL) ? mik_scal2(ctx, mik_real_dtype(dtype & ~MIK_SCALAR_REAL), 2 * n, a, x, b, y) : mik_c_scal2(ctx, dtype, n, a, x, b, y);
     const bool vec = mik_aligned16(x) && mik_aligned16(y);
     if (dtype == MIK_F64) { OpScal2<double> op{(double *)x, (double *)y, *(const double *)a, *(const double *)b}; return launch_map<double>(ctx, n, op, vec, (double *)nullptr, nullptr); }
     if (dtype == MIK_F32) { OpScal2<float> op{(float *)x, (float *)y, *(const float *)a, *(const float *)b}; return launch_map<float>(ctx, n, op, vec, (float *)nullptr, nullptr); }
@@ -2138,6 +2146,10 @@ extern "C" int mik_qmr_update(mik_ctx *ctx, int dtype, int64_t n, const void *v,
 {
     if (!ctx || n < 0 || !inv || !g || (p_curr && !neg_h1) || (p_prev && !neg_h0) || (n && (!v || !x || !p_out))) return MIK_ERR_INVALID;
     if (p_out == v || p_out == p_curr) return MIK_ERR_INVALID;      // p_out may only be p_prev's storage (element i is read before it is written) or a vector of its own
+    if (mik_is_complex(dtype & ~MIK_SCALAR_REAL)) {      // four real scalars: the real sweep over 2 n; four complex ones: k_cqmr_update
+        if (dtype & MIK_SCALAR_REAL) return mik_qmr_update(ctx, mik_real_dtype(dtype & ~MIK_SCALAR_REAL), 2 * n, v, neg_h1, p_curr, neg_h0, p_prev, inv, g, x, p_out);
+        return mik_c_qmr_update(ctx, dtype, n, v, neg_h1, p_curr, neg_h0, p_prev, inv, g, x, p_out);
+    }
     const bool vec = mik_aligned16(v) && mik_aligned16(x) && mik_aligned16(p_out) && (!p_curr || mik_aligned16(p_curr)) && (!p_prev || mik_aligned16(p_prev));
     if (dtype == MIK_F64) {
         OpQmrUpdate<double> op{(const double *)v, (const double *)p_curr, (const double *)p_prev, (double *)p_out, (double *)x,

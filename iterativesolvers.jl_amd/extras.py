@@ -6,6 +6,9 @@ unadvertised.  They run on the same L1 / L2 entry points of libmik.so as the sec
 tested against their oracle restatements (``tests/test_idrs.py``, ``test_lsqr_lsmr.py``, ``test_qmr.py``, ``test_powm.py``) and are benchmarked
 only by ``bench.py --extras``.  Bit parity is against the repository's own oracle; the reference's ``LowerTriangular \\`` in IDR(s)
 dispatches to BLAS ``trsv``, whose operation order may differ by ulps from the forward substitution used here and in the oracle.
+
+QMR, IDR(s) and the power method also take ``complex128`` / ``complex64`` operands (``tests/test_complex_extras_host.py``,
+``tests/test_gpu_complex_extras.py``); LSQR and LSMR are real only, as the reference tests them.
 """
 from __future__ import annotations
 
@@ -15,17 +18,19 @@ import math
 import numpy as np
 
 from ._lib import MikError, check, lib
-from .api import (ConvergenceHistory, HipCSR, HipMatrix, HipVector, Identity, JacobiPrec, _default_reltol, _scalar, _vp, dot,     # noqa: F401
-                  givens_algorithm, mul_, norm, zerox)
+from .api import (ConvergenceHistory, HipCSR, HipMatrix, HipVector, Identity, JacobiPrec, _default_reltol, _is_complex, _real_dtype, _refuse_complex_jacobi,    # noqa: F401
+                  _scalar, _vp, dot, gemv_t_, givens_algorithm, mul_, norm, zerox)
 
 
 def with_adjoint(n_rows, n_cols, colptr, rowval, nzval, *, index_base=1, ctx=None) -> HipCSR:
-    """The operator of a ``SparseMatrixCSC`` together with its adjoint (``adjoint(A)`` below; real element types): the SAME three arrays read
-    as a CSR matrix are A' (n_cols x n_rows) -- row j of A' is column j of A, entries in storage order, which is the order
-    ``mul!(y, adjoint(A), x)`` of SparseArrays sums them in.  Two device operators (a second copy of the arrays in HBM); no transpose is
-    ever formed for the adjoint."""
+    """The operator of a ``SparseMatrixCSC`` together with its adjoint (``adjoint(A)`` below): the SAME three arrays read as a CSR matrix
+    are transpose(A) (n_cols x n_rows) -- row j is column j of A, entries in storage order, which is the order
+    ``mul!(y, adjoint(A), x)`` of SparseArrays sums them in.  For a real element type that is A'; for a complex one the second operator is
+    uploaded with ``conj(nzval)`` (negation is exact, so every product ``conj(a) * x[row]`` has the reference's bits).  Two device
+    operators (a second copy of the arrays in HBM); no transpose is ever formed for the adjoint."""
     A = HipCSR(n_rows, n_cols, colptr, rowval, nzval, index_base=index_base, is_csc=True, ctx=ctx)
-    A.adj = HipCSR(n_cols, n_rows, colptr, rowval, nzval, index_base=index_base, is_csc=False, ctx=A.ctx)
+    adj_val = np.conj(np.ascontiguousarray(nzval)) if _is_complex(A.dtype) else nzval
+    A.adj = HipCSR(n_cols, n_rows, colptr, rowval, adj_val, index_base=index_base, is_csc=False, ctx=A.ctx)
     A.adj.adj = A
     return A
 
@@ -37,27 +42,33 @@ def with_adjoint_from_scipy(m, ctx=None) -> HipCSR:
 
 
 class IDRSIterable:
-    """``IDRSIterable`` -- src/idrs.jl:84-113, construction per ``idrs_iterable!`` (:116-147); real element types.  ``P`` replaces the
+    """``IDRSIterable`` -- src/idrs.jl:84-113, construction per ``idrs_iterable!`` (:116-147); real and complex element types.  ``P`` replaces the
     reference's ``rand!`` shadow vectors (:136) when reproducibility is wanted: a ``HipMatrix`` or an n x s array; default: uniform [0, 1)
-    numbers like ``rand!``.  The iteration state is the pair ``(iter, step)`` of the reference (:164)."""
+    numbers like ``rand!`` (complex: in both components).  The iteration state is the pair ``(iter, step)`` of the reference (:164).
+    Complex operands: ``tol`` and ``normR`` are real, ``M``, ``f`` and ``omega`` complex, ``dot(P[i], .)`` conjugates
+    ``P``; the ``mik_idrs_*`` handle is real only and is never created (``_step is None``) -- ``fused`` then composes the step from the complex
+    entries whose bits equal the L1 chain's (``mik_axpy2_dot`` in the bi-orthogonalisation, ``mik_gemv_t`` for the column of ``M``)."""
 
     def __init__(self, log, X, A, C_, s, Pl, abstol, reltol, maxiter, *, smoothing=False, verbose=False, P=None, fused=True):
-        T = X.dtype.type
+        T, RT = X.dtype.type, _real_dtype(X.dtype).type                    # RT = real(T): T itself for the real types
+        cplx = _is_complex(X.dtype)
         self.log, self.X, self.A, self.s, self.smoothing, self.verbose = log, X, A, int(s), bool(smoothing), bool(verbose)
         self.Pl = Identity() if Pl is None else Pl
+        _refuse_complex_jacobi(X.dtype, self.Pl)
         self.abstol, self.reltol, self.maxiter = abstol, reltol, maxiter
         n = X.n
         self.R = X.similar()
         mul_(self.R, A, X)                                                   # R = C - A*X  :119
-        self.R.xpby_(C_, T(-1))
+        self.R.xpby_(C_, RT(-1))
         self.normR = norm(self.R)                                            # :120
-        self.tol = max(T(reltol) * self.normR, T(abstol))                    # :121
+        self.tol = max(RT(reltol) * self.normR, RT(abstol))                  # :121
         if self.smoothing:                                                   # :123-126
             self.X_s, self.R_s, self.T_s = X.similar().copyto_(X), X.similar().copyto_(self.R), X.zero()
         else:
             self.X_s = self.R_s = self.T_s = None
         if P is None:
-            P = np.random.default_rng().random((n, self.s)).astype(X.dtype)  # :136
+            rng = np.random.default_rng()                                    # :136
+            P = (rng.random((n, self.s)) + 1j * rng.random((n, self.s)) if cplx else rng.random((n, self.s))).astype(X.dtype)
         if isinstance(P, HipMatrix):
             if P.n != n or P.cols < self.s or P.dtype != X.dtype or P.ctx is not X.ctx:
                 raise MikError(3, "IDRSIterable", "P must be an n x s block (n = %d, s = %d) of X's element type on X's context" % (n, self.s))
@@ -75,7 +86,8 @@ class IDRSIterable:
         self.omega = T(1)                                                    # :146
         # fused, a HipCSR operator, Identity / diagonal Pl, s <= 32: one C call per step (mik_idrs_step); M, f and omega then live in the handle
         self._step = None
-        if fused and isinstance(A, HipCSR) and isinstance(self.Pl, (Identity, JacobiPrec)) and self.s <= 32:
+        self._compose = bool(fused) and cplx and isinstance(X, HipVector)    # complex: no handle; single entries where their bits are the chain's
+        if fused and not cplx and isinstance(A, HipCSR) and isinstance(self.Pl, (Identity, JacobiPrec)) and self.s <= 32:
             h = _vp()
             d = self.Pl.diagonal.ptr if isinstance(self.Pl, JacobiPrec) else None
             check(lib().mik_idrs_create(X.ctx.handle, A.handle, self.s, _vp(X.ptr), _vp(self.R.ptr), _vp(self.P.col(0).ptr), self.P.ld,
@@ -107,7 +119,7 @@ class IDRSIterable:
     def iterate(self, state=None):
         """``iterate(it, (iter, step))`` -- src/idrs.jl:164-272."""
         it, step = (1, 1) if state is None else state
-        T = self.X.dtype.type
+        T, RT = self.X.dtype.type, _real_dtype(self.X.dtype).type
         s, P, U, G, M, f = self.s, self.P, self.U, self.G, self.M, self.f
         if self.normR < self.tol or it > self.maxiter:                       # :168
             if self.log is not None:
@@ -135,16 +147,29 @@ class IDRSIterable:
             for i in range(k + 1, s):                                        # :191-194
                 self.V.axpy_(c[i - k], G.col(i))
                 self.Q.axpy_(c[i - k], U.col(i))
-            self.V.xpby_(self.R, T(-1))                                      # V .= R .- V  :197
+            self.V.xpby_(self.R, RT(-1))                                     # V .= R .- V  :197
             self._ldiv(self.V)                                               # :200
             U.col(k).copyto_(self.Q).axpy_(self.omega, self.V)               # :202
             mul_(G.col(k), self.A, U.col(k))                                 # :203
-            for i in range(k):                                               # :207-211
-                alpha = dot(P.col(i), G.col(k)) / M[i, i]
-                G.col(k).axpy_(-alpha, G.col(i))
-                U.col(k).axpy_(-alpha, U.col(i))
-            for i in range(k, s):
-                M[i, k] = dot(P.col(i), G.col(k))                            # :215-217
+            if self._compose:                                                # the dot of pass i + 1 rides on the update of pass i; then one sweep for M[k+1:s, k]
+                d = dot(P.col(0), G.col(k)) if k else None
+                for i in range(k):                                           # :207-211
+                    alpha = d / M[i, i]
+                    d = _axpy2_dot(G.col(k), -alpha, G.col(i), None, None, P.col(i + 1))
+                    U.col(k).axpy_(-alpha, U.col(i))
+                first = k
+                if k:
+                    M[k, k] = d
+                    first = k + 1
+                if first < s:
+                    M[first:, k] = gemv_t_(P, s - first, G.col(k), col0=first)  # :215-217
+            else:
+                for i in range(k):                                           # :207-211
+                    alpha = dot(P.col(i), G.col(k)) / M[i, i]
+                    G.col(k).axpy_(-alpha, G.col(i))
+                    U.col(k).axpy_(-alpha, U.col(i))
+                for i in range(k, s):
+                    M[i, k] = dot(P.col(i), G.col(k))                        # :215-217
             beta = f[k] / M[k, k]                                            # :221
             self.R.axpy_(-beta, G.col(k))                                    # :222
             self.X.axpy_(beta, U.col(k))                                     # :223
@@ -578,7 +603,8 @@ def lsmr(A, b, **kwargs):
 # qmr.jl
 # ==============================================================================================
 class LanczosDecomp:
-    """``LanczosDecomp`` -- src/qmr.jl:5-58: the two-sided Lanczos process on A and adjoint(A); real element types."""
+    """``LanczosDecomp`` -- src/qmr.jl:5-58: the two-sided Lanczos process on A and adjoint(A); real and complex element types (complex:
+    ``alpha``, ``beta`` and ``delta`` are of the element type as the reference's fields are, ``resnorm`` is real; conjugate() is the identity on reals)."""
 
     def __init__(self, x, A, b, *, initially_zero=False, fused=True):
         T = x.dtype.type
@@ -590,7 +616,7 @@ class LanczosDecomp:
             self.v_curr.axpy_(T(-1), self.v_next)                            # :34
         self.resnorm = norm(self.v_curr)                                     # :36
         with np.errstate(divide="ignore"):
-            self.v_curr.scal_(T(1) / self.resnorm)                           # :37
+            self.v_curr.scal_(type(self.resnorm)(1) / self.resnorm)          # :37 (inv of a real: real x complex on a complex vector)
         self.w_prev, self.w_curr, self.w_next = x.zero(), x.similar().copyto_(self.v_curr), x.similar()   # :39-41
         self.alpha = self.beta_prev = self.beta_curr = self.delta = T(0)     # :43-46
 
@@ -600,27 +626,25 @@ class LanczosDecomp:
         mul_(self.v_next, self.A, self.v_curr)                               # :67
         self.alpha = dot(self.v_next, self.w_curr)                           # :69
         if self.fused:
-            _axpy2_dot(self.v_next, -self.alpha, self.v_curr, -self.beta_curr, self.v_prev if iteration > 1 else None, None)      # :70-72
+            _axpy2_dot(self.v_next, -self.alpha.conjugate(), self.v_curr, -self.beta_curr.conjugate(), self.v_prev if iteration > 1 else None, None)   # :70-72
             mul_(self.w_next, self.At, self.w_curr)                          # :75
             vw = _axpy2_dot(self.w_next, -self.alpha, self.w_curr, -self.delta, self.w_prev if iteration > 1 else None, self.v_next)   # :76-81
         else:
-            self.v_next.axpy_(-self.alpha, self.v_curr)                      # :70
+            self.v_next.axpy_(-self.alpha.conjugate(), self.v_curr)          # :70
             if iteration > 1:
-                self.v_next.axpy_(-self.beta_curr, self.v_prev)              # :72
+                self.v_next.axpy_(-self.beta_curr.conjugate(), self.v_prev)  # :72
             mul_(self.w_next, self.At, self.w_curr)                          # :75
             self.w_next.axpy_(-self.alpha, self.w_curr)                      # :76
             if iteration > 1:
                 self.w_next.axpy_(-self.delta, self.w_prev)                  # :78
             vw = dot(self.v_next, self.w_next)                               # :81
-        self.delta = np.sqrt(abs(vw))                                        # :82
+        self.delta = T(np.sqrt(abs(vw)))                                     # :82 (the field is of the element type)
         if self.delta == 0:
             return None                                                      # :83-85
         self.beta_prev = self.beta_curr                                      # :87-88
         self.beta_curr = vw / self.delta
         if self.fused:
-            sa, sb = _scalar(self.v_next.dtype, T(1) / self.delta), _scalar(self.v_next.dtype, T(1) / self.beta_curr)
-            check(lib().mik_scal2(self.v_next.ctx.handle, self.v_next.code, self.v_next.n, sa[1], _vp(self.v_next.ptr), sb[1], _vp(self.w_next.ptr)),
-                  "mik_scal2", self.v_next.ctx.handle)                       # :90-91
+            _scal2(T(1) / self.delta, self.v_next, T(1) / self.beta_curr, self.w_next)    # :90-91
         else:
             self.v_next.scal_(T(1) / self.delta)                             # :90
             self.w_next.scal_(T(1) / self.beta_curr)                         # :91
@@ -630,12 +654,28 @@ class LanczosDecomp:
 
 
 def _axpy2_dot(y, a, x1, b, x2, z):
-    """``y .+= a .* x1; y .+= b .* x2`` (x2 may be None) and ``dot(y, z)`` (z may be None) in one sweep (``mik_axpy2_dot``)."""
+    """``y .+= a .* x1; y .+= b .* x2`` (x2 may be None) and ``dot(z, y)`` (z may be None) in one sweep (``mik_axpy2_dot``); the scalars are
+    passed in the element type."""
     out = np.zeros(1, y.dtype)
-    sa, sb = _scalar(y.dtype, a), _scalar(y.dtype, b)
+    sa, sb = _scalar(y.dtype, a), _scalar(y.dtype, 0 if b is None else b)
     check(lib().mik_axpy2_dot(y.ctx.handle, y.code, y.n, sa[1], _vp(x1.ptr), sb[1], _vp(x2.ptr if x2 is not None else None), _vp(y.ptr),
                               _vp(z.ptr if z is not None else None), out.ctypes.data_as(_vp)), "mik_axpy2_dot", y.ctx.handle)
     return out[0]
+
+
+def _scal2(a, x, b, y):
+    """``x .*= a; y .*= b`` in one sweep (``mik_scal2``), both scalars in the element type."""
+    sa, sb = _scalar(x.dtype, a), _scalar(x.dtype, b)
+    check(lib().mik_scal2(x.ctx.handle, x.code, x.n, sa[1], _vp(x.ptr), sb[1], _vp(y.ptr)), "mik_scal2", x.ctx.handle)
+
+
+def _qmr_update(v, neg_h1, p_curr, neg_h0, p_prev, inv, g, x, p_out):
+    """``p = v + neg_h1 p_curr + neg_h0 p_prev`` (either vector may be None), ``p .*= inv``, ``x .+= g .* p``, ``p_out = p`` in one sweep
+    (``mik_qmr_update``); the four scalars in the element type."""
+    sc = [_scalar(x.dtype, val) for val in (neg_h1, neg_h0, inv, g)]
+    check(lib().mik_qmr_update(x.ctx.handle, x.code, x.n, _vp(v.ptr), sc[0][1], _vp(p_curr.ptr if p_curr is not None else None), sc[1][1],
+                               _vp(p_prev.ptr if p_prev is not None else None), sc[2][1], sc[3][1], _vp(x.ptr), _vp(p_out.ptr)),
+          "mik_qmr_update", x.ctx.handle)
 
 
 class QMRIterable:
@@ -652,7 +692,8 @@ class QMRIterable:
         self.H = np.zeros(4, x.dtype)
         self.c_prev, self.s_prev, self.c_curr, self.s_curr = T(1), T(0), T(1), T(0)       # :137-138
         self.p_prev, self.p_curr = x.zero(), x.zero()                        # :140-141
-        self.tol = max(T(reltol) * self.lanczos.resnorm, T(abstol))          # :143
+        RT = _real_dtype(x.dtype).type                                       # real(T): the tolerance and resnorm are real
+        self.tol = max(RT(reltol) * self.lanczos.resnorm, RT(abstol))        # :143
         self.maxiter = int(maxiter)
 
     def converged(self):
@@ -671,25 +712,23 @@ class QMRIterable:
             return None
         T, H, g, lz = self.x.dtype.type, self.H, self.g, self.lanczos
         lz.iterate(iteration)                                                # :165
-        H[1] = lz.beta_prev                                                  # :167-169
-        H[2] = lz.alpha
+        H[1] = lz.beta_prev.conjugate()                                      # :167-169
+        H[2] = lz.alpha.conjugate()
         H[3] = lz.delta
         if iteration > 2:                                                    # :171-174
             H[0] = self.s_prev * H[1]
             H[1] = self.c_prev * H[1]
         if iteration > 1:                                                    # :176-180
-            tmp = -self.s_curr * H[1] + self.c_curr * H[2]
+            tmp = -self.s_curr.conjugate() * H[1] + self.c_curr * H[2]
             H[1] = self.c_curr * H[1] + self.s_curr * H[2]
             H[2] = tmp
         c, s, H[2] = givens_algorithm(H[2], H[3], self.x.dtype)              # :183
-        g[1] = -s * g[0]                                                     # :185-186
+        g[1] = -s.conjugate() * g[0]                                         # :185-186
         g[0] = c * g[0]
         if self.fused:                                                       # :188-197 in one sweep; the names rotate instead of the two copies
             with np.errstate(divide="ignore"):
-                sc = [_scalar(self.x.dtype, val) for val in (-H[1], -H[0], T(1) / H[2], g[0])]
-            check(lib().mik_qmr_update(self.x.ctx.handle, self.x.code, self.x.n, _vp(lz.v_prev.ptr), sc[0][1], _vp(self.p_curr.ptr if iteration > 1 else None),
-                                       sc[1][1], _vp(self.p_prev.ptr if iteration > 2 else None), sc[2][1], sc[3][1], _vp(self.x.ptr), _vp(self.p_prev.ptr)),
-                  "mik_qmr_update", self.x.ctx.handle)
+                inv = T(1) / H[2]
+            _qmr_update(lz.v_prev, -H[1], self.p_curr if iteration > 1 else None, -H[0], self.p_prev if iteration > 2 else None, inv, g[0], self.x, self.p_prev)
             self.p_prev, self.p_curr = self.p_curr, self.p_prev
         else:
             lz.v_next.copyto_(lz.v_prev)                                     # we need v_m, not v_m+1  :188
@@ -702,6 +741,8 @@ class QMRIterable:
             self.x.axpy_(g[0], lz.v_next)                                    # :193
             self.p_prev.copyto_(self.p_curr)                                 # :196-197
             self.p_curr.copyto_(lz.v_next)
+        if _is_complex(self.x.dtype):
+            c = T(c)                                                         # c is real, the field of the element type
         self.c_prev, self.s_prev, self.c_curr, self.s_curr = self.c_curr, self.s_curr, c, s           # :195
         g[0] = g[1]                                                          # :198
         self.resnorm = abs(g[1])                                             # :200
@@ -752,14 +793,15 @@ def qmr(A, b, **kwargs):
 # simple.jl: power method
 # ==============================================================================================
 class PowerMethodIterable:
-    """``PowerMethodIterable`` -- src/simple.jl:5-14, construction per ``powm_iterable!`` (:36-39); real element types."""
+    """``PowerMethodIterable`` -- src/simple.jl:5-14, construction per ``powm_iterable!`` (:36-39); real and complex element types (complex:
+    ``theta = dot(x, Ax)`` is complex, ``tol`` and ``residual`` are real)."""
 
     def __init__(self, A, x, *, tol, maxiter):
-        T = x.dtype.type
-        self.A, self.x, self.tol, self.maxiter = A, x, T(tol), int(maxiter)
+        T, RT = x.dtype.type, _real_dtype(x.dtype).type
+        self.A, self.x, self.tol, self.maxiter = A, x, RT(tol), int(maxiter)
         self.theta = T(0)
         self.r, self.Ax = x.similar(), x.similar()
-        self.residual = np.finfo(x.dtype).max                                # floatmax  :38
+        self.residual = np.finfo(_real_dtype(x.dtype)).max                   # floatmax(real(T))  :38
 
     def converged(self):
         return self.residual <= self.tol                                     # :15
@@ -783,7 +825,8 @@ class PowerMethodIterable:
         self.residual = norm(self.r)                                         # :28
         self.x.copyto_(self.Ax)                                              # :31
         with np.errstate(divide="ignore"):
-            self.x.scal_(T(1) / norm(self.x))                                # :32
+            nx = norm(self.x)
+            self.x.scal_(type(nx)(1) / nx)                                   # :32 (inv of a real)
         return self.residual, iteration + 1
 
     def __iter__(self):
@@ -795,7 +838,7 @@ class PowerMethodIterable:
 
 def powm_iterable_(A, x, *, tol=None, maxiter=None):
     """``powm_iterable!(A, x; tol, maxiter)`` -- src/simple.jl:36-39."""
-    tol = np.finfo(x.dtype).eps * A.size(2) ** 3 if tol is None else tol
+    tol = np.finfo(_real_dtype(x.dtype)).eps * A.size(2) ** 3 if tol is None else tol       # eps(real(T)) n^3
     return PowerMethodIterable(A, x, tol=tol, maxiter=A.size(1) if maxiter is None else maxiter)
 
 
@@ -803,7 +846,7 @@ def powm_(B, x, *, tol=None, maxiter=None, shift=0, inverse=False, log=False, ve
     """``powm!(B, x; tol, maxiter, shift, inverse, log, verbose)`` -- src/simple.jl:113-142: (λ, x[, history]).  With ``log`` the history also
     carries the residual norm of every iterate (the reference reserves ``:resnorm`` but never pushes to it)."""
     T = x.dtype.type
-    tol = np.finfo(x.dtype).eps * B.size(2) ** 3 if tol is None else tol     # :114
+    tol = np.finfo(_real_dtype(x.dtype)).eps * B.size(2) ** 3 if tol is None else tol     # :114
     maxiter = B.size(1) if maxiter is None else maxiter
     history = ConvergenceHistory(partial=not log)
     history["tol"] = tol
