@@ -763,6 +763,40 @@ int mik_dense_sor_step(mik_dense_stationary *S, void *x, void *tmp, const void *
 /* One iteration of DenseSSORIterable -- :227-263.  tmp keeps the accumulators of the backward half. */
 int mik_dense_ssor_step(mik_dense_stationary *S, void *x, void *tmp, const void *b, const void *omega, int scalar_dtype);
 
+/* ---- dense LU: lu!(A) with partial pivoting and ldiv!(y, F, x) on a square device matrix ------------------------------------------
+ * What the reference's tests pass as Pl / Pr (test/gmres.jl:28-35, test/cg.jl:44-47, test/bicgstabl.jl:40-42, test/idrs.jl:55) and as the
+ * operator of invpowm (test/simple_eigensolvers.jl:40).  Added without a version bump, additive; real MIK_F64 / MIK_F32 (MIK_C64 / MIK_C32:
+ * MIK_ERR_NOTIMPL with a message that names the element type).
+ * THE BIT CONTRACT: the factors, the pivots and the solution are those of the unblocked loops of mik_lu_solve.
+ *   - the pivot of column j is the FIRST row i >= j with the largest |A[i,j]| (strict >, LAPACK's idamax);
+ *   - the multiplier is A[i,j] / pivot, a division;
+ *   - every element (i,c) receives a = a - m * u for k = 0, 1, ..., min(i,c) - 1 in ascending k, the product and the difference rounded
+ *     on their own (no fma, no matrix cores);
+ *   - ldiv! applies the row interchanges to x, then runs the unit-lower chain of every row in ascending column order, then the upper chain
+ *     of every row in DESCENDING column order with the division by U[i,i] last.
+ * The device plan is blocked (panels of W columns, a tiled trailing update); blocking keeps k ascending per element and so keeps the bits.
+ * Every dependency between workgroups is a kernel boundary on the ctx stream; nothing is allocated per solve. */
+typedef struct mik_dense_lu mik_dense_lu;
+/* lu!(A): A (column-major n x n, leading dimension ld, device) is overwritten by L\U and must outlive the handle.  MIK_ERR_SINGULAR and
+ * *singular_col = k (1-based) for the first exactly zero pivot column (-0.0 included) -- SingularException(k); no handle is returned then.
+ * MIK_ERR_MISMATCH for ld < n or n < 1; MIK_ERR_NOTIMPL for n >= 2^31 - 64.  Synchronises once, at the end. */
+int mik_dense_lu_create(mik_ctx *ctx, void *A, int64_t n, int64_t ld, int dtype, int64_t *singular_col, mik_dense_lu **out);
+int mik_dense_lu_destroy(mik_dense_lu *F);
+/* host, n entries, 1-based: LAPACK's ipiv / F.ipiv (row j was interchanged with row ipiv[j]).  No device access. */
+int mik_dense_lu_ipiv(const mik_dense_lu *F, int64_t *ipiv);
+/* ldiv!(y, F, x) on DEVICE n-vectors, asynchronous on the ctx stream.  y may equal x (ldiv!(F, x)); a partial overlap, or a vector that
+ * overlaps the factors, is MIK_ERR_INVALID. */
+int mik_dense_lu_solve(mik_dense_lu *F, void *y, const void *x);
+/* The same as a mik_ldiv_fn (user = the handle): a host fills mik_precond{NULL, mik_dense_lu_ldiv_fn, handle} and the fused iterables
+ * apply Pl / Pr with no host frame of the caller's. */
+int mik_dense_lu_ldiv_fn(void *user, void *y, const void *x);
+/* Every size at which the code switches.  panel_w: W; search_rows: rows per workgroup of the pivot search and of the panel update;
+ * tile_rows / tile_cols: the tile of the trailing update; one_launch_rows: the row limit of a one-launch panel (0: not built);
+ * launches_factor: kernel launches the factorisation made; launches_solve: launches of one solve (1 + 2 ceil(n / W)); bytes: device memory
+ * held besides A.  Any pointer may be NULL. */
+int mik_dense_lu_info(const mik_dense_lu *F, int64_t *panel_w, int64_t *search_rows, int64_t *tile_rows, int64_t *tile_cols,
+                      int64_t *one_launch_rows, int64_t *launches_factor, int64_t *launches_solve, int64_t *bytes);
+
 /* ---- svdl: Golub-Kahan-Lanczos bidiagonalisation with thick restart (src/svdl.jl) ------------------------------------------
  * The Lanczos loop of extend! (:542-609) runs on mik_spmv (A and its adjoint as two operators), mik_gemv_t / mik_gemv_n and the fused
  * sweeps above; the k x k SVD of a restart stays on the host.  Two things no entry above does in one pass (added without a version bump,

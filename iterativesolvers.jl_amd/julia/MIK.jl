@@ -419,6 +419,10 @@ end
 function precond_struct(P, ::Type{T}, n::Int, ctx::Context, keep::Vector{Any}) where {T}
     P isa Identity && return nothing
     P isa HipJacobi && return MikPrecond(P.diagonal.ptr, C_NULL, C_NULL)
+    if P isa HipLU                                               # the library's own callback: no Julia frame per ldiv!
+        push!(keep, P)
+        return lu_precond_struct(P, T, n)
+    end
     box = CallbackBox{T}(P, n, ctx); push!(keep, box)
     MikPrecond(C_NULL, @cfunction(ldiv_trampoline, Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid})), pointer_from_objref(box))
 end
@@ -1340,6 +1344,59 @@ end
 function dense_operator_struct(A::HipDenseAdjoint, ::Type{T}, n::Int) where {T}
     dense_square(A, T, n)
     MikOperator(dtype_code(T), n, C_NULL, cglobal((:mik_dense_mul_adj_fn, libmik)), dense_operator(A.parent).handle)
+end
+
+# ---- dense LU: lu(A) / lu!(A) with partial pivoting and ldiv!(y, F, x) on a dense device matrix (csrc/mik_dense_lu.hip) ------------------
+# What the reference's tests pass as Pl / Pr (test/gmres.jl:28-35, test/cg.jl:44-47, test/bicgstabl.jl:40-42) and wrap as the operator of
+# invpowm (test/simple_eigensolvers.jl:40).  Factors, pivots and solution have the bits of the unblocked loops of mik_lu_solve (include/mik.h).
+mutable struct HipLU{T}
+    handle::Ptr{Cvoid}
+    factors::HipDenseMatrix{T}       # L\U, read at every solve; kept alive with the handle
+    ipiv::Vector{Int64}              # 1-based, LAPACK's
+    ctx::Context
+end
+function LinearAlgebra.lu!(A::HipDenseMatrix{T}) where {T}
+    size(A, 1) == size(A, 2) || throw(DimensionMismatch("the matrix is $(size(A, 1)) x $(size(A, 2)), not square"))
+    h = Ref{Ptr{Cvoid}}(C_NULL); col = Ref{Int64}(0)
+    code = ccall((:mik_dense_lu_create, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Ref{Int64}, Ref{Ptr{Cvoid}}),
+                 A.ctx.handle, A.ptr, A.n, A.ld, dtype_code(T), col, h)
+    code == 8 && throw(LinearAlgebra.SingularException(Int(col[])))
+    check(code, "mik_dense_lu_create", A.ctx.handle)
+    ipiv = Vector{Int64}(undef, A.n)
+    check(ccall((:mik_dense_lu_ipiv, libmik), Cint, (Ptr{Cvoid}, Ptr{Int64}), h[], ipiv), "mik_dense_lu_ipiv", A.ctx.handle)
+    F = HipLU{T}(h[], A, ipiv, A.ctx)
+    finalizer(o -> alive(o.ctx) && ccall((:mik_dense_lu_destroy, libmik), Cint, (Ptr{Cvoid},), o.handle), F)
+    F
+end
+function LinearAlgebra.lu(A::HipDenseMatrix{T}) where {T}        # factors a copy
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mik_malloc, libmik), Cint, (Ptr{Cvoid}, Csize_t, Ref{Ptr{Cvoid}}), A.ctx.handle, A.ld * max(A.cols, 1) * sizeof(T), p), "mik_malloc", A.ctx.handle)
+    m = HipDenseMatrix{T}(p[], A.n, A.cols, A.ld, A.ctx)
+    finalizer(x -> alive(x.ctx) && ccall((:mik_free, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), x.ctx.handle, x.ptr), m)
+    check(ccall((:mik_copy, libmik), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}), A.ctx.handle, dtype_code(T), A.ld * A.cols, A.ptr, m.ptr),
+          "mik_copy", A.ctx.handle)
+    LinearAlgebra.lu!(m)
+end
+Base.size(F::HipLU) = size(F.factors)
+Base.size(F::HipLU, d::Integer) = size(F.factors, d)
+Base.eltype(::HipLU{T}) where {T} = T
+function LinearAlgebra.ldiv!(y::HipVector{T}, F::HipLU{T}, x::HipVector{T}) where {T}
+    (length(y) == F.factors.n && length(x) == F.factors.n) || throw(DimensionMismatch("ldiv!: vectors of $(length(y)) and $(length(x)), a factorisation of order $(F.factors.n)"))
+    check(ccall((:mik_dense_lu_solve, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), F.handle, y.ptr, x.ptr), "mik_dense_lu_solve", F.ctx.handle)
+    y
+end
+LinearAlgebra.ldiv!(F::HipLU{T}, x::HipVector{T}) where {T} = LinearAlgebra.ldiv!(x, F, x)
+Base.:\(F::HipLU{T}, x::HipVector{T}) where {T} = LinearAlgebra.ldiv!(similar(x), F, x)
+"panel width, rows per workgroup of the pivot search, tile of the trailing update, row limit of the one-launch panel (0: not built), launches, device bytes"
+function dense_lu_info(F::HipLU)
+    w = Ref{Int64}(0); r = Ref{Int64}(0); tr = Ref{Int64}(0); tc = Ref{Int64}(0); one = Ref{Int64}(0); lf = Ref{Int64}(0); ls = Ref{Int64}(0); b = Ref{Int64}(0)
+    check(ccall((:mik_dense_lu_info, libmik), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                F.handle, w, r, tr, tc, one, lf, ls, b), "mik_dense_lu_info", F.ctx.handle)
+    (W = w[], R = r[], tile_rows = tr[], tile_cols = tc[], one_launch_rows = one[], launches_factor = lf[], launches_solve = ls[], bytes = b[])
+end
+function lu_precond_struct(F::HipLU, ::Type{T}, n::Int) where {T}
+    (eltype(F) == T && F.factors.n == n) || throw(DimensionMismatch("the lu of a $(F.factors.n) x $(F.factors.n) $(eltype(F)) matrix as a preconditioner of $n-vectors of $T"))
+    MikPrecond(C_NULL, cglobal((:mik_dense_lu_ldiv_fn, libmik)), F.handle)
 end
 
 end # module
