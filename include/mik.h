@@ -774,6 +774,9 @@ int mik_dense_ssor_step(mik_dense_stationary *S, void *x, void *tmp, const void 
  *     on their own (no fma, no matrix cores);
  *   - ldiv! applies the row interchanges to x, then runs the unit-lower chain of every row in ascending column order, then the upper chain
  *     of every row in DESCENDING column order with the division by U[i,i] last.
+ * Non-finite data follow the same loops: a NaN in A[j,j] keeps the pivot of column j in row j and is not a zero pivot, a NaN in any row
+ * below is never the pivot and hides no other row, equal infinities are a tie like any other, and NaN / Inf in A or x propagate as those
+ * operations propagate them (where a NaN stands is part of the contract, its sign and payload are not).
  * The device plan is blocked (panels of W columns, a tiled trailing update); blocking keeps k ascending per element and so keeps the bits.
  * Every dependency between workgroups is a kernel boundary on the ctx stream; nothing is allocated per solve. */
 typedef struct mik_dense_lu mik_dense_lu;

@@ -10,7 +10,7 @@
 // Only the order within one element's (one row's) chain matters, so the blocked right-looking plan below -- panels of W columns, each
 // element's k ascending inside a panel and panel after panel -- gives the same bits as the unblocked loop.
 //
-//   k_lu_search  per-workgroup (value, row) partials of max |A[r,j]| over the rows [j, n)       (first column of a panel only)
+//   k_lu_search  per-workgroup (key, row) partials of max |A[r,j]| over the rows [j, n); lu_key  (first column of a panel only)
 //   k_lu_pick    ONE workgroup: combine the partials (larger value, else smaller row), record ipiv[j] and a zero pivot, interchange
 //                the rows j and p inside the panel
 //   k_lu_update  a lane owns a row r > j: m = A[r,j] / pivot, A[r,c] -= m * A[j,c] for the panel columns c > j, and the partials of
@@ -22,7 +22,8 @@
 //   k_lu_fwd     one panel of the forward substitution (k_ds_panel's shape without the division)
 //   k_lu_bwd     one panel of the backward substitution, its mirror image
 // Every dependency between workgroups is a kernel boundary; nothing indexes memory through a DATA value (ipiv is clamped to [j, n)
-// where it is produced), so a singular or non-finite matrix cannot fault.
+// where it is produced), so a singular or non-finite matrix cannot fault.  Non-finite data follow the loop too: the pivot search treats a
+// NaN as the loop's comparisons do (lu_key), and everything else is the same operations on the same operands in the same order.
 #pragma once
 #include "mik_internal.h"
 #include "mik_dense_stationary.h"
@@ -37,10 +38,19 @@ constexpr int MIK_LU_THREADS = 256;     // workgroup of the trailing update: 16 
 static_assert(MIK_LU_W == MIK_DS_W && MIK_DS_R == MIK_DS_W, "the substitution kernels take one panel per 64-row workgroup");
 static_assert(MIK_LU_TR == 64 && MIK_LU_TC == 64 && MIK_LU_THREADS == 256 && MIK_LU_W == 64, "the tile loaders are written for these sizes");
 
-// b replaces a: a larger value, else the same value in a smaller row.  A NaN never replaces and is never replaced, as in the loop.
+// What the row of the value a = |A[r,j]| offers to the search of column j.  The loop starts with best = |A[j,j]| and replaces it only by a
+// strictly larger value, so a NaN in the FIRST searched row is never replaced (the pivot stays in row j, and best, a NaN, is not zero),
+// while a NaN in any other row never replaces anything.  A compare-and-keep tree cannot hold a NaN for that: the lane that holds it would
+// also refuse every candidate folded into it and hide them from the lanes above.  So no NaN enters the tree.  The first row's becomes
+// +Inf -- it wins, also against a real Inf further down (same value, smaller row), and is not zero; any other becomes -1, below every
+// magnitude, like a dead lane.  The keys only choose the row and raise the zero-pivot flag; no key is ever stored into the matrix.
+template <typename T> __device__ __forceinline__ T lu_key(T a, bool first) { return a != a ? (first ? T(INFINITY) : T(-1)) : a; }
+
+// b replaces a: a larger key, else the same key in a smaller row -- the loop's "first of the largest".  Keys are never NaN (lu_key).
 template <typename T> __device__ __forceinline__ bool lu_better(T vb, int rb, T va, int ra) { return vb > va || (vb == va && rb < ra); }
 
-// (value, row) of the workgroup's best candidate, valid in thread 0.  A dead lane offers (-1, INT_MAX) and can never win against a live one.
+// (key, row) of the workgroup's best candidate, valid in thread 0.  A dead lane offers (-1, INT_MAX): it loses to every live lane, since a
+// live lane's key is >= 0 or, at -1, comes with a smaller row.
 template <typename T>
 __device__ __forceinline__ void lu_block_best(T &v, int &row, T *sval, int *srow)
 {
@@ -62,13 +72,15 @@ __global__ void __launch_bounds__(MIK_LU_R) k_lu_search(int n, int j, const T *_
     __shared__ T sval[MIK_LU_R];
     __shared__ int srow[MIK_LU_R];
     const int r = j + (int)blockIdx.x * MIK_LU_R + (int)threadIdx.x;
-    T v = r < n ? (T)fabs(A[(int64_t)j * ld + r]) : T(-1);
+    T v = r < n ? lu_key((T)fabs(A[(int64_t)j * ld + r]), r == j) : T(-1);
     int row = r < n ? r : INT_MAX;
     lu_block_best(v, row, sval, srow);
     if (threadIdx.x == 0) { pval[blockIdx.x] = v; prow[blockIdx.x] = row; }
 }
 
-// One wave.  nparts >= 1 partials of the rows [j, n); partial 0 always names a live row.
+// One wave.  nparts >= 1 partials of the rows [j, n); partial 0 always names a live row, and its key is >= 0: it holds the first searched
+// row, whose key is never -1.  No partial is a NaN (lu_key), so the combine below is the loop's rule across workgroups, and v == 0 is the
+// loop's best == 0.
 template <typename T>
 __global__ void __launch_bounds__(64) k_lu_pick(int n, int j, int k0, int k1, T *A, int64_t ld, int nparts, const T *__restrict__ pval,
                                                 const int *__restrict__ prow, int *__restrict__ ipiv, int *first_zero)
@@ -133,7 +145,7 @@ __global__ void __launch_bounds__(MIK_LU_R) k_lu_update(int n, int j, int k1, T 
             if (live) Ar[(int64_t)(j + 1 + q) * ld] = a[q];
         }
     if (cnt > 0) {                                             // the search of column j + 1 over the rows [j + 1, n): this launch's rows
-        T v = live ? (T)fabs(a[0]) : T(-1);
+        T v = live ? lu_key((T)fabs(a[0]), r == j + 1) : T(-1);
         int row = live ? r : INT_MAX;
         lu_block_best(v, row, sval, srow);
         if (t == 0) { pval[blockIdx.x] = v; prow[blockIdx.x] = row; }

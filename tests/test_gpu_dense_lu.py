@@ -1,6 +1,8 @@
 """lu(A) / lu_(A) on a dense device matrix and ldiv_ (iterativesolvers.jl_amd/dense_lu.py over the mik_dense_lu_* entries), bit for bit
-against tests/dense_ref/dense_lu_ref.c -- the contract's unblocked loops restated in C.  Every bit comparison is np.array_equal.  Every
-shape comes from mik_dense_lu_info.  The reference's own statements with lu(A) as Pl / Pr carry the reference's own bounds."""
+against tests/dense_ref/dense_lu_ref.c -- the contract's unblocked loops restated in C.  Every comparison of device values with the
+checker's is dense_lu_host.same_bits (NaN positions, and the bits everywhere else: -0.0 is not +0.0); comparisons with a fixture's
+construction are np.array_equal.  Every shape comes from mik_dense_lu_info.  Non-finite data, poisoned padding, other leading dimensions
+and ties in later columns are in test_gpu_dense_lu_edges.py.  The reference's own statements with lu(A) as Pl / Pr carry the reference's own bounds."""
 import ctypes as C
 
 import numpy as np
@@ -72,7 +74,7 @@ def test_factors_and_pivots_bit_for_bit(pkg, ctx, ref, shape, dtype):
         assert F.n == n and F.dtype == np.dtype(dtype) and F.ipiv.dtype == np.int64
         assert np.array_equal(F.ipiv, ipiv), (n, np.flatnonzero(F.ipiv != ipiv)[:4])
         got = F.factors.to_numpy()
-        assert np.array_equal(got, LU), f"factors differ, n = {n}, {np.dtype(dtype)}, first at {np.argwhere(got != LU)[:4].tolist()}"
+        assert lh.same_bits(got, LU), f"factors differ, n = {n}, {np.dtype(dtype)}, first at {lh.first_difference(got, LU)}"
         assert F.factors is not M and np.array_equal(M.to_numpy(), A)                  # lu(A) leaves A untouched
 
 
@@ -85,11 +87,11 @@ def test_ldiv_bit_for_bit(pkg, ctx, ref, shape, dtype):
         assert np.isfinite(want).all()
         x, y = pkg.HipVector.from_numpy(b), pkg.HipVector(n, dtype).fill_(0)
         assert F.ldiv_(y, x) is y
-        assert np.array_equal(y.to_numpy(), want), (n, np.flatnonzero(y.to_numpy() != want)[:4])
+        assert lh.same_bits(y.to_numpy(), want), (n, lh.first_difference(y.to_numpy(), want))
         assert np.array_equal(x.to_numpy(), b)                                         # x is untouched in the two-argument form
-        assert F.ldiv_(x) is x and np.array_equal(x.to_numpy(), want)                  # ldiv!(F, x)
+        assert F.ldiv_(x) is x and lh.same_bits(x.to_numpy(), want)                    # ldiv!(F, x)
         s = F.solve(pkg.HipVector.from_numpy(b))
-        assert s is not y and np.array_equal(s.to_numpy(), want)
+        assert s is not y and lh.same_bits(s.to_numpy(), want)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -112,7 +114,7 @@ def test_pivot_rules(pkg, ctx, ref, shape, dtype):
     A = lh.ties(n, dtype, rows)
     LU, ipiv, _ = ref.factor(A)
     F = pkg.lu(pkg.HipMatrix.from_numpy(A))
-    assert ipiv[0] == rows[0] + 1 == F.ipiv[0] and np.array_equal(F.ipiv, ipiv) and np.array_equal(F.factors.to_numpy(), LU)
+    assert ipiv[0] == rows[0] + 1 == F.ipiv[0] and np.array_equal(F.ipiv, ipiv) and lh.same_bits(F.factors.to_numpy(), LU)
     rows = (2 * R + 3, 3 * R + 6)                                 # ... also when no candidate sits in the first workgroups
     F = pkg.lu(pkg.HipMatrix.from_numpy(lh.ties(n, dtype, rows)))
     assert F.ipiv[0] == rows[0] + 1
@@ -120,7 +122,7 @@ def test_pivot_rules(pkg, ctx, ref, shape, dtype):
     A = lh.last_row(n, dtype)
     LU, ipiv, _ = ref.factor(A)
     F = pkg.lu(pkg.HipMatrix.from_numpy(A))
-    assert (ipiv == n).all() and np.array_equal(F.ipiv, ipiv) and np.array_equal(F.factors.to_numpy(), LU)
+    assert (ipiv == n).all() and np.array_equal(F.ipiv, ipiv) and lh.same_bits(F.factors.to_numpy(), LU)
     n = 2 * W + 1
     F = pkg.lu(pkg.HipMatrix.from_numpy(lh.dominant(n, dtype)))
     assert np.array_equal(F.ipiv, np.arange(1, n + 1))            # identity pivots
@@ -133,7 +135,7 @@ def test_in_place_views_and_overlap(pkg, ctx, ref, shape):
         A, LU, ipiv, _, _ = case(pkg, ref, n, dtype)
         M = pkg.HipMatrix.from_numpy(A)
         F = pkg.lu_(M)
-        assert F.factors is M and np.array_equal(M.to_numpy(), LU)                     # lu!(A): in place
+        assert F.factors is M and lh.same_bits(M.to_numpy(), LU)                       # lu!(A): in place
         b = lh.vector(n, dtype)
         want = ref.solve(LU, ipiv, b)
         big = pkg.HipVector(3 * n + 40, dtype).fill_(7)
@@ -141,13 +143,13 @@ def test_in_place_views_and_overlap(pkg, ctx, ref, shape):
         x.copy_from_host(b)
         F.ldiv_(y, x)
         h = big.to_numpy()
-        assert np.array_equal(h[3:3 + n], want) and np.array_equal(h[n + 9:2 * n + 9], b)
+        assert lh.same_bits(h[3:3 + n], want) and np.array_equal(h[n + 9:2 * n + 9], b)
         untouched = np.ones(3 * n + 40, bool)
         untouched[3:3 + n] = untouched[n + 9:2 * n + 9] = False
         assert (h[untouched] == 7).all()                                               # nothing was stored outside y
         F.ldiv_(x)                                                                     # in place at a non-zero offset
         h = big.to_numpy()
-        assert np.array_equal(h[n + 9:2 * n + 9], want) and (h[untouched] == 7).all()
+        assert lh.same_bits(h[n + 9:2 * n + 9], want) and (h[untouched] == 7).all()
         with pytest.raises(pkg.MikError) as ei:
             F.ldiv_(big.view(0, n), big.view(5, n))                                    # a partial overlap
         assert ei.value.code == 1
