@@ -764,7 +764,7 @@ int mik_dense_sor_step(mik_dense_stationary *S, void *x, void *tmp, const void *
 int mik_dense_ssor_step(mik_dense_stationary *S, void *x, void *tmp, const void *b, const void *omega, int scalar_dtype);
 
 /* ---- dense LU: lu!(A) with partial pivoting and ldiv!(y, F, x) on a square device matrix ------------------------------------------
- * What the reference's tests pass as Pl / Pr (test/gmres.jl:28-35, test/cg.jl:44-47, test/bicgstabl.jl:40-42, test/idrs.jl:55) and as the
+ * What the reference's tests pass as Pl / Pr (test/gmres.jl:28-35, test/bicgstabl.jl:40-42, test/idrs.jl:55) and as the
  * operator of invpowm (test/simple_eigensolvers.jl:40).  Added without a version bump, additive; real MIK_F64 / MIK_F32 (MIK_C64 / MIK_C32:
  * MIK_ERR_NOTIMPL with a message that names the element type).
  * THE BIT CONTRACT: the factors, the pivots and the solution are those of the unblocked loops of mik_lu_solve.
@@ -799,6 +799,44 @@ int mik_dense_lu_ldiv_fn(void *user, void *y, const void *x);
  * held besides A.  Any pointer may be NULL. */
 int mik_dense_lu_info(const mik_dense_lu *F, int64_t *panel_w, int64_t *search_rows, int64_t *tile_rows, int64_t *tile_cols,
                       int64_t *one_launch_rows, int64_t *launches_factor, int64_t *launches_solve, int64_t *bytes);
+
+/* ---- dense Cholesky: cholesky!(Hermitian(A, :L)) and ldiv!(y, F, x) on a square device matrix, real and complex ---------------------
+ * What the reference's tests pass as Pl to cg (test/cg.jl:44-47: F = cholesky(A, Val(false)); cg(A, b; Pl=F)) and to chebyshev
+ * (test/chebyshev.jl:59-66), in Float32, Float64, ComplexF32 and ComplexF64.  Added without a version bump, additive; MIK_F64 / MIK_F32 /
+ * MIK_C64 / MIK_C32.
+ * THE BIT CONTRACT (restated as unblocked C99 loops in tests/dense_ref/dense_chol_ref.c).  Complex products are four rounded products, one
+ * rounded difference and one rounded sum; every subtraction is componentwise; no fma, no matrix cores, no reciprocal.  For j = 0 ... n - 1:
+ *   - diagonal: d = re(A[j,j]); for k = 0 ... j - 1 ascending d = d - (lr lr + li li) of L[j,k] (real types: d - L[j,k] L[j,k]); that sum is
+ *     exactly the real part of L[j,k] conj(L[j,k]).  !(d > 0), which a NaN satisfies too, fails column j and the FIRST such j is reported,
+ *     1-based; otherwise L[j,j] = sqrt(d), correctly rounded, stored with imaginary part +0;
+ *   - below the diagonal, i > j: a = A[i,j]; for k = 0 ... j - 1 ascending a = a - L[i,k] conj(L[j,k]); L[i,j] = a / L[j,j], a true division
+ *     per component;
+ *   - ldiv!: forward, acc = x[i], for k < i ascending acc -= L[i,k] w[k], w[i] = acc / L[i,i]; backward, acc = w[i], for k > i DESCENDING
+ *     acc -= conj(L[k,i]) y[k], y[i] = acc / L[i,i].
+ * Only the lower triangle of A and the real parts of its diagonal are read (LAPACK's rule); the strict upper triangle is never read and
+ * never written.  After a failure at column k the contents of the columns >= k are unspecified.  Whether A is Hermitian is not checked.
+ * The device plan is blocked (panels of W columns, three launches each: the diagonal block, the rows below it, the lower tiles of the
+ * trailing update); blocking keeps k ascending per element and so keeps the bits.  Nothing indexes memory through a data value: an
+ * indefinite or non-finite matrix cannot fault.  Every dependency between workgroups is a kernel boundary on the ctx stream. */
+typedef struct mik_dense_chol mik_dense_chol;
+/* cholesky!(Hermitian(A, :L)): the lower triangle of A (column-major n x n, leading dimension ld, device) is overwritten by L; A must
+ * outlive the handle.  A column whose pivot is not positive: with check != 0, MIK_ERR_SINGULAR, *failed_col = k (1-based), the message names
+ * PosDefException(k) and no handle is returned; with check == 0, MIK_OK and a handle whose info is k (cholesky(A; check = false)).
+ * MIK_ERR_MISMATCH for ld < n or n < 1; MIK_ERR_NOTIMPL for n >= 2^31 - 64.  Synchronises once, at the end. */
+int mik_dense_chol_create(mik_ctx *ctx, void *A, int64_t n, int64_t ld, int dtype, int check, int64_t *failed_col, mik_dense_chol **out);
+int mik_dense_chol_destroy(mik_dense_chol *F);
+/* ldiv!(y, F, x) on DEVICE n-vectors, asynchronous on the ctx stream; nothing is allocated.  y may equal x (ldiv!(F, x)); a partial overlap,
+ * a vector that overlaps the factors, or a handle whose info is not 0 is MIK_ERR_INVALID. */
+int mik_dense_chol_solve(mik_dense_chol *F, void *y, const void *x);
+/* The same as a mik_ldiv_fn (user = the handle): a host fills mik_precond{NULL, mik_dense_chol_ldiv_fn, handle} and the fused iterables
+ * apply Pl / Pr with no host frame of the caller's. */
+int mik_dense_chol_ldiv_fn(void *user, void *y, const void *x);
+/* Every size at which the code switches, for the handle's element type.  panel_w: W; rows_per_group: rows per workgroup of the panel
+ * kernel; tile_rows / tile_cols: the tile of the trailing update; launches_factor: kernel launches the factorisation made (3 per panel, 1
+ * for the last); launches_solve: launches of one solve (2 ceil(n / W)); bytes: device memory held besides A; info: 0, or the 1-based index
+ * of the first failing column.  Any pointer may be NULL. */
+int mik_dense_chol_info(const mik_dense_chol *F, int64_t *panel_w, int64_t *rows_per_group, int64_t *tile_rows, int64_t *tile_cols,
+                        int64_t *launches_factor, int64_t *launches_solve, int64_t *bytes, int64_t *info);
 
 /* ---- svdl: Golub-Kahan-Lanczos bidiagonalisation with thick restart (src/svdl.jl) ------------------------------------------
  * The Lanczos loop of extend! (:542-609) runs on mik_spmv (A and its adjoint as two operators), mik_gemv_t / mik_gemv_n and the fused

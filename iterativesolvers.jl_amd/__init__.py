@@ -10,6 +10,7 @@ The directory name (``iterativesolvers.jl_amd``) is not a Python identifier; loa
   stationary.py  jacobi / gauss_seidel / sor / ssor and their iterables on a HipCSR (src/stationary_sparse.jl)
   stationary_dense.py  the same four on a dense HipMatrix (src/stationary.jl), and the public names that dispatch between the two
   dense_lu.py  lu / lu_ of a dense HipMatrix (partial pivoting on the device) and its ldiv_: the exact Pl / Pr of the reference's tests
+  dense_chol.py  cholesky / cholesky_ of a dense HipMatrix, real or complex (lower form, on the device) and its ldiv_: the Pl of test/cg.jl:44-47
   svdl.py    svdl: Golub-Kahan-Lanczos SVD with thick restart (src/svdl.jl) on a HipCSR uploaded with its adjoint, or on a HipMatrix
   lobpcg.py  lobpcg: block eigensolver (src/lobpcg.jl) on HipCSR operators, with dense=True also on dense HipMatrix ones, every sweep on a block of columns
   extras.py  solvers outside the scope contract (IDR(s), LSQR, LSMR, QMR, power method); kept apart, unjudged
@@ -29,12 +30,13 @@ from .api import (CGIterable, CGStateVariables, ClassicalGramSchmidt, Convergenc
                   gemv_t_, lu_solve_, ChebyshevIterable, chebyshev, chebyshev_, chebyshev_iterable_, MINRESIterable, minres, minres_,
                   minres_iterable_, givens_algorithm, axpy_dot_, axpy2_nrm2_, gram_, LinearOperator, cheb_direction_, minres_update_,
                   bicgstab_mr_update_)
-from .stationary import (GaussSeidelIterable, JacobiIterable, SingularException, SORIterable, SSORIterable,   # noqa: F401
+from .stationary import (GaussSeidelIterable, JacobiIterable, PosDefException, SingularException, SORIterable, SSORIterable,   # noqa: F401
                          StationaryOperator)
 from .stationary_dense import (DenseGaussSeidelIterable, DenseJacobiIterable, DenseSORIterable, DenseSSORIterable,   # noqa: F401
                                DenseStationaryOperator, gauss_seidel, gauss_seidel_, gauss_seidel_iterable, jacobi, jacobi_,
                                jacobi_iterable, sor, sor_, sor_iterable, ssor, ssor_, ssor_iterable)   # dispatch: HipCSR -> stationary.py
 from .dense_lu import DenseLU, lu, lu_                   # noqa: F401
+from .dense_chol import DenseCholesky, cholesky, cholesky_   # noqa: F401
 from .svdl import (BrokenArrowBidiagonal, PartialFactorization, svdl, svdl_method_, isconverged, build, thickrestart_,   # noqa: F401
                    harmonicrestart_, extend_, ArgumentError, BoundsError, SvdlBreakdown, SVD)
 from .lobpcg import (LOBPCGIterator, LOBPCGResults, LOBPCGState, LobpcgCholeskyError, LobpcgRefusal, lobpcg, lobpcg_)   # noqa: F401

@@ -619,6 +619,12 @@ class _Bound:
                 raise ValueError(f"DimensionMismatch: the lu of a {P.n} x {P.n} {P.dtype} matrix as a preconditioner of {self.n}-vectors of {self.dtype}")
             self.keep.append(P)
             return _lib.MikPrecond(None, C.cast(lib().mik_dense_lu_ldiv_fn, _lib.LDIV_FN), P.handle)
+        from .dense_chol import DenseCholesky
+        if isinstance(P, DenseCholesky):                                 # likewise
+            if P.n != self.n or P.dtype != self.dtype:
+                raise ValueError(f"DimensionMismatch: the cholesky of a {P.n} x {P.n} {P.dtype} matrix as a preconditioner of {self.n}-vectors of {self.dtype}")
+            self.keep.append(P)
+            return _lib.MikPrecond(None, C.cast(lib().mik_dense_chol_ldiv_fn, _lib.LDIV_FN), P.handle)
         if not callable(getattr(P, "ldiv_", None)):
             raise MikError(5, "preconditioner", "needs ldiv_(y, x) (docs/src/preconditioning.md:5-14)")
 

@@ -1,0 +1,162 @@
+// mik_dense_chol.hip -- cholesky!(Hermitian(A, :L)) and ldiv!(y, F, x) on a square column-major device matrix, real and complex: what the
+// reference's tests pass as Pl to cg (test/cg.jl:44-47) and to chebyshev (test/chebyshev.jl:59-66) in all four element types.
+//
+// The bit contract and the kernels are in csrc/mik_dense_chol.h.  The plan is right-looking over panels of W columns, three launches per
+// panel -- the diagonal block in one workgroup, the rows below it, the lower tiles of the trailing update -- where the pivoted LU needs
+// 2 W + 4; the last panel has no rows below it and is one launch.  Every dependency between workgroups is a kernel boundary on the context's
+// stream.  A column whose pivot is not positive records its index and the remaining launches still run; create reads the flag once at the
+// end -- the factorisation's only host synchronisation.  ldiv! is ceil(n / W) launches each way; nothing is allocated per solve.
+#include "mik_internal.h"
+#include "mik_dense_chol.h"
+
+#include <new>
+
+struct mik_dense_chol {
+    mik_ctx *ctx = nullptr;
+    int dtype = MIK_F64;
+    int n = 0;
+    int64_t ld = 0;
+    void *A = nullptr;               // the caller's matrix, its lower triangle now L
+    void *work = nullptr;            // n elements: the accumulators of both substitutions
+    int *flag = nullptr;             // device: the first failing column, or a value above every column index
+    int64_t info = 0;                // 0, or the 1-based index of the first column whose pivot was not positive
+    int64_t launches_factor = 0;
+    int64_t bytes = 0;
+};
+
+namespace {
+
+void chol_free(mik_dense_chol *F)
+{
+    if (!F) return;
+    if (F->ctx) { (void)hipSetDevice(F->ctx->device); (void)hipStreamSynchronize(F->ctx->stream); }
+    for (void *p : {F->work, (void *)F->flag})
+        if (p) (void)hipFree(p);
+    delete F;
+}
+
+inline unsigned chol_grid(int count, int per) { return (unsigned)((count + per - 1) / per); }
+
+template <typename E>
+int chol_factor(mik_dense_chol *F)
+{
+    mik_ctx *ctx = F->ctx;
+    hipStream_t st = ctx->stream;
+    const int n = F->n;
+    const int64_t ld = F->ld;
+    E *A = (E *)F->A;
+    MIK_HIP(ctx, hipMemsetAsync(F->flag, 0x7f, sizeof(int), st));                // 0x7f7f7f7f: above every column index
+    int64_t launches = 0;
+    for (int k0 = 0; k0 < n; k0 += MIK_CH_W) {
+        const int k1 = std::min(k0 + MIK_CH_W, n);
+        hipLaunchKernelGGL((k_chol_diag<E>), dim3(1), dim3(MIK_CH_THREADS), 0, st, k0, k1 - k0, A, ld, F->flag);
+        ++launches;
+        if (k1 < n) {
+            const unsigned tiles = chol_grid(n - k1, MIK_CH_T);
+            hipLaunchKernelGGL((k_chol_panel<E>), dim3(chol_grid(n - k1, MIK_CH_R)), dim3(MIK_CH_THREADS), 0, st, n, k0, k1 - k0, A, ld);
+            hipLaunchKernelGGL((k_chol_trail<E>), dim3(tiles, tiles), dim3(MIK_CH_THREADS), 0, st, n, k0, A, ld);
+            launches += 2;
+        }
+        MIK_LAUNCH_CHECK(ctx);
+    }
+    F->launches_factor = launches;
+    int first = 0;
+    MIK_HIP(ctx, hipMemcpyAsync(&first, F->flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    MIK_HIP(ctx, hipStreamSynchronize(st));
+    F->info = first < n ? (int64_t)first + 1 : 0;
+    return MIK_OK;
+}
+
+template <typename E>
+int chol_solve_dev(mik_dense_chol *F, E *y, const E *x)
+{
+    mik_ctx *ctx = F->ctx;
+    hipStream_t st = ctx->stream;
+    const int n = F->n;
+    const E *A = (const E *)F->A;
+    E *t = (E *)F->work;
+    for (int k0 = 0; k0 < n; k0 += MIK_CH_W)
+        hipLaunchKernelGGL((k_chol_fwd<E>), dim3(chol_grid(n - k0, MIK_DS_R)), dim3(MIK_DS_R), 0, st, n, k0, A, F->ld, k0 ? (const E *)t : x, t);
+    for (int k0 = (n - 1) / MIK_CH_W * MIK_CH_W; k0 >= 0; k0 -= MIK_CH_W)
+        hipLaunchKernelGGL((k_chol_bwd<E>), dim3((unsigned)(k0 / MIK_DS_R + 1)), dim3(MIK_DS_R), 0, st, n, k0, std::min(k0 + MIK_CH_W, n), A, F->ld, t, y);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
+}  // namespace
+
+extern "C" int mik_dense_chol_create(mik_ctx *ctx, void *A, int64_t n, int64_t ld, int dtype, int check, int64_t *failed_col, mik_dense_chol **out)
+{
+    if (failed_col) *failed_col = 0;
+    if (!ctx || !A || !out) return MIK_ERR_INVALID;
+    *out = nullptr;
+    if (dtype != MIK_F64 && dtype != MIK_F32 && dtype != MIK_C64 && dtype != MIK_C32)
+        return mik_fail(ctx, MIK_ERR_INVALID, "mik_dense_chol_create: dtype must be MIK_F64, MIK_F32, MIK_C64 or MIK_C32");
+    if (n < 1 || ld < n) return mik_fail(ctx, MIK_ERR_MISMATCH, "mik_dense_chol_create: n = %lld, ld = %lld (need 1 <= n <= ld)", (long long)n, (long long)ld);
+    if (n > (int64_t)std::numeric_limits<int>::max() - MIK_CH_W) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_dense_chol_create: n >= 2^31 - 64");
+    mik_dense_chol *F = new (std::nothrow) mik_dense_chol();
+    if (!F) return mik_fail(ctx, MIK_ERR_NOMEM, "mik_dense_chol_create: host allocation failed");
+    F->ctx = ctx; F->dtype = dtype; F->n = (int)n; F->ld = ld; F->A = A;
+    (void)hipSetDevice(ctx->device);
+    const size_t vec = std::max<size_t>((size_t)n * mik_dtype_size(dtype), 16);
+    auto alloc = [&]() -> int {
+        MIK_HIP(ctx, hipMalloc(&F->work, vec));
+        MIK_HIP(ctx, hipMalloc((void **)&F->flag, 16));
+        return MIK_OK;
+    };
+    int rc = alloc();
+    F->bytes = (int64_t)(vec + 16);
+    if (rc == MIK_OK)
+        rc = dtype == MIK_F64   ? chol_factor<double>(F)
+             : dtype == MIK_F32 ? chol_factor<float>(F)
+             : dtype == MIK_C64 ? chol_factor<chol_cx<double>>(F)
+                                : chol_factor<chol_cx<float>>(F);
+    if (rc == MIK_OK && F->info && check) {
+        if (failed_col) *failed_col = F->info;
+        rc = mik_fail(ctx, MIK_ERR_SINGULAR, "mik_dense_chol_create: PosDefException(%lld): the matrix is not positive definite, the pivot of that column is not positive",
+                      (long long)F->info);
+    }
+    if (rc != MIK_OK) { chol_free(F); return rc; }
+    if (failed_col) *failed_col = F->info;
+    *out = F;
+    return MIK_OK;
+}
+
+extern "C" int mik_dense_chol_destroy(mik_dense_chol *F)
+{
+    chol_free(F);
+    return MIK_OK;
+}
+
+extern "C" int mik_dense_chol_solve(mik_dense_chol *F, void *y, const void *x)
+{
+    if (!F || !y || !x) return MIK_ERR_INVALID;
+    if (F->info) return mik_fail(F->ctx, MIK_ERR_INVALID, "mik_dense_chol_solve: the factorisation failed at column %lld (PosDefException)", (long long)F->info);
+    const size_t es = mik_dtype_size(F->dtype), bytes = (size_t)F->n * es, all = (size_t)F->ld * (size_t)F->n * es;
+    if (y != x && mik_overlap(y, bytes, x, bytes)) return mik_fail(F->ctx, MIK_ERR_INVALID, "mik_dense_chol_solve: y and x overlap without being equal");
+    if (mik_overlap(y, bytes, F->A, all) || mik_overlap(x, bytes, F->A, all)) return mik_fail(F->ctx, MIK_ERR_INVALID, "mik_dense_chol_solve: a vector overlaps the factors");
+    (void)hipSetDevice(F->ctx->device);
+    switch (F->dtype) {
+    case MIK_F64: return chol_solve_dev<double>(F, (double *)y, (const double *)x);
+    case MIK_F32: return chol_solve_dev<float>(F, (float *)y, (const float *)x);
+    case MIK_C64: return chol_solve_dev<chol_cx<double>>(F, (chol_cx<double> *)y, (const chol_cx<double> *)x);
+    default: return chol_solve_dev<chol_cx<float>>(F, (chol_cx<float> *)y, (const chol_cx<float> *)x);
+    }
+}
+
+extern "C" int mik_dense_chol_ldiv_fn(void *user, void *y, const void *x) { return mik_dense_chol_solve((mik_dense_chol *)user, y, x); }
+
+extern "C" int mik_dense_chol_info(const mik_dense_chol *F, int64_t *panel_w, int64_t *rows_per_group, int64_t *tile_rows, int64_t *tile_cols,
+                                   int64_t *launches_factor, int64_t *launches_solve, int64_t *bytes, int64_t *info)
+{
+    if (!F) return MIK_ERR_INVALID;
+    if (panel_w) *panel_w = MIK_CH_W;
+    if (rows_per_group) *rows_per_group = MIK_CH_R;
+    if (tile_rows) *tile_rows = MIK_CH_T;
+    if (tile_cols) *tile_cols = MIK_CH_T;
+    if (launches_factor) *launches_factor = F->launches_factor;
+    if (launches_solve) *launches_solve = 2 * (((int64_t)F->n + MIK_CH_W - 1) / MIK_CH_W);
+    if (bytes) *bytes = F->bytes;
+    if (info) *info = F->info;
+    return MIK_OK;
+}

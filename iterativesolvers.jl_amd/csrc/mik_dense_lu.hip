@@ -1,5 +1,5 @@
 // mik_dense_lu.hip -- lu!(A) with partial pivoting and ldiv!(y, F, x) on a square column-major device matrix: what the reference's
-// tests pass as Pl / Pr (test/gmres.jl:28-35, test/cg.jl:44-47, test/bicgstabl.jl:40-42) and as the operator of invpowm.
+// tests pass as Pl / Pr (test/gmres.jl:28-35, test/bicgstabl.jl:40-42) and as the operator of invpowm.
 //
 // The bit contract is stated in csrc/mik_dense_lu.h: the factors, the pivots and the solution are those of the unblocked loops of
 // lu_solve<T> (csrc/mik_krylov.hip).  The plan is right-looking over panels of W columns:

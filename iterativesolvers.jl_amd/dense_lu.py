@@ -1,5 +1,5 @@
 """``lu(A)`` / ``lu!(A)`` of a square dense device matrix and ``ldiv!(y, F, x)`` -- what the reference's tests pass as ``Pl`` / ``Pr``
-(test/gmres.jl:28-35, test/cg.jl:44-47, test/bicgstabl.jl:40-42, test/idrs.jl:55) and as the operator of ``invpowm``
+(test/gmres.jl:28-35, test/bicgstabl.jl:40-42, test/idrs.jl:55) and as the operator of ``invpowm``
 (test/simple_eigensolvers.jl:40) -- over the ``mik_dense_lu_*`` entries of include/mik.h.
 
 The factorisation (partial pivoting) and both substitutions run on the device.  The factors, the pivots and the solution are bit for

@@ -423,6 +423,10 @@ function precond_struct(P, ::Type{T}, n::Int, ctx::Context, keep::Vector{Any}) w
         push!(keep, P)
         return lu_precond_struct(P, T, n)
     end
+    if P isa HipCholesky
+        push!(keep, P)
+        return chol_precond_struct(P, T, n)
+    end
     box = CallbackBox{T}(P, n, ctx); push!(keep, box)
     MikPrecond(C_NULL, @cfunction(ldiv_trampoline, Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid})), pointer_from_objref(box))
 end
@@ -1347,7 +1351,7 @@ function dense_operator_struct(A::HipDenseAdjoint, ::Type{T}, n::Int) where {T}
 end
 
 # ---- dense LU: lu(A) / lu!(A) with partial pivoting and ldiv!(y, F, x) on a dense device matrix (csrc/mik_dense_lu.hip) ------------------
-# What the reference's tests pass as Pl / Pr (test/gmres.jl:28-35, test/cg.jl:44-47, test/bicgstabl.jl:40-42) and wrap as the operator of
+# What the reference's tests pass as Pl / Pr (test/gmres.jl:28-35, test/bicgstabl.jl:40-42) and wrap as the operator of
 # invpowm (test/simple_eigensolvers.jl:40).  Factors, pivots and solution have the bits of the unblocked loops of mik_lu_solve (include/mik.h).
 mutable struct HipLU{T}
     handle::Ptr{Cvoid}
@@ -1397,6 +1401,60 @@ end
 function lu_precond_struct(F::HipLU, ::Type{T}, n::Int) where {T}
     (eltype(F) == T && F.factors.n == n) || throw(DimensionMismatch("the lu of a $(F.factors.n) x $(F.factors.n) $(eltype(F)) matrix as a preconditioner of $n-vectors of $T"))
     MikPrecond(C_NULL, cglobal((:mik_dense_lu_ldiv_fn, libmik)), F.handle)
+end
+
+# ---- dense Cholesky: cholesky(A) / cholesky!(A) in the lower form and ldiv!(y, F, x) on a dense device matrix, real or complex ------------
+# (csrc/mik_dense_chol.hip).  What the reference's tests pass as Pl to cg (test/cg.jl:44-47) and to chebyshev (test/chebyshev.jl:59-66).
+# Only the lower triangle of A and the real parts of its diagonal are read; whether A is Hermitian is not checked.  The factor and the
+# solution have the bits of the unblocked loops stated in include/mik.h.
+mutable struct HipCholesky{T}
+    handle::Ptr{Cvoid}
+    factors::HipDenseMatrix{T}       # the lower triangle holds L, read at every solve; kept alive with the handle
+    uplo::Char                       # 'L'
+    info::Int64                      # 0, or the first column whose pivot was not positive (check = false)
+    ctx::Context
+end
+function LinearAlgebra.cholesky!(A::HipDenseMatrix{T}; check::Bool = true) where {T}
+    size(A, 1) == size(A, 2) || throw(DimensionMismatch("the matrix is $(size(A, 1)) x $(size(A, 2)), not square"))
+    h = Ref{Ptr{Cvoid}}(C_NULL); col = Ref{Int64}(0)
+    code = ccall((:mik_dense_chol_create, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Cint, Ref{Int64}, Ref{Ptr{Cvoid}}),
+                 A.ctx.handle, A.ptr, A.n, A.ld, dtype_code(T), check ? 1 : 0, col, h)
+    code == 8 && throw(LinearAlgebra.PosDefException(Int(col[])))
+    MIK.check(code, "mik_dense_chol_create", A.ctx.handle)     # `check` is the keyword here
+    F = HipCholesky{T}(h[], A, 'L', col[], A.ctx)
+    finalizer(o -> alive(o.ctx) && ccall((:mik_dense_chol_destroy, libmik), Cint, (Ptr{Cvoid},), o.handle), F)
+    F
+end
+function LinearAlgebra.cholesky(A::HipDenseMatrix{T}; check::Bool = true) where {T}        # factors a copy
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    MIK.check(ccall((:mik_malloc, libmik), Cint, (Ptr{Cvoid}, Csize_t, Ref{Ptr{Cvoid}}), A.ctx.handle, A.ld * max(A.cols, 1) * sizeof(T), p), "mik_malloc", A.ctx.handle)
+    m = HipDenseMatrix{T}(p[], A.n, A.cols, A.ld, A.ctx)
+    finalizer(x -> alive(x.ctx) && ccall((:mik_free, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), x.ctx.handle, x.ptr), m)
+    MIK.check(ccall((:mik_copy, libmik), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}), A.ctx.handle, dtype_code(T), A.ld * A.cols, A.ptr, m.ptr),
+              "mik_copy", A.ctx.handle)
+    LinearAlgebra.cholesky!(m; check = check)
+end
+Base.size(F::HipCholesky) = size(F.factors)
+Base.size(F::HipCholesky, d::Integer) = size(F.factors, d)
+Base.eltype(::HipCholesky{T}) where {T} = T
+LinearAlgebra.issuccess(F::HipCholesky) = F.info == 0
+function LinearAlgebra.ldiv!(y::HipVector{T}, F::HipCholesky{T}, x::HipVector{T}) where {T}
+    (length(y) == F.factors.n && length(x) == F.factors.n) || throw(DimensionMismatch("ldiv!: vectors of $(length(y)) and $(length(x)), a factorisation of order $(F.factors.n)"))
+    MIK.check(ccall((:mik_dense_chol_solve, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), F.handle, y.ptr, x.ptr), "mik_dense_chol_solve", F.ctx.handle)
+    y
+end
+LinearAlgebra.ldiv!(F::HipCholesky{T}, x::HipVector{T}) where {T} = LinearAlgebra.ldiv!(x, F, x)
+Base.:\(F::HipCholesky{T}, x::HipVector{T}) where {T} = LinearAlgebra.ldiv!(similar(x), F, x)
+"panel width, rows per workgroup of the panel kernel, tile of the trailing update, launches, device bytes, info"
+function dense_chol_info(F::HipCholesky)
+    w = Ref{Int64}(0); r = Ref{Int64}(0); tr = Ref{Int64}(0); tc = Ref{Int64}(0); lf = Ref{Int64}(0); ls = Ref{Int64}(0); b = Ref{Int64}(0); info = Ref{Int64}(0)
+    MIK.check(ccall((:mik_dense_chol_info, libmik), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                    F.handle, w, r, tr, tc, lf, ls, b, info), "mik_dense_chol_info", F.ctx.handle)
+    (W = w[], R = r[], tile_rows = tr[], tile_cols = tc[], launches_factor = lf[], launches_solve = ls[], bytes = b[], info = info[])
+end
+function chol_precond_struct(F::HipCholesky, ::Type{T}, n::Int) where {T}
+    (eltype(F) == T && F.factors.n == n) || throw(DimensionMismatch("the cholesky of a $(F.factors.n) x $(F.factors.n) $(eltype(F)) matrix as a preconditioner of $n-vectors of $T"))
+    MikPrecond(C_NULL, cglobal((:mik_dense_chol_ldiv_fn, libmik)), F.handle)
 end
 
 end # module

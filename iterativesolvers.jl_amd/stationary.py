@@ -46,6 +46,14 @@ class SingularException(np.linalg.LinAlgError):
         super().__init__(f"SingularException({self.col})")
 
 
+class PosDefException(np.linalg.LinAlgError):
+    """``LinearAlgebra.PosDefException(k)``: the pivot of column ``k`` (1-based) of a Cholesky factorisation is not positive."""
+
+    def __init__(self, k: int):
+        self.k = int(k)
+        super().__init__(f"PosDefException({self.k}): matrix is not positive definite; the factorisation failed at column {self.k}")
+
+
 def _host(dtype, value):
     a = np.asarray([value], dtype=dtype)
     return a, a.ctypes.data_as(_vp)
