@@ -9,6 +9,7 @@ The directory name (``iterativesolvers.jl_amd``) is not a Python identifier; loa
              a HipMatrix is an operator too (mul!(y, A::Matrix, x) and adjoint(A): csrc/mik_dense_mul.hip)
   stationary.py  jacobi / gauss_seidel / sor / ssor and their iterables on a HipCSR (src/stationary_sparse.jl)
   stationary_dense.py  the same four on a dense HipMatrix (src/stationary.jl), and the public names that dispatch between the two
+  dense_factor.py  what dense_lu.py and dense_chol.py share: the refusals, the handle, ldiv_ / solve, "factor a copy"
   dense_lu.py  lu / lu_ of a dense HipMatrix (partial pivoting on the device) and its ldiv_: the exact Pl / Pr of the reference's tests
   dense_chol.py  cholesky / cholesky_ of a dense HipMatrix, real or complex (lower form, on the device) and its ldiv_: the Pl of test/cg.jl:44-47
   svdl.py    svdl: Golub-Kahan-Lanczos SVD with thick restart (src/svdl.jl) on a HipCSR uploaded with its adjoint, or on a HipMatrix

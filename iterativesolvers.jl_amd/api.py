@@ -613,18 +613,12 @@ class _Bound:
             return None
         if isinstance(P, JacobiPrec):
             return _lib.MikPrecond(P.diagonal.ptr, _lib.LDIV_FN(), None)
-        from .dense_lu import DenseLU                                    # (dense_lu imports this module)
-        if isinstance(P, DenseLU):                                       # the library's own callback: no Python frame per ldiv!
+        from .dense_factor import DenseFactor                            # (dense_factor imports this module)
+        if isinstance(P, DenseFactor):                                   # lu / cholesky: the library's own callback, no Python frame per ldiv!
             if P.n != self.n or P.dtype != self.dtype:                   # the callback never sees the vector lengths
-                raise ValueError(f"DimensionMismatch: the lu of a {P.n} x {P.n} {P.dtype} matrix as a preconditioner of {self.n}-vectors of {self.dtype}")
+                raise ValueError(f"DimensionMismatch: the {P._name} of a {P.n} x {P.n} {P.dtype} matrix as a preconditioner of {self.n}-vectors of {self.dtype}")
             self.keep.append(P)
-            return _lib.MikPrecond(None, C.cast(lib().mik_dense_lu_ldiv_fn, _lib.LDIV_FN), P.handle)
-        from .dense_chol import DenseCholesky
-        if isinstance(P, DenseCholesky):                                 # likewise
-            if P.n != self.n or P.dtype != self.dtype:
-                raise ValueError(f"DimensionMismatch: the cholesky of a {P.n} x {P.n} {P.dtype} matrix as a preconditioner of {self.n}-vectors of {self.dtype}")
-            self.keep.append(P)
-            return _lib.MikPrecond(None, C.cast(lib().mik_dense_chol_ldiv_fn, _lib.LDIV_FN), P.handle)
+            return _lib.MikPrecond(None, C.cast(getattr(lib(), f"{P._entry}_ldiv_fn"), _lib.LDIV_FN), P.handle)
         if not callable(getattr(P, "ldiv_", None)):
             raise MikError(5, "preconditioner", "needs ldiv_(y, x) (docs/src/preconditioning.md:5-14)")
 

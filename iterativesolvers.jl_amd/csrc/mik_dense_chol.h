@@ -20,62 +20,28 @@
 //                 current column in LDS), records a failing column (atomicMin) and stores the block's L
 //   k_chol_panel  L21 = A21 L11^-H: four lanes own a row below the block, its W values in their registers, L11 in LDS, k ascending, the
 //                 division last
-//   k_chol_trail  A22[i,c] -= sum_k L21[i,k] conj(L21[c,k]), k ascending: TR x TC tiles with blockIdx.x >= blockIdx.y, the diagonal
+//   k_dense_trail<E, true>  A22[i,c] -= sum_k L21[i,k] conj(L21[c,k]), k ascending: T x T tiles with blockIdx.x >= blockIdx.y, the diagonal
 //                 tiles masked to r >= c, both LDS tiles loaded from L21 along contiguous rows
 // and per panel of a solve one launch each way:
-//   k_chol_fwd    one panel of the forward substitution (k_lu_fwd's shape, with the division by the diagonal)
+//   k_dense_fwd<E, false>   one panel of the forward substitution, with the division by the diagonal
 //   k_chol_bwd    one panel of the backward substitution: row r needs conj(L[c,r]), element c of COLUMN r, so the block is loaded along
 //                 its columns (coalesced), turned in LDS (padded pitch) and walked from there, c descending
+// The element (de_cx and the de_* operations), the serial step of a diagonal block (de_step) and the two k_dense_* kernels are those of
+// csrc/mik_dense_elem.h, written once for the dense stationary methods, the LU and this file.
 // Nothing indexes memory through a data value, so an indefinite or non-finite matrix cannot fault: after the first failing column the
 // remaining launches run on whatever values there are.
 #pragma once
 #include "mik_internal.h"
-#include "mik_complex.h"
-#include "mik_dense_stationary.h"
+#include "mik_dense_elem.h"
 
 #include <utility>
 
-constexpr int MIK_CH_W = 64;            // panel width; the substitution panels are the factorisation's
+constexpr int MIK_CH_W = MIK_DS_W;      // panel width; the substitution panels are the factorisation's
 constexpr int MIK_CH_R = 64;            // rows per workgroup of k_chol_panel (four waves; wave g owns the columns g, g + 4, ... of the 64 rows)
-constexpr int MIK_CH_T = 64;            // tile edge of the trailing update (rows and columns)
-constexpr int MIK_CH_THREADS = 256;     // workgroup of k_chol_diag, of k_chol_panel and of k_chol_trail (16 x 16 lanes, 4 x 4 elements each)
+constexpr int MIK_CH_T = MIK_DS_T;      // tile edge of the trailing update (rows and columns)
+constexpr int MIK_CH_THREADS = 256;     // workgroup of k_chol_diag and of k_chol_panel
 constexpr int MIK_CH_BC = 32;           // columns per transposed chunk of the backward substitution
-static_assert(MIK_CH_W == 64 && MIK_CH_R == 64 && MIK_CH_T == 64 && MIK_CH_THREADS == 256 && MIK_CH_W % MIK_CH_BC == 0 && MIK_DS_R == 64,
-              "the loaders are written for these sizes");
-
-// ---- the element: a real, or an interleaved (re, im) pair moved as one 8- or 16-byte access --------------------------------------------
-template <typename R> struct alignas(2 * sizeof(R)) chol_cx { R re, im; };
-template <typename E> struct chol_real { using type = E; };
-template <typename R> struct chol_real<chol_cx<R>> { using type = R; };
-// rows of the trailing update's LDS tiles per pass: both tiles stay within 32 KB, two workgroups and more per compute unit
-template <typename E> struct chol_kc { static constexpr int value = sizeof(E) <= 4 ? 64 : sizeof(E) <= 8 ? 32 : 16; };
-
-template <typename E> __device__ __forceinline__ E ch_zero() { return E{}; }
-__device__ __forceinline__ float ch_re(float a) { return a; }
-__device__ __forceinline__ double ch_re(double a) { return a; }
-template <typename R> __device__ __forceinline__ R ch_re(chol_cx<R> a) { return a.re; }
-__device__ __forceinline__ void ch_set_real(float &a, float d) { a = d; }
-__device__ __forceinline__ void ch_set_real(double &a, double d) { a = d; }
-template <typename R> __device__ __forceinline__ void ch_set_real(chol_cx<R> &a, R d) { a.re = d; a.im = R(0); }
-// a = a - l conj(m)
-__device__ __forceinline__ void ch_msub_cj(float &a, float l, float m) { const float p = l * m; a = a - p; }
-__device__ __forceinline__ void ch_msub_cj(double &a, double l, double m) { const double p = l * m; a = a - p; }
-template <typename R> __device__ __forceinline__ void ch_msub_cj(chol_cx<R> &a, chol_cx<R> l, chol_cx<R> m) { cx_msub(l.re, l.im, m.re, -m.im, a.re, a.im); }
-// a = a - l w
-__device__ __forceinline__ void ch_msub(float &a, float l, float w) { const float p = l * w; a = a - p; }
-__device__ __forceinline__ void ch_msub(double &a, double l, double w) { const double p = l * w; a = a - p; }
-template <typename R> __device__ __forceinline__ void ch_msub(chol_cx<R> &a, chol_cx<R> l, chol_cx<R> w) { cx_msub(l.re, l.im, w.re, w.im, a.re, a.im); }
-// a = a - conj(l) y
-__device__ __forceinline__ void ch_msub_lc(float &a, float l, float y) { ch_msub(a, l, y); }
-__device__ __forceinline__ void ch_msub_lc(double &a, double l, double y) { ch_msub(a, l, y); }
-template <typename R> __device__ __forceinline__ void ch_msub_lc(chol_cx<R> &a, chol_cx<R> l, chol_cx<R> y) { cx_msub(l.re, -l.im, y.re, y.im, a.re, a.im); }
-// a / d for a real d: one division per component
-__device__ __forceinline__ float ch_div(float a, float d) { return a / d; }
-__device__ __forceinline__ double ch_div(double a, double d) { return a / d; }
-template <typename R> __device__ __forceinline__ chol_cx<R> ch_div(chol_cx<R> a, R d) { return chol_cx<R>{a.re / d, a.im / d}; }
-__device__ __forceinline__ float ch_bcast(float v, int j) { return ds_bcast(v, j); }
-__device__ __forceinline__ double ch_bcast(double v, int j) { return ds_bcast(v, j); }
-template <typename R> __device__ __forceinline__ chol_cx<R> ch_bcast(chol_cx<R> v, int j) { return chol_cx<R>{ds_bcast(v.re, j), ds_bcast(v.im, j)}; }
+static_assert(MIK_CH_W == 64 && MIK_CH_R == 64 && MIK_CH_THREADS == 256 && MIK_CH_W % MIK_CH_BC == 0 && MIK_DS_R == 64, "the loaders are written for these sizes");
 
 // ---- the diagonal block [k0, k0 + w), w <= W.  ONE workgroup of four waves.  Thread (i, g) keeps the elements (i, c) of the columns
 // c = g, g + 4, ... in registers, so wave g owns every fourth column.  Column j: its wave reads the pivot from lane j, divides, and puts
@@ -85,22 +51,22 @@ template <typename R> __device__ __forceinline__ chol_cx<R> ch_bcast(chol_cx<R> 
 template <typename E, int J>
 __device__ __forceinline__ void chol_diag_col(E (&a)[MIK_CH_W / (MIK_CH_THREADS / 64)], E (*Cb)[MIK_CH_W], int i, int g, int w, int k0, int *first_bad)
 {
-    using R = typename chol_real<E>::type;
+    using R = typename de_real<E>::type;
     constexpr int G = MIK_CH_THREADS / 64, Q = MIK_CH_W / G, QJ = J / G;
     if (J >= w) return;                                        // workgroup-uniform
     if (g == J % G) {
-        const R d = ds_bcast(ch_re(a[QJ]), J);
+        const R d = ds_bcast(de_re(a[QJ]), J);
         const R ljj = mik_sqrt(d);
         if (i == 0 && !(d > R(0))) atomicMin(first_bad, k0 + J);
-        if (i == J) ch_set_real(a[QJ], ljj);
-        else if (i > J) a[QJ] = ch_div(a[QJ], ljj);
+        if (i == J) de_set_real(a[QJ], ljj);
+        else if (i > J) a[QJ] = de_div(a[QJ], ljj);
         Cb[J & 1][i] = a[QJ];
     }
     __syncthreads();
     const E lij = Cb[J & 1][i];
 #pragma unroll
     for (int q = QJ; q < Q; ++q)
-        if (q > QJ || g > J % G) ch_msub_cj(a[q], lij, Cb[J & 1][g + G * q]);      // the columns c > J of this thread
+        if (q > QJ || g > J % G) de_msub_cj(a[q], lij, Cb[J & 1][g + G * q]);      // the columns c > J of this thread
 }
 template <typename E, int... J>
 __device__ __forceinline__ void chol_diag_cols(std::integer_sequence<int, J...>, E (&a)[MIK_CH_W / (MIK_CH_THREADS / 64)], E (*Cb)[MIK_CH_W], int i, int g, int w,
@@ -121,7 +87,7 @@ __global__ void __launch_bounds__(MIK_CH_THREADS) k_chol_diag(int k0, int w, E *
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
         const int c = g + G * q;
-        a[q] = (i >= c && i < w) ? Ab[(int64_t)c * ld + i] : ch_zero<E>();      // i < w and i >= c: c < w
+        a[q] = (i >= c && i < w) ? Ab[(int64_t)c * ld + i] : de_zero<E>();      // i < w and i >= c: c < w
     }
     chol_diag_cols<E>(std::make_integer_sequence<int, W>{}, a, Cb, i, g, w, k0, first_bad);
 #pragma unroll
@@ -144,14 +110,14 @@ __device__ __forceinline__ void chol_panel_col(E (&a)[MIK_CH_W / (MIK_CH_THREADS
     constexpr int W = MIK_CH_W, G = MIK_CH_THREADS / 64, Q = W / G, QK = K / G, OFF = K * W - K * (K - 1) / 2;
     if (K >= w) return;                                        // workgroup-uniform and never taken (w = W), see k_chol_panel
     if (g == K % G) {
-        a[QK] = ch_div(a[QK], ch_re(Lt[OFF]));
+        a[QK] = de_div(a[QK], de_re(Lt[OFF]));
         Cb[K & 1][i] = a[QK];
     }
     __syncthreads();
     const E vk = Cb[K & 1][i];
 #pragma unroll
     for (int q = QK; q < Q; ++q)
-        if (q > QK || g > K % G) ch_msub_cj(a[q], vk, Lt[OFF + g + G * q - K]);      // the columns c > K of this thread
+        if (q > QK || g > K % G) de_msub_cj(a[q], vk, Lt[OFF + g + G * q - K]);      // the columns c > K of this thread
 }
 template <typename E, int... K>
 __device__ __forceinline__ void chol_panel_cols(std::integer_sequence<int, K...>, E (&a)[MIK_CH_W / (MIK_CH_THREADS / 64)], const E *Lt, E (*Cb)[MIK_CH_W], int i, int g,
@@ -188,130 +154,6 @@ __global__ void __launch_bounds__(MIK_CH_THREADS) k_chol_panel(int n, int k0, in
     }
 }
 
-// ---- A22 -= L21 L21^H for the full panel [k0, k0 + W): tile (blockIdx.x, blockIdx.y) of T x T elements from (k0 + W, k0 + W), the lower
-// tiles only.  Both LDS tiles are rows of L21: Rs[k * T + i] = L21[r0 + i, k], Cs[k * T + c] = L21[c0 + c, k], KC columns k per pass.
-template <typename E>
-__global__ void __launch_bounds__(MIK_CH_THREADS) k_chol_trail(int n, int k0, E *A, int64_t ld)
-{
-    constexpr int W = MIK_CH_W, T = MIK_CH_T, KC = chol_kc<E>::value;
-    if (blockIdx.x < blockIdx.y) return;                       // workgroup-uniform
-    __shared__ __attribute__((aligned(16))) E Rs[KC * T];
-    __shared__ __attribute__((aligned(16))) E Cs[KC * T];
-    const int t = (int)threadIdx.x;
-    const int k1 = k0 + W;
-    const int r0 = k1 + (int)blockIdx.x * T, c0 = k1 + (int)blockIdx.y * T;
-    const int i0 = 4 * (t & 15), j0 = 4 * (t >> 4);
-    E acc[4][4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const int r = r0 + i0 + a, c = c0 + j0 + b;
-            acc[a][b] = (r < n && r >= c) ? A[(int64_t)c * ld + r] : ch_zero<E>();
-        }
-    const int q = t & 63, s = t >> 6;
-    for (int kb = 0; kb < W; kb += KC) {
-        if (kb) __syncthreads();                               // the previous pass has been read
-#pragma unroll
-        for (int it = 0; it < KC / 4; ++it) {
-            const int k = s + 4 * it;
-            const E *col = A + (int64_t)(k0 + kb + k) * ld;
-            Rs[k * T + q] = r0 + q < n ? col[r0 + q] : ch_zero<E>();
-            Cs[k * T + q] = c0 + q < n ? col[c0 + q] : ch_zero<E>();
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int k = 0; k < KC; ++k) {
-            E l[4], u[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) l[a] = Rs[k * T + i0 + a];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) u[b] = Cs[k * T + j0 + b];
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int a = 0; a < 4; ++a) ch_msub_cj(acc[a][b], l[a], u[b]);
-        }
-    }
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const int r = r0 + i0 + a, c = c0 + j0 + b;
-            if (r < n && r >= c) A[(int64_t)c * ld + r] = acc[a][b];
-        }
-}
-
-// acc = acc - Ar[c * ld] * x[c] over the columns c of [lo, hi), ascending: ds_walk for any element type.  lo and hi are wave-uniform; the
-// loads of the next batch are issued before the chain of the current one is evaluated.
-template <typename E>
-__device__ __forceinline__ E ch_walk(E acc, const E *__restrict__ Ar, int64_t ld, const E *__restrict__ x, int lo, int hi)
-{
-    constexpr int U = MIK_DS_U;
-    int c = lo;
-    E cur[U], nxt[U];
-    if (hi - c >= U) {
-#pragma unroll
-        for (int q = 0; q < U; ++q) cur[q] = Ar[(int64_t)(c + q) * ld];
-    }
-    while (hi - c >= U) {
-        const bool more = hi - c >= 2 * U;
-        if (more) {
-#pragma unroll
-            for (int q = 0; q < U; ++q) nxt[q] = Ar[(int64_t)(c + U + q) * ld];
-        }
-#pragma unroll
-        for (int q = 0; q < U; ++q) ch_msub(acc, cur[q], x[c + q]);
-        if (more) {
-#pragma unroll
-            for (int q = 0; q < U; ++q) cur[q] = nxt[q];
-        }
-        c += U;
-    }
-    for (; c < hi; ++c) ch_msub(acc, Ar[(int64_t)c * ld], x[c]);
-    return acc;
-}
-
-// ---- panel k0 / W of the forward substitution, launched over the rows [k0, n) in workgroups of W rows.  src is x in the first launch
-// (every row is touched there first) and t afterwards; t holds the solved entries below k0 and every other row's accumulator.
-//   every workgroup:   its rows' chains -= L[r, c] t[c] over the previous panel's columns c in [k0 - W, k0), ascending
-//   workgroup 0 only:  the diagonal block: W serial steps j, t[k0 + j] = acc / L[k0 + j, k0 + j], the rows below subtract L[r, k0 + j] t[k0 + j]
-template <typename E>
-__global__ void __launch_bounds__(MIK_DS_R) k_chol_fwd(int n, int k0, const E *__restrict__ A, int64_t ld, const E *src, E *t)
-{
-    using R = typename chol_real<E>::type;
-    const int lane = (int)threadIdx.x;
-    const int r = k0 + (int)blockIdx.x * MIK_DS_R + lane;
-    const bool live = r < n;
-    const E *Ar = A + (live ? r : k0);
-    E acc = live ? src[r] : ch_zero<E>();
-    if (k0 > 0) acc = ch_walk<E>(acc, Ar, ld, t, k0 - MIK_CH_W, k0);
-    if (blockIdx.x == 0) {
-        const int m = min(MIK_CH_W, n - k0);
-        const R d = live ? ch_re(Ar[(int64_t)r * ld]) : R(1);
-        E mine = acc;
-        for (int j0 = 0; j0 < m; j0 += MIK_DS_U) {
-            E a[MIK_DS_U];
-#pragma unroll
-            for (int q = 0; q < MIK_DS_U; ++q) a[q] = (j0 + q < m && lane > j0 + q && live) ? Ar[(int64_t)(k0 + j0 + q) * ld] : ch_zero<E>();
-#pragma unroll
-            for (int q = 0; q < MIK_DS_U; ++q) {
-                const int j = j0 + q;
-                if (j < m) {                                   // wave-uniform
-                    const E quo = ch_div(acc, d);
-                    const E wj = ch_bcast(quo, j);
-                    if (lane == j) mine = quo;
-                    E s = acc;
-                    ch_msub(s, a[q], wj);
-                    if (lane > j) acc = s;
-                }
-            }
-        }
-        acc = mine;
-    }
-    if (live) t[r] = acc;
-}
-
 // ---- panel [k0, k1) of the backward substitution, launched over the rows [0, k1) in workgroups of W rows.
 //   every workgroup:     its rows' chains -= conj(L[c, r]) t[c] over the columns c of the panel ABOVE, [k1, min(k1 + W, n)), DESCENDING
 //   the last workgroup:  the diagonal block: steps j = m - 1 ... 0, t[k0 + j] = acc / L[k0 + j, k0 + j], the rows above subtract
@@ -328,7 +170,7 @@ __device__ __forceinline__ void ch_turn_load(E (&reg)[MIK_CH_BC], const E *__res
 #pragma unroll
     for (int it = 0; it < BC; ++it) {
         const int row = r0 + h + PER * it;
-        reg[it] = (row < rows_end && c < c_hi && c > row) ? A[(int64_t)row * ld + c] : ch_zero<E>();
+        reg[it] = (row < rows_end && c < c_hi && c > row) ? A[(int64_t)row * ld + c] : de_zero<E>();
     }
 }
 template <typename E>
@@ -345,7 +187,7 @@ __device__ __forceinline__ void ch_turn_store(E *Ts, const E (&reg)[MIK_CH_BC], 
 template <typename E>
 __global__ void __launch_bounds__(MIK_DS_R) k_chol_bwd(int n, int k0, int k1, const E *__restrict__ A, int64_t ld, E *t, E *y)
 {
-    using R = typename chol_real<E>::type;
+    using R = typename de_real<E>::type;
     constexpr int BC = MIK_CH_BC;
     static_assert(64 % BC == 0 && 64 / BC * BC == 64 && BC == 32, "a wave loads 64 / BC columns of BC elements per pass, BC passes per chunk");
     __shared__ E Ts[64 * (BC + 1)];
@@ -358,8 +200,8 @@ __global__ void __launch_bounds__(MIK_DS_R) k_chol_bwd(int n, int k0, int k1, co
     // the chunks of the columns [lo, hi) in descending order, lo = k0 for the workgroup of the diagonal block and k1 for the others;
     // k1 - k0 = W whenever there are columns above k1, so every chunk lies on one side of k1
     const int lo = diag ? k0 : k1;
-    E acc = live ? t[r] : ch_zero<E>();
-    const R d = (diag && live) ? ch_re(A[(int64_t)r * ld + r]) : R(1);
+    E acc = live ? t[r] : de_zero<E>();
+    const R d = (diag && live) ? de_re(A[(int64_t)r * ld + r]) : R(1);
     E mine = acc;
     E reg[BC];
     int c_lo = lo + (hi - lo - 1) / BC * BC;
@@ -369,17 +211,9 @@ __global__ void __launch_bounds__(MIK_DS_R) k_chol_bwd(int n, int k0, int k1, co
         if (c_lo - BC >= lo) ch_turn_load<E>(reg, A, ld, r0, k1, c_lo - BC, hi, lane);
         const int cnt = min(BC, hi - c_lo);
         if (c_lo >= k1) {                                      // the panel above: its solution is in t
-            for (int c = cnt - 1; c >= 0; --c) ch_msub_lc(acc, Ts[lane * (BC + 1) + c], t[c_lo + c]);
+            for (int c = cnt - 1; c >= 0; --c) de_msub_lc(acc, Ts[lane * (BC + 1) + c], t[c_lo + c]);
         } else {                                               // the diagonal block: steps j descending
-            for (int c = cnt - 1; c >= 0; --c) {
-                const int j = c_lo + c - k0;                   // wave-uniform
-                const E quo = ch_div(acc, d);
-                const E yj = ch_bcast(quo, j);
-                if (lane == j) mine = quo;
-                E s = acc;
-                ch_msub_lc(s, Ts[lane * (BC + 1) + c], yj);
-                if (lane < j) acc = s;
-            }
+            for (int c = cnt - 1; c >= 0; --c) de_step<false, false>(acc, mine, d, de_conj(Ts[lane * (BC + 1) + c]), c_lo + c - k0, lane);      // wave-uniform j
         }
     }
     if (!diag) {

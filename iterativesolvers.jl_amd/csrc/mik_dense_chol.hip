@@ -7,35 +7,14 @@
 // stream.  A column whose pivot is not positive records its index and the remaining launches still run; create reads the flag once at the
 // end -- the factorisation's only host synchronisation.  ldiv! is ceil(n / W) launches each way; nothing is allocated per solve.
 #include "mik_internal.h"
+#include "mik_dense_factor.h"
 #include "mik_dense_chol.h"
 
-#include <new>
-
-struct mik_dense_chol {
-    mik_ctx *ctx = nullptr;
-    int dtype = MIK_F64;
-    int n = 0;
-    int64_t ld = 0;
-    void *A = nullptr;               // the caller's matrix, its lower triangle now L
-    void *work = nullptr;            // n elements: the accumulators of both substitutions
-    int *flag = nullptr;             // device: the first failing column, or a value above every column index
+struct mik_dense_chol : mik_dense_factor {    // aux: the flag -- the first failing column, or a value above every column index
     int64_t info = 0;                // 0, or the 1-based index of the first column whose pivot was not positive
-    int64_t launches_factor = 0;
-    int64_t bytes = 0;
 };
 
 namespace {
-
-void chol_free(mik_dense_chol *F)
-{
-    if (!F) return;
-    if (F->ctx) { (void)hipSetDevice(F->ctx->device); (void)hipStreamSynchronize(F->ctx->stream); }
-    for (void *p : {F->work, (void *)F->flag})
-        if (p) (void)hipFree(p);
-    delete F;
-}
-
-inline unsigned chol_grid(int count, int per) { return (unsigned)((count + per - 1) / per); }
 
 template <typename E>
 int chol_factor(mik_dense_chol *F)
@@ -45,24 +24,23 @@ int chol_factor(mik_dense_chol *F)
     const int n = F->n;
     const int64_t ld = F->ld;
     E *A = (E *)F->A;
-    MIK_HIP(ctx, hipMemsetAsync(F->flag, 0x7f, sizeof(int), st));                // 0x7f7f7f7f: above every column index
+    MIK_TRY(dense_flag_arm(ctx, F->aux));
     int64_t launches = 0;
     for (int k0 = 0; k0 < n; k0 += MIK_CH_W) {
         const int k1 = std::min(k0 + MIK_CH_W, n);
-        hipLaunchKernelGGL((k_chol_diag<E>), dim3(1), dim3(MIK_CH_THREADS), 0, st, k0, k1 - k0, A, ld, F->flag);
+        hipLaunchKernelGGL((k_chol_diag<E>), dim3(1), dim3(MIK_CH_THREADS), 0, st, k0, k1 - k0, A, ld, F->aux);
         ++launches;
         if (k1 < n) {
-            const unsigned tiles = chol_grid(n - k1, MIK_CH_T);
-            hipLaunchKernelGGL((k_chol_panel<E>), dim3(chol_grid(n - k1, MIK_CH_R)), dim3(MIK_CH_THREADS), 0, st, n, k0, k1 - k0, A, ld);
-            hipLaunchKernelGGL((k_chol_trail<E>), dim3(tiles, tiles), dim3(MIK_CH_THREADS), 0, st, n, k0, A, ld);
+            const unsigned tiles = dense_grid(n - k1, MIK_CH_T);
+            hipLaunchKernelGGL((k_chol_panel<E>), dim3(dense_grid(n - k1, MIK_CH_R)), dim3(MIK_CH_THREADS), 0, st, n, k0, k1 - k0, A, ld);
+            hipLaunchKernelGGL((k_dense_trail<E, true>), dim3(tiles, tiles), dim3(MIK_DS_THREADS), 0, st, n, k0, A, ld);
             launches += 2;
         }
         MIK_LAUNCH_CHECK(ctx);
     }
     F->launches_factor = launches;
     int first = 0;
-    MIK_HIP(ctx, hipMemcpyAsync(&first, F->flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    MIK_HIP(ctx, hipStreamSynchronize(st));
+    MIK_TRY(dense_flag_read(ctx, F->aux, &first));
     F->info = first < n ? (int64_t)first + 1 : 0;
     return MIK_OK;
 }
@@ -76,7 +54,7 @@ int chol_solve_dev(mik_dense_chol *F, E *y, const E *x)
     const E *A = (const E *)F->A;
     E *t = (E *)F->work;
     for (int k0 = 0; k0 < n; k0 += MIK_CH_W)
-        hipLaunchKernelGGL((k_chol_fwd<E>), dim3(chol_grid(n - k0, MIK_DS_R)), dim3(MIK_DS_R), 0, st, n, k0, A, F->ld, k0 ? (const E *)t : x, t);
+        hipLaunchKernelGGL((k_dense_fwd<E, false>), dim3(dense_grid(n - k0, MIK_DS_R)), dim3(MIK_DS_R), 0, st, n, k0, A, F->ld, k0 ? (const E *)t : x, t);
     for (int k0 = (n - 1) / MIK_CH_W * MIK_CH_W; k0 >= 0; k0 -= MIK_CH_W)
         hipLaunchKernelGGL((k_chol_bwd<E>), dim3((unsigned)(k0 / MIK_DS_R + 1)), dim3(MIK_DS_R), 0, st, n, k0, std::min(k0 + MIK_CH_W, n), A, F->ld, t, y);
     MIK_LAUNCH_CHECK(ctx);
@@ -92,31 +70,15 @@ extern "C" int mik_dense_chol_create(mik_ctx *ctx, void *A, int64_t n, int64_t l
     *out = nullptr;
     if (dtype != MIK_F64 && dtype != MIK_F32 && dtype != MIK_C64 && dtype != MIK_C32)
         return mik_fail(ctx, MIK_ERR_INVALID, "mik_dense_chol_create: dtype must be MIK_F64, MIK_F32, MIK_C64 or MIK_C32");
-    if (n < 1 || ld < n) return mik_fail(ctx, MIK_ERR_MISMATCH, "mik_dense_chol_create: n = %lld, ld = %lld (need 1 <= n <= ld)", (long long)n, (long long)ld);
-    if (n > (int64_t)std::numeric_limits<int>::max() - MIK_CH_W) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_dense_chol_create: n >= 2^31 - 64");
-    mik_dense_chol *F = new (std::nothrow) mik_dense_chol();
-    if (!F) return mik_fail(ctx, MIK_ERR_NOMEM, "mik_dense_chol_create: host allocation failed");
-    F->ctx = ctx; F->dtype = dtype; F->n = (int)n; F->ld = ld; F->A = A;
-    (void)hipSetDevice(ctx->device);
-    const size_t vec = std::max<size_t>((size_t)n * mik_dtype_size(dtype), 16);
-    auto alloc = [&]() -> int {
-        MIK_HIP(ctx, hipMalloc(&F->work, vec));
-        MIK_HIP(ctx, hipMalloc((void **)&F->flag, 16));
-        return MIK_OK;
-    };
-    int rc = alloc();
-    F->bytes = (int64_t)(vec + 16);
-    if (rc == MIK_OK)
-        rc = dtype == MIK_F64   ? chol_factor<double>(F)
-             : dtype == MIK_F32 ? chol_factor<float>(F)
-             : dtype == MIK_C64 ? chol_factor<chol_cx<double>>(F)
-                                : chol_factor<chol_cx<float>>(F);
+    mik_dense_chol *F = nullptr;
+    int rc = dense_new(ctx, "mik_dense_chol_create", A, n, ld, dtype, false, &F);
+    if (rc == MIK_OK) rc = dense_dispatch<true>(dtype, [&](auto e) { return chol_factor<decltype(e)>(F); });
     if (rc == MIK_OK && F->info && check) {
         if (failed_col) *failed_col = F->info;
         rc = mik_fail(ctx, MIK_ERR_SINGULAR, "mik_dense_chol_create: PosDefException(%lld): the matrix is not positive definite, the pivot of that column is not positive",
                       (long long)F->info);
     }
-    if (rc != MIK_OK) { chol_free(F); return rc; }
+    if (rc != MIK_OK) { dense_free(F); return rc; }
     if (failed_col) *failed_col = F->info;
     *out = F;
     return MIK_OK;
@@ -124,7 +86,7 @@ extern "C" int mik_dense_chol_create(mik_ctx *ctx, void *A, int64_t n, int64_t l
 
 extern "C" int mik_dense_chol_destroy(mik_dense_chol *F)
 {
-    chol_free(F);
+    dense_free(F);
     return MIK_OK;
 }
 
@@ -132,16 +94,8 @@ extern "C" int mik_dense_chol_solve(mik_dense_chol *F, void *y, const void *x)
 {
     if (!F || !y || !x) return MIK_ERR_INVALID;
     if (F->info) return mik_fail(F->ctx, MIK_ERR_INVALID, "mik_dense_chol_solve: the factorisation failed at column %lld (PosDefException)", (long long)F->info);
-    const size_t es = mik_dtype_size(F->dtype), bytes = (size_t)F->n * es, all = (size_t)F->ld * (size_t)F->n * es;
-    if (y != x && mik_overlap(y, bytes, x, bytes)) return mik_fail(F->ctx, MIK_ERR_INVALID, "mik_dense_chol_solve: y and x overlap without being equal");
-    if (mik_overlap(y, bytes, F->A, all) || mik_overlap(x, bytes, F->A, all)) return mik_fail(F->ctx, MIK_ERR_INVALID, "mik_dense_chol_solve: a vector overlaps the factors");
-    (void)hipSetDevice(F->ctx->device);
-    switch (F->dtype) {
-    case MIK_F64: return chol_solve_dev<double>(F, (double *)y, (const double *)x);
-    case MIK_F32: return chol_solve_dev<float>(F, (float *)y, (const float *)x);
-    case MIK_C64: return chol_solve_dev<chol_cx<double>>(F, (chol_cx<double> *)y, (const chol_cx<double> *)x);
-    default: return chol_solve_dev<chol_cx<float>>(F, (chol_cx<float> *)y, (const chol_cx<float> *)x);
-    }
+    MIK_TRY(dense_check_solve(F, "mik_dense_chol_solve", y, x));
+    return dense_dispatch<true>(F->dtype, [&](auto e) { return chol_solve_dev(F, (decltype(e) *)y, (const decltype(e) *)x); });
 }
 
 extern "C" int mik_dense_chol_ldiv_fn(void *user, void *y, const void *x) { return mik_dense_chol_solve((mik_dense_chol *)user, y, x); }

@@ -17,26 +17,25 @@
 //                the search of column j + 1 from the values it has just stored
 //   k_lu_swap    the panel's interchanges on the columns left and right of it: a lane owns a column and applies them in order, in LDS
 //   k_lu_strip   U12 = L11^-1 A12: a lane owns a column, its W values in registers, L11 in LDS, k ascending
-//   k_lu_trail   A22[i,c] -= L21[i,k] * U12[k,c], k ascending: TR x TC tiles, L21 and U12 tiles in LDS, a 4 x 4 register block per lane
 //   k_lu_gather  w[i] = x[perm[i]]: the interchanges of ldiv!
-//   k_lu_fwd     one panel of the forward substitution (k_ds_panel's shape without the division)
-//   k_lu_bwd     one panel of the backward substitution, its mirror image
+//   k_lu_bwd     one panel of the backward substitution
+// and, from csrc/mik_dense_elem.h, where the pieces the dense kernels share are written once (the walk de_walk, the serial step de_step):
+//   k_dense_trail<T, false>  A22[i,c] -= L21[i,k] * U12[k,c], k ascending: TR x TC tiles, L21 and U12 tiles in LDS, a 4 x 4 register block per lane
+//   k_dense_fwd<T, true>     one panel of the forward substitution with the unit-lower factor
 // Every dependency between workgroups is a kernel boundary; nothing indexes memory through a DATA value (ipiv is clamped to [j, n)
 // where it is produced), so a singular or non-finite matrix cannot fault.  Non-finite data follow the loop too: the pivot search treats a
 // NaN as the loop's comparisons do (lu_key), and everything else is the same operations on the same operands in the same order.
 #pragma once
 #include "mik_internal.h"
-#include "mik_dense_stationary.h"
+#include "mik_dense_elem.h"
 
 #include <climits>
 
-constexpr int MIK_LU_W = 64;            // panel width; equals MIK_DS_W (the substitution panels are the factorisation's)
+constexpr int MIK_LU_W = MIK_DS_W;      // panel width: the substitution panels are the factorisation's
 constexpr int MIK_LU_R = 256;           // rows per workgroup of the pivot search and of the panel update
-constexpr int MIK_LU_TR = 64;           // tile rows of the trailing update
-constexpr int MIK_LU_TC = 64;           // tile columns of the trailing update
-constexpr int MIK_LU_THREADS = 256;     // workgroup of the trailing update: 16 x 16 lanes, 4 x 4 elements each
-static_assert(MIK_LU_W == MIK_DS_W && MIK_DS_R == MIK_DS_W, "the substitution kernels take one panel per 64-row workgroup");
-static_assert(MIK_LU_TR == 64 && MIK_LU_TC == 64 && MIK_LU_THREADS == 256 && MIK_LU_W == 64, "the tile loaders are written for these sizes");
+constexpr int MIK_LU_TR = MIK_DS_T;     // tile rows of the trailing update
+constexpr int MIK_LU_TC = MIK_DS_T;     // tile columns of the trailing update
+static_assert(MIK_LU_W == 64, "k_lu_swap and k_lu_strip are written for this size");
 
 // What the row of the value a = |A[r,j]| offers to the search of column j.  The loop starts with best = |A[j,j]| and replaces it only by a
 // strictly larger value, so a NaN in the FIRST searched row is never replaced (the pivot stays in row j, and best, a NaN, is not zero),
@@ -233,105 +232,11 @@ __global__ void __launch_bounds__(64) k_lu_strip(int n, int k0, T *A, int64_t ld
     }
 }
 
-template <typename T> struct lu_tile { static constexpr int US = MIK_LU_TC + 16 / (int)sizeof(T); };   // row pitch of the U12 tile: 16-byte rows, spread banks
-
-// A22 -= L21 U12 for the full panel [k0, k0 + W): tile (blockIdx.x, blockIdx.y) of TR x TC elements from (k0 + W, k0 + W).
-template <typename T>
-__global__ void __launch_bounds__(MIK_LU_THREADS) k_lu_trail(int n, int k0, T *A, int64_t ld)
-{
-    constexpr int W = MIK_LU_W, TR = MIK_LU_TR, TC = MIK_LU_TC, US = lu_tile<T>::US;
-    __shared__ __attribute__((aligned(16))) T Ls[W * TR];      // Ls[k * TR + i] = L21[r0 + i, k0 + k]
-    __shared__ __attribute__((aligned(16))) T Us[W * US];      // Us[k * US + c] = U12[k0 + k, c0 + c]
-    const int t = (int)threadIdx.x;
-    const int k1 = k0 + W;
-    const int r0 = k1 + (int)blockIdx.x * TR, c0 = k1 + (int)blockIdx.y * TC;
-    const int i0 = 4 * (t & 15), j0 = 4 * (t >> 4);
-    T acc[4][4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const int r = r0 + i0 + a, c = c0 + j0 + b;
-            acc[a][b] = (r < n && c < n) ? A[(int64_t)c * ld + r] : T(0);
-        }
-    {
-        const int q = t & 63, s = t >> 6;
-        const int r = r0 + q;
-#pragma unroll
-        for (int it = 0; it < W / 4; ++it) {
-            const int k = s + 4 * it;
-            Ls[k * TR + q] = r < n ? A[(int64_t)(k0 + k) * ld + r] : T(0);
-        }
-#pragma unroll
-        for (int it = 0; it < TC / 4; ++it) {
-            const int c = s + 4 * it;
-            Us[q * US + c] = c0 + c < n ? A[(int64_t)(c0 + c) * ld + k0 + q] : T(0);
-        }
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int k = 0; k < W; ++k) {
-        T l[4], u[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) l[a] = Ls[k * TR + i0 + a];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) u[b] = Us[k * US + j0 + b];
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const T p = l[a] * u[b];
-                acc[a][b] = acc[a][b] - p;
-            }
-    }
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const int r = r0 + i0 + a, c = c0 + j0 + b;
-            if (r < n && c < n) A[(int64_t)c * ld + r] = acc[a][b];
-        }
-}
-
 template <typename T>
 __global__ void __launch_bounds__(256) k_lu_gather(int n, const int *__restrict__ perm, const T *__restrict__ x, T *__restrict__ w)
 {
     const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (i < n) w[i] = x[perm[i]];
-}
-
-// Panel k0 / W of the forward substitution with the unit-lower factor, launched over the rows [k0, n) in workgroups of W rows.  t holds
-// the solved entries below k0 and every other row's accumulator.
-//   every workgroup:   t-chain of its rows -= L[r, c] * t[c] over the previous panel's columns c in [k0 - W, k0), ascending
-//   workgroup 0 only:  its rows are the diagonal block: W serial steps j, t[k0 + j] is final, the rows below subtract L[r, k0 + j] * t[k0 + j]
-template <typename T>
-__global__ void __launch_bounds__(MIK_DS_R) k_lu_fwd(int n, int k0, const T *__restrict__ A, int64_t ld, T *t)
-{
-    const int lane = (int)threadIdx.x;
-    const int r = k0 + (int)blockIdx.x * MIK_DS_R + lane;
-    const bool live = r < n;
-    const T *Ar = A + (live ? r : k0);
-    T acc = live ? t[r] : T(0);
-    if (k0 > 0) acc = ds_walk<T, true, MIK_DS_ALL>(acc, Ar, ld, t, k0 - MIK_LU_W, k0, r);
-    if (blockIdx.x == 0) {
-        const int m = min(MIK_LU_W, n - k0);
-        for (int j0 = 0; j0 < m; j0 += MIK_DS_U) {
-            T a[MIK_DS_U];
-#pragma unroll
-            for (int q = 0; q < MIK_DS_U; ++q) a[q] = j0 + q < m ? Ar[(int64_t)(k0 + j0 + q) * ld] : T(0);
-#pragma unroll
-            for (int q = 0; q < MIK_DS_U; ++q) {
-                const int j = j0 + q;
-                if (j < m) {                                   // wave-uniform
-                    const T xj = ds_bcast(acc, j);
-                    const T p = a[q] * xj;
-                    const T s = acc - p;
-                    acc = lane > j ? s : acc;
-                }
-            }
-        }
-    }
-    if (live) t[r] = acc;
 }
 
 // Panel [k0, k1) of the backward substitution with the upper factor, launched over the rows [0, k1) in workgroups of W rows.
@@ -346,7 +251,7 @@ __global__ void __launch_bounds__(MIK_DS_R) k_lu_bwd(int n, int k0, int k1, cons
     const bool live = r < k1;
     const T *Ar = A + (live ? r : 0);
     T acc = live ? t[r] : T(0);
-    if (k1 < n) acc = ds_walk<T, false, MIK_DS_ALL>(acc, Ar, ld, t, k1, min(k1 + MIK_LU_W, n), r);
+    if (k1 < n) acc = de_walk<T, false, MIK_DS_ALL>(acc, Ar, ld, t, k1, min(k1 + MIK_LU_W, n), r);
     if ((int)blockIdx.x * MIK_DS_R != k0) {
         if (live) t[r] = acc;
         return;
@@ -360,15 +265,8 @@ __global__ void __launch_bounds__(MIK_DS_R) k_lu_bwd(int n, int k0, int k1, cons
         for (int q = 0; q < MIK_DS_U; ++q) a[q] = j0 + q < m ? Ar[(int64_t)(k1 - 1 - j0 - q) * ld] : T(0);
 #pragma unroll
         for (int q = 0; q < MIK_DS_U; ++q) {
-            const int j = m - 1 - j0 - q;
-            if (j >= 0) {                                      // wave-uniform
-                const T quo = acc / d;
-                const T xj = ds_bcast(quo, j);
-                if (lane == j) mine = quo;
-                const T p = a[q] * xj;
-                const T s = acc - p;
-                acc = lane < j ? s : acc;
-            }
+            const int j = m - 1 - j0 - q;                  // tested as j >= 0: shared with the loads' bound the test becomes a lane mask
+            if (j >= 0) de_step<false, false>(acc, mine, d, a[q], j, lane);                       // wave-uniform
         }
     }
     if (live) { t[r] = mine; y[r] = mine; }

@@ -11,37 +11,17 @@
 // remaining launches still run; create reads the flag (and the pivots) once at the end -- the factorisation's only host synchronisation.
 // ldiv! is a gather into the handle's work vector and ceil(n / W) launches each way; nothing is allocated per solve.
 #include "mik_internal.h"
+#include "mik_dense_factor.h"
 #include "mik_dense_lu.h"
 
-#include <new>
 #include <vector>
 
-struct mik_dense_lu {
-    mik_ctx *ctx = nullptr;
-    int dtype = MIK_F64;
-    int n = 0;
-    int64_t ld = 0;
-    void *A = nullptr;               // the caller's matrix, now L\U
-    void *work = nullptr;            // n elements: the permuted right-hand side, then the accumulators of both substitutions
-    int *perm = nullptr;             // device: the interchanges as one gather
+struct mik_dense_lu : mik_dense_factor {      // aux: the interchanges as one gather, n integers
     std::vector<int> ipiv;           // host, 0-based
     std::vector<int> perm_host;
-    int64_t launches_factor = 0;
-    int64_t bytes = 0;
 };
 
 namespace {
-
-void lu_free(mik_dense_lu *F)
-{
-    if (!F) return;
-    if (F->ctx) { (void)hipSetDevice(F->ctx->device); (void)hipStreamSynchronize(F->ctx->stream); }
-    for (void *p : {F->work, (void *)F->perm})
-        if (p) (void)hipFree(p);
-    delete F;
-}
-
-inline unsigned lu_grid(int count, int per) { return (unsigned)((count + per - 1) / per); }
 
 struct lu_scratch {                  // device memory of the factorisation only
     void *pval = nullptr;
@@ -62,35 +42,35 @@ int lu_factor(mik_dense_lu *F, int64_t *singular_col)
     const int64_t ld = F->ld;
     T *A = (T *)F->A;
     lu_scratch s;
-    const size_t nparts = lu_grid(n, MIK_LU_R);
+    const size_t nparts = dense_grid(n, MIK_LU_R);
     MIK_HIP(ctx, hipMalloc(&s.pval, std::max<size_t>(nparts * sizeof(T), 16)));
     MIK_HIP(ctx, hipMalloc((void **)&s.prow, std::max<size_t>(nparts * sizeof(int), 16)));
     MIK_HIP(ctx, hipMalloc((void **)&s.ipiv, std::max<size_t>((size_t)n * sizeof(int), 16)));
     MIK_HIP(ctx, hipMalloc((void **)&s.flag, 16));
-    MIK_HIP(ctx, hipMemsetAsync(s.flag, 0x7f, sizeof(int), st));                 // 0x7f7f7f7f: above every column index
+    MIK_TRY(dense_flag_arm(ctx, s.flag));
     T *pval = (T *)s.pval;
     int64_t launches = 0;
     for (int k0 = 0; k0 < n; k0 += MIK_LU_W) {
         const int k1 = std::min(k0 + MIK_LU_W, n);
-        hipLaunchKernelGGL((k_lu_search<T>), dim3(lu_grid(n - k0, MIK_LU_R)), dim3(MIK_LU_R), 0, st, n, k0, (const T *)A, ld, pval, s.prow);
+        hipLaunchKernelGGL((k_lu_search<T>), dim3(dense_grid(n - k0, MIK_LU_R)), dim3(MIK_LU_R), 0, st, n, k0, (const T *)A, ld, pval, s.prow);
         ++launches;
         for (int j = k0; j < k1; ++j) {
-            hipLaunchKernelGGL((k_lu_pick<T>), dim3(1), dim3(64), 0, st, n, j, k0, k1, A, ld, (int)lu_grid(n - j, MIK_LU_R), (const T *)pval,
+            hipLaunchKernelGGL((k_lu_pick<T>), dim3(1), dim3(64), 0, st, n, j, k0, k1, A, ld, (int)dense_grid(n - j, MIK_LU_R), (const T *)pval,
                                (const int *)s.prow, s.ipiv, s.flag);
             ++launches;
             if (j + 1 < n) {
-                hipLaunchKernelGGL((k_lu_update<T>), dim3(lu_grid(n - j - 1, MIK_LU_R)), dim3(MIK_LU_R), 0, st, n, j, k1, A, ld, pval, s.prow);
+                hipLaunchKernelGGL((k_lu_update<T>), dim3(dense_grid(n - j - 1, MIK_LU_R)), dim3(MIK_LU_R), 0, st, n, j, k1, A, ld, pval, s.prow);
                 ++launches;
             }
         }
         if (n > k1 - k0) {
-            hipLaunchKernelGGL((k_lu_swap<T>), dim3(lu_grid(n - (k1 - k0), 64)), dim3(64), 0, st, n, k0, k1, A, ld, (const int *)s.ipiv);
+            hipLaunchKernelGGL((k_lu_swap<T>), dim3(dense_grid(n - (k1 - k0), 64)), dim3(64), 0, st, n, k0, k1, A, ld, (const int *)s.ipiv);
             ++launches;
         }
         if (k1 < n) {
-            hipLaunchKernelGGL((k_lu_strip<T>), dim3(lu_grid(n - k1, 64)), dim3(64), 0, st, n, k0, A, ld);
-            const unsigned tr = lu_grid(n - k1, MIK_LU_TR), tc = lu_grid(n - k1, MIK_LU_TC);
-            hipLaunchKernelGGL((k_lu_trail<T>), dim3(tr, tc), dim3(MIK_LU_THREADS), 0, st, n, k0, A, ld);
+            hipLaunchKernelGGL((k_lu_strip<T>), dim3(dense_grid(n - k1, 64)), dim3(64), 0, st, n, k0, A, ld);
+            const unsigned tr = dense_grid(n - k1, MIK_LU_TR), tc = dense_grid(n - k1, MIK_LU_TC);
+            hipLaunchKernelGGL((k_dense_trail<T, false>), dim3(tr, tc), dim3(MIK_DS_THREADS), 0, st, n, k0, A, ld);
             launches += 2;
         }
         MIK_LAUNCH_CHECK(ctx);
@@ -98,9 +78,8 @@ int lu_factor(mik_dense_lu *F, int64_t *singular_col)
     F->launches_factor = launches;
     int first = 0;
     F->ipiv.resize((size_t)n);
-    MIK_HIP(ctx, hipMemcpyAsync(&first, s.flag, sizeof(int), hipMemcpyDeviceToHost, st));
     MIK_HIP(ctx, hipMemcpyAsync(F->ipiv.data(), s.ipiv, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
-    MIK_HIP(ctx, hipStreamSynchronize(st));
+    MIK_TRY(dense_flag_read(ctx, s.flag, &first));
     if (first < n) {
         if (singular_col) *singular_col = (int64_t)first + 1;
         return mik_fail(ctx, MIK_ERR_SINGULAR, "mik_dense_lu_create: SingularException(%d): zero pivot column", first + 1);
@@ -108,19 +87,8 @@ int lu_factor(mik_dense_lu *F, int64_t *singular_col)
     F->perm_host.resize((size_t)n);
     for (int i = 0; i < n; ++i) F->perm_host[(size_t)i] = i;
     for (int j = 0; j < n; ++j) std::swap(F->perm_host[(size_t)j], F->perm_host[(size_t)F->ipiv[(size_t)j]]);
-    MIK_HIP(ctx, hipMemcpyAsync(F->perm, F->perm_host.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
+    MIK_HIP(ctx, hipMemcpyAsync(F->aux, F->perm_host.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
     return MIK_OK;
-}
-
-int lu_create(mik_dense_lu *F, int64_t *singular_col)
-{
-    mik_ctx *ctx = F->ctx;
-    (void)hipSetDevice(ctx->device);
-    const size_t vec = std::max<size_t>((size_t)F->n * mik_dtype_size(F->dtype), 16), idx = std::max<size_t>((size_t)F->n * sizeof(int), 16);
-    MIK_HIP(ctx, hipMalloc(&F->work, vec));
-    MIK_HIP(ctx, hipMalloc((void **)&F->perm, idx));
-    F->bytes = (int64_t)(vec + idx);
-    return F->dtype == MIK_F64 ? lu_factor<double>(F, singular_col) : lu_factor<float>(F, singular_col);
 }
 
 template <typename T>
@@ -131,9 +99,9 @@ int lu_solve_dev(mik_dense_lu *F, T *y, const T *x)
     const int n = F->n;
     const T *A = (const T *)F->A;
     T *t = (T *)F->work;
-    hipLaunchKernelGGL((k_lu_gather<T>), dim3(lu_grid(n, 256)), dim3(256), 0, st, n, (const int *)F->perm, x, t);
+    hipLaunchKernelGGL((k_lu_gather<T>), dim3(dense_grid(n, 256)), dim3(256), 0, st, n, (const int *)F->aux, x, t);
     for (int k0 = 0; k0 < n; k0 += MIK_LU_W)
-        hipLaunchKernelGGL((k_lu_fwd<T>), dim3(lu_grid(n - k0, MIK_DS_R)), dim3(MIK_DS_R), 0, st, n, k0, A, F->ld, t);
+        hipLaunchKernelGGL((k_dense_fwd<T, true>), dim3(dense_grid(n - k0, MIK_DS_R)), dim3(MIK_DS_R), 0, st, n, k0, A, F->ld, (const T *)t, t);
     for (int k0 = (n - 1) / MIK_LU_W * MIK_LU_W; k0 >= 0; k0 -= MIK_LU_W)
         hipLaunchKernelGGL((k_lu_bwd<T>), dim3((unsigned)(k0 / MIK_DS_R + 1)), dim3(MIK_DS_R), 0, st, n, k0, std::min(k0 + MIK_LU_W, n), A, F->ld, t, y);
     MIK_LAUNCH_CHECK(ctx);
@@ -151,20 +119,17 @@ extern "C" int mik_dense_lu_create(mik_ctx *ctx, void *A, int64_t n, int64_t ld,
         return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_dense_lu_create: lu is not built for %s (it needs |re| + |im| pivots and a complex division on the device)",
                         dtype == MIK_C64 ? "ComplexF64 (MIK_C64)" : "ComplexF32 (MIK_C32)");
     if (dtype != MIK_F64 && dtype != MIK_F32) return mik_fail(ctx, MIK_ERR_INVALID, "mik_dense_lu_create: dtype must be MIK_F64 or MIK_F32");
-    if (n < 1 || ld < n) return mik_fail(ctx, MIK_ERR_MISMATCH, "mik_dense_lu_create: n = %lld, ld = %lld (need 1 <= n <= ld)", (long long)n, (long long)ld);
-    if (n > (int64_t)std::numeric_limits<int>::max() - MIK_LU_W) return mik_fail(ctx, MIK_ERR_NOTIMPL, "mik_dense_lu_create: n >= 2^31 - 64");
-    mik_dense_lu *F = new (std::nothrow) mik_dense_lu();
-    if (!F) return mik_fail(ctx, MIK_ERR_NOMEM, "mik_dense_lu_create: host allocation failed");
-    F->ctx = ctx; F->dtype = dtype; F->n = (int)n; F->ld = ld; F->A = A;
-    const int rc = lu_create(F, singular_col);
-    if (rc != MIK_OK) { lu_free(F); return rc; }
+    mik_dense_lu *F = nullptr;
+    int rc = dense_new(ctx, "mik_dense_lu_create", A, n, ld, dtype, true, &F);
+    if (rc == MIK_OK) rc = dense_dispatch<false>(dtype, [&](auto e) { return lu_factor<decltype(e)>(F, singular_col); });
+    if (rc != MIK_OK) { dense_free(F); return rc; }
     *out = F;
     return MIK_OK;
 }
 
 extern "C" int mik_dense_lu_destroy(mik_dense_lu *F)
 {
-    lu_free(F);
+    dense_free(F);
     return MIK_OK;
 }
 
@@ -178,12 +143,8 @@ extern "C" int mik_dense_lu_ipiv(const mik_dense_lu *F, int64_t *ipiv)
 extern "C" int mik_dense_lu_solve(mik_dense_lu *F, void *y, const void *x)
 {
     if (!F || !y || !x) return MIK_ERR_INVALID;
-    const size_t bytes = (size_t)F->n * mik_dtype_size(F->dtype);
-    if (y != x && mik_overlap(y, bytes, x, bytes)) return mik_fail(F->ctx, MIK_ERR_INVALID, "mik_dense_lu_solve: y and x overlap without being equal");
-    if (mik_overlap(y, bytes, F->A, (size_t)F->ld * (size_t)F->n * mik_dtype_size(F->dtype)) || mik_overlap(x, bytes, F->A, (size_t)F->ld * (size_t)F->n * mik_dtype_size(F->dtype)))
-        return mik_fail(F->ctx, MIK_ERR_INVALID, "mik_dense_lu_solve: a vector overlaps the factors");
-    (void)hipSetDevice(F->ctx->device);
-    return F->dtype == MIK_F64 ? lu_solve_dev<double>(F, (double *)y, (const double *)x) : lu_solve_dev<float>(F, (float *)y, (const float *)x);
+    MIK_TRY(dense_check_solve(F, "mik_dense_lu_solve", y, x));
+    return dense_dispatch<false>(F->dtype, [&](auto e) { return lu_solve_dev(F, (decltype(e) *)y, (const decltype(e) *)x); });
 }
 
 extern "C" int mik_dense_lu_ldiv_fn(void *user, void *y, const void *x) { return mik_dense_lu_solve((mik_dense_lu *)user, y, x); }

@@ -3,7 +3,9 @@
 // The reference's column loops give every row ONE serial order of subtractions, acc = acc - (A[r,c] * x[c]) with the product and the
 // difference rounded on their own (the library is built -ffp-contract=off).  A lane therefore owns a row and walks its columns in that
 // order; a row's chain is never split, so a sweep has n-fold parallelism and no more.  The 64 lanes of a wave read 64 consecutive rows
-// of one column (one coalesced line), x[c] is wave-uniform, and two batches of MIK_DS_U column loads are in flight per lane.
+// of one column (one coalesced line), x[c] is wave-uniform, and two batches of MIK_DS_U column loads are in flight per lane.  The walk
+// (de_walk), the broadcast (ds_bcast) and the panel shape (MIK_DS_W, MIK_DS_R, MIK_DS_U) are those of csrc/mik_dense_elem.h, shared with
+// the dense LU and Cholesky.
 //   k_ds_row    row-owned sweep: Jacobi (:53-69), the upper phase of Gauss-Seidel / SOR / SSOR (:113-119, :172-178, :232-238), the
 //               backward half of SSOR (:247-260)
 //   k_ds_panel  one panel of the forward substitution (:121-126, :180-185, :240-245): subtract the previous panel's columns from the
@@ -11,58 +13,7 @@
 //   k_ds_check_diag  check_diag (:6-12)
 #pragma once
 #include "mik_internal.h"
-
-constexpr int MIK_DS_W = 64;      // columns per panel of the forward substitution
-constexpr int MIK_DS_R = 64;      // rows per workgroup (one wave: a row sweep over n rows spreads over n / 64 compute units)
-constexpr int MIK_DS_U = 16;      // column loads per batch; two batches in flight
-
-enum { MIK_DS_ALL = 0, MIK_DS_BELOW = 1, MIK_DS_ABOVE = 2, MIK_DS_OFFDIAG = 3 };   // which columns c of [lo, hi) row r takes: all, c < r, c > r, c != r
-
-template <int PRED> __device__ __forceinline__ bool ds_take(int c, int r)
-{
-    return PRED == MIK_DS_ALL || (PRED == MIK_DS_BELOW && c < r) || (PRED == MIK_DS_ABOVE && c > r) || (PRED == MIK_DS_OFFDIAG && c != r);
-}
-
-// acc = acc - (Ar[c * ld] * x[c]) over the columns c of [lo, hi) that PRED admits, ascending or descending.  Ar = A + r; lo and hi are
-// wave-uniform.  The loads of the next batch are issued before the chain of the current one is evaluated.
-template <typename T, bool ASC, int PRED>
-__device__ __forceinline__ T ds_walk(T acc, const T *__restrict__ Ar, int64_t ld, const T *__restrict__ x, int lo, int hi, int r)
-{
-    constexpr int U = MIK_DS_U;
-    int left = hi - lo;
-    int c = ASC ? lo : hi - 1;                      // first column of the current batch, in walking order
-    T cur[U], nxt[U];
-    if (left >= U) {
-#pragma unroll
-        for (int q = 0; q < U; ++q) cur[q] = Ar[(int64_t)(ASC ? c + q : c - q) * ld];
-    }
-    while (left >= U) {
-        const int cn = ASC ? c + U : c - U;
-        if (left >= 2 * U) {
-#pragma unroll
-            for (int q = 0; q < U; ++q) nxt[q] = Ar[(int64_t)(ASC ? cn + q : cn - q) * ld];
-        }
-#pragma unroll
-        for (int q = 0; q < U; ++q) {
-            const int cc = ASC ? c + q : c - q;
-            const T p = cur[q] * x[cc];
-            const T s = acc - p;
-            acc = ds_take<PRED>(cc, r) ? s : acc;
-        }
-        if (left >= 2 * U) {
-#pragma unroll
-            for (int q = 0; q < U; ++q) cur[q] = nxt[q];
-        }
-        c = cn;
-        left -= U;
-    }
-    for (; left > 0; --left, c += ASC ? 1 : -1) {
-        const T p = Ar[(int64_t)c * ld] * x[c];
-        const T s = acc - p;
-        acc = ds_take<PRED>(c, r) ? s : acc;
-    }
-    return acc;
-}
+#include "mik_dense_elem.h"
 
 // x + omega * (q - x) with Julia's types (:181, :241, :259): the inner difference in T, the product and the sum in S, one rounding at
 // the store.  S is double for Float32 data with a Float64 omega, else T.
@@ -72,18 +23,6 @@ __device__ __forceinline__ T ds_relax(T xo, T q, S omega)
     const T dq = q - xo;
     const S w = omega * (S)dq;
     return (T)((S)xo + w);
-}
-
-// the value lane j holds, in every lane; j is wave-uniform, so this is a register read (v_readlane), not a trip through the LDS crossbar
-__device__ __forceinline__ float ds_bcast(float v, int j)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
-}
-__device__ __forceinline__ double ds_bcast(double v, int j)
-{
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, j), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), j);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
 enum { MIK_DS_JACOBI = 0, MIK_DS_UPPER = 1, MIK_DS_BACKWARD = 2 };
@@ -103,20 +42,20 @@ __global__ void __launch_bounds__(MIK_DS_R) k_ds_row(int n, const T *__restrict_
     const T *Ar = A + r;
     T acc = b[r];
     if (MODE == MIK_DS_JACOBI) {
-        acc = ds_walk<T, true, MIK_DS_ALL>(acc, Ar, ld, x, 0, r0, r);
-        acc = ds_walk<T, true, MIK_DS_OFFDIAG>(acc, Ar, ld, x, r0, r1, r);
-        acc = ds_walk<T, true, MIK_DS_ALL>(acc, Ar, ld, x, r1, n, r);
+        acc = de_walk<T, true, MIK_DS_ALL>(acc, Ar, ld, x, 0, r0, r);
+        acc = de_walk<T, true, MIK_DS_OFFDIAG>(acc, Ar, ld, x, r0, r1, r);
+        acc = de_walk<T, true, MIK_DS_ALL>(acc, Ar, ld, x, r1, n, r);
         acc_out[r] = acc;
         out[r] = acc / Ar[(int64_t)r * ld];
     } else if (MODE == MIK_DS_UPPER) {
-        acc = ds_walk<T, true, MIK_DS_ABOVE>(acc, Ar, ld, x, r0, r1, r);
-        acc = ds_walk<T, true, MIK_DS_ALL>(acc, Ar, ld, x, r1, n, r);
+        acc = de_walk<T, true, MIK_DS_ABOVE>(acc, Ar, ld, x, r0, r1, r);
+        acc = de_walk<T, true, MIK_DS_ALL>(acc, Ar, ld, x, r1, n, r);
         acc_out[r] = acc;
     } else {
-        acc = ds_walk<T, false, MIK_DS_BELOW>(acc, Ar, ld, x, r0, r1, r);
-        acc = ds_walk<T, false, MIK_DS_ALL>(acc, Ar, ld, x, 0, r0, r);
-        acc = ds_walk<T, false, MIK_DS_ALL>(acc, Ar, ld, x, r1, n, r);
-        acc = ds_walk<T, false, MIK_DS_ABOVE>(acc, Ar, ld, x, r0, r1, r);
+        acc = de_walk<T, false, MIK_DS_BELOW>(acc, Ar, ld, x, r0, r1, r);
+        acc = de_walk<T, false, MIK_DS_ALL>(acc, Ar, ld, x, 0, r0, r);
+        acc = de_walk<T, false, MIK_DS_ALL>(acc, Ar, ld, x, r1, n, r);
+        acc = de_walk<T, false, MIK_DS_ABOVE>(acc, Ar, ld, x, r0, r1, r);
         acc_out[r] = acc;
         out[r] = ds_relax<T, S>(x[r], acc / Ar[(int64_t)r * ld], omega);
     }
@@ -128,6 +67,8 @@ __global__ void __launch_bounds__(MIK_DS_R) k_ds_row(int n, const T *__restrict_
 //   workgroup 0 only:  its rows are the diagonal block.  W serial steps j: x[k0 + j] = t / d (RELAX: relax(x_old, t / d)), broadcast,
 //                      the rows below subtract A[r, k0 + j] * x[k0 + j].  t[r] keeps the accumulator the division read (the reference's tmp).
 // No workgroup waits for another one; the launches of a sweep follow each other on the stream.
+// The serial loop is de_step's with two additions -- the quotient is relaxed before it is broadcast, and t keeps the accumulator the
+// division read -- which de_step could only take as a functor or a further template parameter, so the loop is written out here.
 template <typename T, typename S, bool RELAX>
 __global__ void __launch_bounds__(MIK_DS_R) k_ds_panel(int n, int k0, const T *__restrict__ A, int64_t ld, T *t, T *x, S omega)
 {
@@ -136,7 +77,7 @@ __global__ void __launch_bounds__(MIK_DS_R) k_ds_panel(int n, int k0, const T *_
     const bool live = r < n;
     const T *Ar = A + (live ? r : k0);              // a dead lane reads row k0 (in bounds) and stores nothing
     T acc = live ? t[r] : T(0);
-    if (k0 > 0) acc = ds_walk<T, true, MIK_DS_ALL>(acc, Ar, ld, x, k0 - MIK_DS_W, k0, r);
+    if (k0 > 0) acc = de_walk<T, true, MIK_DS_ALL>(acc, Ar, ld, x, k0 - MIK_DS_W, k0, r);
     if (blockIdx.x != 0) {
         if (live) t[r] = acc;
         return;

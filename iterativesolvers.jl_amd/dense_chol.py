@@ -24,87 +24,36 @@ generic iterables and every other solver call ``ldiv_`` like on any user precond
 """
 from __future__ import annotations
 
-import ctypes as C
-
-import numpy as np
-
-from . import _lib
-from ._lib import MikError, check, lib
-from .api import HipMatrix, HipVector
+from ._lib import MikError
+from .api import HipMatrix
+from .dense_factor import DenseFactor
 from .stationary import PosDefException
 
-_vp = C.c_void_p
 
-
-def _admit(A):
-    """the refusals of cholesky / cholesky!: not a HipMatrix, not square"""
-    if not isinstance(A, HipMatrix):
-        raise TypeError(f"cholesky takes a HipMatrix, got {type(A).__name__}")
-    if A.n != A.cols:
-        raise ValueError(f"DimensionMismatch: the matrix is {A.n} x {A.cols}, not square")
-
-
-class DenseCholesky:
+class DenseCholesky(DenseFactor):
     """The factorisation of a square ``HipMatrix`` of float64 / float32 / complex128 / complex64, made in place in the lower triangle
     of ``factors``."""
 
+    _entry, _name, _failure = "mik_dense_chol", "cholesky", PosDefException
+    _info_keys = ("W", "R", "tile_rows", "tile_cols", "launches_factor", "launches_solve", "bytes", "info")
     uplo = "L"
 
     def __init__(self, factors: HipMatrix, check: bool = True):
-        _admit(factors)
-        self.factors = factors
-        self.ctx = factors.ctx
-        self.dtype = np.dtype(factors.dtype)
-        self.n = factors.n
-        h = _vp()
-        col = C.c_int64()
-        code = lib().mik_dense_chol_create(self.ctx.handle, _vp(factors.buf.ptr), self.n, factors.ld, _lib.dtype_code(self.dtype), 1 if check else 0,
-                                           C.byref(col), C.byref(h))
-        if code == 8:
-            raise PosDefException(col.value)
-        _lib.check(code, "mik_dense_chol_create", self.ctx.handle)
-        self.handle = h
-        self.info = int(col.value)
+        self.info = self._create(factors, 1 if check else 0)
 
     def issuccess(self) -> bool:
         return self.info == 0
 
-    def _vec(self, v: HipVector, name: str):
-        if not isinstance(v, HipVector) or v.n != self.n or v.dtype != self.dtype:
-            raise ValueError(f"DimensionMismatch: {name} has {getattr(v, 'n', '?')}/{getattr(v, 'dtype', type(v).__name__)}, the factorisation {self.n}/{self.dtype}")
-        return _vp(v.ptr)
-
-    def ldiv_(self, y: HipVector, x: HipVector = None) -> HipVector:
-        """``ldiv!(y, F, x)``; with one argument ``ldiv!(F, y)``.  ``x`` is not modified; ``y`` may be ``x``.  Refused on a failed
-        factorisation (``info != 0``)."""
-        x = y if x is None else x
-        yp, xp = self._vec(y, "y"), self._vec(x, "x")
+    def _usable(self):
+        """``ldiv_`` is refused on a failed factorisation (``info != 0``)"""
         if self.info:
             raise MikError(1, "mik_dense_chol_solve", f"the factorisation failed: PosDefException({self.info})")
-        check(lib().mik_dense_chol_solve(self.handle, yp, xp), "mik_dense_chol_solve", self.ctx.handle)
-        return y
-
-    def solve(self, b: HipVector) -> HipVector:
-        """``F \\ b``: a new vector."""
-        self._vec(b, "b")
-        return self.ldiv_(b.similar(), b)
 
     def plan(self) -> dict:
         """Panel width W, rows per workgroup of the panel kernel R, tile of the trailing update, launches of the factorisation and of one
         solve, device bytes held, and ``info`` -- for this handle's element type (``mik_dense_chol_info``).  ``F.info`` itself is the
         reference's field, an integer."""
-        v = [C.c_int64() for _ in range(8)]
-        check(lib().mik_dense_chol_info(self.handle, *[C.byref(q) for q in v]), "mik_dense_chol_info", self.ctx.handle)
-        keys = ("W", "R", "tile_rows", "tile_cols", "launches_factor", "launches_solve", "bytes", "info")
-        return {k: q.value for k, q in zip(keys, v)}
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None) and self.ctx.handle:
-                lib().mik_dense_chol_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
+        return self._read_info()
 
 
 def cholesky_(A: HipMatrix, check: bool = True) -> DenseCholesky:
@@ -115,7 +64,4 @@ def cholesky_(A: HipMatrix, check: bool = True) -> DenseCholesky:
 
 def cholesky(A: HipMatrix, check: bool = True) -> DenseCholesky:
     """``cholesky(Hermitian(A, :L))``: factors a copy; ``A`` is left as it is."""
-    _admit(A)
-    copy = HipMatrix(A.n, A.cols, A.dtype, A.ctx)
-    copy.buf.copyto_(A.buf)
-    return DenseCholesky(copy, check)
+    return DenseCholesky._of_copy(A, check)

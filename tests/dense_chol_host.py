@@ -3,17 +3,12 @@ Cholesky, in all four element types), a plain-numpy BLOCKED restatement of the t
 `same_bits`, and the matrices of the dense Cholesky tests -- each failing one with a function that asserts, on the checker, the
 condition the fixture exists for.  Test infrastructure only."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "dense_ref", "dense_chol_ref.c")
+from dense_ref_host import DTYPES, _p, build_ref, first_difference, same_bits  # noqa: F401
 
-DTYPES = [np.float64, np.float32, np.complex128, np.complex64]
 _SFX = {"float64": "f64", "float32": "f32", "complex128": "c64", "complex64": "c32"}
-_vp = C.c_void_p
 
 
 def real_of(dtype):
@@ -25,14 +20,7 @@ def is_complex(dtype):
 
 
 def build(outdir):
-    """gcc -O2 -ffp-contract=off (no product is ever fused into a difference) -> a shared object in `outdir`."""
-    so = os.path.join(str(outdir), "dense_chol_ref.so")
-    subprocess.check_call(["gcc", "-std=c99", "-O2", "-ffp-contract=off", "-shared", "-fPIC", SRC, "-o", so, "-lm"])
-    return Ref(C.CDLL(so))
-
-
-def _p(a):
-    return a.ctypes.data_as(_vp)
+    return Ref(build_ref("dense_chol_ref", outdir, "-lm"))
 
 
 class Ref:
@@ -65,34 +53,6 @@ class Ref:
         x = np.ascontiguousarray(b, L.dtype).copy()
         self._fn("dcr_solve", L.dtype)(C.c_int64(x.size), _p(L), C.c_int64(L.shape[0]), _p(x))
         return x
-
-
-def _reals(a):
-    """a floating array as it is, a complex one as its (re, im) pairs"""
-    return np.ascontiguousarray(np.stack([a.real, a.imag], axis=-1)) if is_complex(a.dtype) else np.ascontiguousarray(a)
-
-
-def same_bits(got, want):
-    """Same shape and dtype, NaN in exactly the same positions (per component of a complex), and everywhere else equal as unsigned
-    integers of the component width, so -0.0 differs from +0.0.  The payload and the sign of a NaN are not compared."""
-    got, want = np.asarray(got), np.asarray(want)
-    if got.shape != want.shape or got.dtype != want.dtype or got.dtype not in DTYPES:
-        return False
-    g, w = _reals(got), _reals(want)
-    u = np.uint64 if g.dtype == np.float64 else np.uint32
-    gn, wn = np.isnan(g), np.isnan(w)
-    return bool(np.array_equal(gn, wn) and np.array_equal(g.view(u)[~gn], w.view(u)[~wn]))
-
-
-def first_difference(got, want):
-    """up to four indices (into the array of real components) at which `same_bits` fails, for an assertion message"""
-    got, want = np.asarray(got), np.asarray(want)
-    if got.shape != want.shape or got.dtype != want.dtype:
-        return (got.shape, got.dtype, want.shape, want.dtype)
-    g, w = _reals(got), _reals(want)
-    u = np.uint64 if g.dtype == np.float64 else np.uint32
-    gn, wn = np.isnan(g), np.isnan(w)
-    return np.argwhere((gn != wn) | (~gn & ~wn & (g.view(u) != w.view(u))))[:4].tolist()
 
 
 def lower(M):

@@ -3,27 +3,16 @@ plain-numpy BLOCKED restatement of the same factorisation, the bitwise compariso
 each non-finite or scaled one with a `*_case` function that asserts, on the checker, the conditions the fixture exists for.  Test
 infrastructure only."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "dense_ref", "dense_lu_ref.c")
+from dense_ref_host import _p, build_ref, first_difference, same_bits  # noqa: F401
 
-_vp = C.c_void_p
 _i64p = C.POINTER(C.c_int64)
 
 
 def build(outdir):
-    """gcc -O2 -ffp-contract=off (no product is ever fused into a difference) -> a shared object in `outdir`."""
-    so = os.path.join(str(outdir), "dense_lu_ref.so")
-    subprocess.check_call(["gcc", "-std=c99", "-O2", "-ffp-contract=off", "-shared", "-fPIC", SRC, "-o", so])
-    return Ref(C.CDLL(so))
-
-
-def _p(a):
-    return a.ctypes.data_as(_vp)
+    return Ref(build_ref("dense_lu_ref", outdir))
 
 
 class Ref:
@@ -62,28 +51,6 @@ class Ref:
         x = self.pivots(ipiv, np.ascontiguousarray(b, LU.dtype))
         self._fn("dlr_solve", LU.dtype)(C.c_int64(x.size), _p(LU), C.c_int64(LU.shape[0]), _p(x))
         return x
-
-
-def same_bits(got, want):
-    """Same shape and dtype, NaN in exactly the same positions, and everywhere else equal as unsigned integers of the element width, so
-    -0.0 differs from +0.0.  The payload and the sign of a NaN are not compared: an x86 host and the device generate different default
-    NaNs, and the contract does not speak of them."""
-    got, want = np.asarray(got), np.asarray(want)
-    if got.shape != want.shape or got.dtype != want.dtype or got.dtype not in (np.float64, np.float32):
-        return False
-    u = np.uint64 if got.dtype == np.float64 else np.uint32
-    gn, wn = np.isnan(got), np.isnan(want)
-    return bool(np.array_equal(gn, wn) and np.array_equal(got.view(u)[~gn], want.view(u)[~wn]))
-
-
-def first_difference(got, want):
-    """up to four indices at which `same_bits` fails, for an assertion message"""
-    got, want = np.asarray(got), np.asarray(want)
-    if got.shape != want.shape or got.dtype != want.dtype:
-        return (got.shape, got.dtype, want.shape, want.dtype)
-    u = np.uint64 if got.dtype == np.float64 else np.uint32
-    gn, wn = np.isnan(got), np.isnan(want)
-    return np.argwhere((gn != wn) | (~gn & ~wn & (got.view(u) != want.view(u))))[:4].tolist()
 
 
 def permutation_of(ipiv):

@@ -171,7 +171,7 @@ def _vector(pkg, n, dtype):
 
 def test_refusals_without_a_device(pkg, monkeypatch):
     fake = FakeLib()
-    monkeypatch.setattr(pkg.dense_chol, "lib", lambda: fake)
+    monkeypatch.setattr(pkg.dense_factor, "lib", lambda: fake)
     for factor in (pkg.cholesky, pkg.cholesky_):
         for bad in (np.eye(3), None, "A"):
             with pytest.raises(TypeError, match="HipMatrix"):
@@ -196,7 +196,7 @@ def test_refusals_without_a_device(pkg, monkeypatch):
 def test_posdef_exception_and_check_false_without_a_device(pkg, monkeypatch):
     assert issubclass(pkg.PosDefException, np.linalg.LinAlgError) and not issubclass(pkg.PosDefException, pkg.SingularException)
     fake = FakeLib(fail_at=7)
-    monkeypatch.setattr(pkg.dense_chol, "lib", lambda: fake)
+    monkeypatch.setattr(pkg.dense_factor, "lib", lambda: fake)
     A = _matrix(pkg, 9, 9, np.complex64)
     with pytest.raises(np.linalg.LinAlgError) as ei:
         pkg.cholesky_(A)
@@ -215,7 +215,7 @@ def test_posdef_exception_and_check_false_without_a_device(pkg, monkeypatch):
 def test_precond_binding_refuses_a_wrong_size_or_type(pkg, monkeypatch):
     """_Bound.precond checks n and dtype where the callback is bound: the callback itself never sees a length"""
     fake = FakeLib()
-    monkeypatch.setattr(pkg.dense_chol, "lib", lambda: fake)
+    monkeypatch.setattr(pkg.dense_factor, "lib", lambda: fake)
     F = pkg.cholesky_(_matrix(pkg, 5, 5, np.float64))
     bound = types.SimpleNamespace(n=6, dtype=np.dtype(np.float64), keep=[])
     with pytest.raises(ValueError, match="DimensionMismatch.*cholesky"):
