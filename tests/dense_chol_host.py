@@ -1,7 +1,7 @@
 """ctypes binding of tests/dense_ref/dense_chol_ref.c (the unblocked loops of cholesky! / ldiv! that state the bit contract of the dense
 Cholesky, in all four element types), a plain-numpy BLOCKED restatement of the three-launch device plan, the bitwise comparison
-`same_bits`, and the matrices of the dense Cholesky tests -- each failing one with a function that asserts, on the checker, the
-condition the fixture exists for.  Test infrastructure only."""
+`same_bits`, and the matrices of the dense Cholesky tests -- each one that exists for a condition (a failing column, a scale, a poisoned
+part that must not be read) with a `*_case` function that asserts that condition on the checker first.  Test infrastructure only."""
 import ctypes as C
 
 import numpy as np
@@ -192,11 +192,121 @@ def failing_case(ref, n, dtype, k, kind):
     return A, out, k + 1
 
 
-def poisoned(A):
-    """A with its strict upper triangle NaN (both components in the complex types)"""
+def poisons(dtype):
+    """what an element that must never be read is filled with: NaN, +Inf and the largest finite value (which overflows in a product and
+    survives a masked sum that a NaN or an Inf would also spoil)"""
+    return (np.nan, np.inf, np.finfo(real_of(dtype)).max)
+
+
+def poison_of(dtype, p):
+    """the element of `dtype` whose every real component is p"""
+    return np.dtype(dtype).type(complex(p, p) if is_complex(dtype) else p)
+
+
+def poisoned(A, p=np.nan):
+    """A with its strict upper triangle p (both components in the complex types)"""
     P = np.array(A, order="F")
-    P[np.triu_indices(P.shape[0], 1)] = np.nan * (1 + 1j) if is_complex(P.dtype) else np.nan
+    P[np.triu_indices(P.shape[0], 1)] = poison_of(P.dtype, p)
     return P
+
+
+def poisoned_case(ref, A, p):
+    """(P, the checker's array of P): the checker's lower triangle and its solve of one b are those of the clean matrix, and the strict
+    upper triangle leaves the loops as it came"""
+    n = A.shape[0]
+    P = poisoned(A, p)
+    clean, info = ref.factor(A)
+    out, info_p = ref.factor(P)
+    assert info == 0 and info_p == 0 and same_bits(lower(out), lower(clean))
+    iu = np.triu_indices(n, 1)
+    assert same_bits(out[iu], P[iu])
+    b = vector(n, A.dtype)
+    assert same_bits(ref.solve(out, b), ref.solve(clean, b))
+    return P, out
+
+
+def imag_poisoned(A, p):
+    """a complex A with the imaginary part of every diagonal entry set to p; the real parts keep their bits (assigned through .imag:
+    real + 1j * nan would poison the real part too)"""
+    assert is_complex(A.dtype)
+    P = np.array(A, order="F")
+    d = np.arange(P.shape[0])
+    P.imag[d, d] = p
+    assert same_bits(np.ascontiguousarray(P.real), np.ascontiguousarray(A.real))
+    return P
+
+
+def imag_poisoned_case(ref, A, p):
+    """(P, the checker's array of the CLEAN matrix): the checker never reads the imaginary part of a diagonal entry, so its whole output
+    for P -- every stored diagonal imaginary part +0 among it -- has the bits of its output for A"""
+    P = imag_poisoned(A, p)
+    out, info = ref.factor(A)
+    got, info_p = ref.factor(P)
+    assert info == 0 and info_p == 0 and same_bits(got, out)
+    R = real_of(A.dtype)
+    assert same_bits(np.ascontiguousarray(np.diag(got).imag), np.zeros(A.shape[0], R))
+    return P, out
+
+
+# ---- the widths of a last panel, the waves that report, the scales -----------------------------------------------------------------------
+def width_sizes(W):
+    """every n whose last panel is m = 1 .. W columns wide, alone (n = m) and behind a full panel (n = W + m), and two sizes with two
+    full panels ahead: a full last panel (3 W) and a last panel of 17 columns, one past a batch of 16 (3 W + 17).  2 W is W + m at
+    m = W: a full last panel behind a full one."""
+    out = sorted({m for m in range(1, W + 1)} | {W + m for m in range(1, W + 1)} | {3 * W, 3 * W + 17})
+    assert len(out) == 2 * W + 2 and {n % W for n in out} == set(range(W))
+    return out
+
+
+def report_columns(n, W):
+    """Failing columns at the positions 1, 2, 3 (mod 4) of the first panel and of a later one; failure_columns(n, W) holds position 0 of
+    both.  If every fourth column of a panel is handled by one of four units, each unit reports in both panels."""
+    cols = (1, 2, 3, W - 1, W + 1, W + 2, W + 3, 2 * W - 1)
+    assert W % 4 == 0 and cols[-1] < n - 1 and len(set(cols)) == len(cols)
+    for panel in (0, 1):
+        mine = {k % W % 4 for k in cols if k // W == panel}
+        both = mine | {k % W % 4 for k in failure_columns(n, W) if k // W == panel}
+        assert mine == {1, 2, 3} and both == {0, 1, 2, 3}
+    return cols
+
+
+def scales(dtype):
+    """(every diagonal entry of hpd(n) * s subnormal, most entries subnormal but not the diagonal, near overflow), of the real type"""
+    R = real_of(dtype)
+    f = np.finfo(R)
+    return R.type(f.tiny * 2.0 ** -10), R.type(f.tiny * 2.0 ** -4), R.type(f.max / 2.0 ** 12)
+
+
+def _components(a):
+    return np.concatenate([np.asarray(a.real).ravel(), np.asarray(a.imag).ravel()]) if is_complex(a.dtype) else np.asarray(a).ravel()
+
+
+def scaled_case(ref, dtype, W, which):
+    """(A, the checker's array, b, the checker's solution) for A = hpd(2 W + 1) * scales(dtype)[which] and b = vector * the same scale.
+    Everywhere: the factorisation succeeds, L is finite with no zero on or below its diagonal, the solution is finite and non-zero.
+    Smallest scale: every diagonal entry of A is subnormal and not zero; a pivot is at most A[j,j], so every argument of sqrt is
+    subnormal.  Both small scales: at least half of the non-zero real components of A are subnormal."""
+    n = 2 * W + 1
+    R = real_of(dtype)
+    s = scales(dtype)[which]
+    tiny = np.finfo(R).tiny
+    A = np.asfortranarray((hpd(n, dtype) * s).astype(dtype))
+    assert A.dtype == np.dtype(dtype)
+    out, info = ref.factor(A)
+    il = np.tril_indices(n)
+    assert info == 0 and np.isfinite(lower(out)).all() and (out[il] != 0).all()
+    if which == 0:
+        d = np.diag(A).real
+        assert (d > 0).all() and (d < tiny).all()
+        assert (np.diag(out).real <= np.sqrt(d)).all()                      # subtracting products that are >= 0 never raises d; sqrt is monotone
+    if which in (0, 1):
+        comp = np.abs(_components(A))
+        assert 2 * np.count_nonzero((comp != 0) & (comp < tiny)) >= np.count_nonzero(comp)
+    b = (vector(n, dtype) * s).astype(dtype)
+    assert b.dtype == np.dtype(dtype)
+    want = ref.solve(out, b)
+    assert np.isfinite(want).all() and (want != 0).all()
+    return A, out, b, want
 
 
 def plan_launches(n, W):

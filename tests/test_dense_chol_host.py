@@ -126,6 +126,83 @@ def test_plan_launches():
     assert [ch.plan_launches(n, 64) for n in (1, 64, 65, 128, 129, 323)] == [1, 1, 4, 4, 7, 16]
 
 
+# ---- the fixtures of tests/test_gpu_dense_chol_edges.py: each builder's own preconditions, once per element type at W ---------------------
+def test_width_sizes_visit_every_width_of_a_last_panel():
+    sizes = ch.width_sizes(W)
+    assert sizes == sorted(set(sizes)) and len(sizes) == 2 * W + 2
+    assert {n for n in sizes if n <= W} == set(range(1, W + 1)) and {n - W for n in sizes if W < n <= 2 * W} == set(range(1, W + 1))
+    for m in (15, 16, 17, 31, 32, 33):                                      # one short of, at and one past a batch of 16 and a chunk of 32
+        assert m in sizes and W + m in sizes
+    assert 2 * W in sizes and 3 * W in sizes and 3 * W + 17 in sizes
+    assert [ch.plan_launches(n, W) for n in (2 * W, 3 * W, 3 * W + 17)] == [4, 7, 10]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_report_columns_fail_where_they_say(ref, dtype):
+    n = 130
+    cols = ch.report_columns(n, W)
+    assert cols == (1, 2, 3, 63, 65, 66, 67, 127) and not set(cols) & set(ch.failure_columns(n, W))
+    L = ch.exact(n, dtype)[1]
+    for k in cols:
+        A, out, info = ch.failing_case(ref, n, dtype, k, "negative")
+        assert info == k + 1 and np.array_equal(ch.lower(out)[:, :k], L[:, :k])
+        assert ch.blocked(A, W)[1] == info
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("which", [0, 1, 2])
+def test_scaled_case_holds_its_preconditions(ref, dtype, which):
+    s = ch.scales(dtype)
+    f = np.finfo(ch.real_of(dtype))
+    assert all(v.dtype == ch.real_of(dtype) for v in s) and 0 < s[0] < s[1] < f.tiny and f.max / 2 ** 13 < s[2] < f.max
+    A, out, b, want = ch.scaled_case(ref, dtype, W, which)
+    assert A.shape == (2 * W + 1, 2 * W + 1) and A.flags.f_contiguous and out.dtype == A.dtype == b.dtype == want.dtype == np.dtype(dtype)
+    if which == 1:                                                          # here the diagonal is normal: most of the rest is not
+        assert (np.diag(A).real >= f.tiny).all()
+    if which < 2:                                                           # flushing the subnormal operands alone already changes the factor
+        flushed = A.copy(order="F")
+        for part in ((flushed.real, flushed.imag) if ch.is_complex(dtype) else (flushed,)):
+            part[np.abs(part) < f.tiny] = 0
+        got, info = ref.factor(flushed)
+        assert info != 0 or not ch.same_bits(ch.lower(got), ch.lower(out))
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.complex64])
+def test_blocked_plan_at_the_smallest_scale(ref, dtype):
+    """the plan's claim -- an element meets its k in the loop's order -- does not lean on the magnitudes: subnormal operands, same bits"""
+    A, out, _, _ = ch.scaled_case(ref, dtype, W, 0)
+    got, info = ch.blocked(A, W)
+    assert info == 0 and ch.same_bits(got, out), ch.first_difference(got, out)
+
+
+@pytest.mark.parametrize("dtype", [np.complex128, np.complex64])
+def test_imag_poisoned_diagonal_on_the_checker(ref, dtype):
+    n = 2 * W + W + 1
+    A = ch.hpd(n, dtype)
+    for p in ch.poisons(dtype) + (7,):
+        P, out = ch.imag_poisoned_case(ref, A, p)
+        d = np.diag(P).imag
+        assert (np.isnan(d).all() if np.isnan(p) else (d == p).all()) and ch.same_bits(np.tril(P, -1), np.tril(A, -1))
+        b = ch.vector(n, dtype)
+        assert ch.same_bits(ref.solve(ref.factor(P)[0], b), ref.solve(out, b))
+    with pytest.raises(AssertionError):
+        ch.imag_poisoned(ch.hpd(3, np.float64), np.nan)                     # a real matrix has nothing to poison there
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_poisoned_upper_triangle_on_the_checker(ref, dtype):
+    n = 2 * W + W + 1
+    A = ch.hpd(n, dtype)
+    ps = ch.poisons(dtype)
+    assert np.isnan(ps[0]) and np.isinf(ps[1]) and ps[2] == np.finfo(ch.real_of(dtype)).max
+    for p in ps:
+        P, out = ch.poisoned_case(ref, A, p)
+        iu = np.triu_indices(n, 1)
+        comp = ch._components(P[iu])
+        assert np.isnan(comp).all() if np.isnan(p) else (comp == p).all()
+        assert ch.same_bits(np.tril(P), np.tril(A))
+
+
 # ---- refusals and check=False on a device-free double of the library ---------------------------------------------------------------------
 class FakeLib:
     """mik_dense_chol_* as the header states them, with no device: create reports `fail_at` the way `check` asks for"""

@@ -2,7 +2,8 @@
 in Float64, Float32, ComplexF64 and ComplexF32, bit for bit against tests/dense_ref/dense_chol_ref.c -- the contract's unblocked loops
 restated in C.  Every comparison of device values with the checker's is dense_chol_host.same_bits (NaN positions, and the bits everywhere
 else: -0.0 is not +0.0); comparisons with a fixture's construction are np.array_equal.  Every shape comes from mik_dense_chol_info
-(F.plan()).  The reference's own statements with cholesky(A) as Pl carry the reference's own bounds."""
+(F.plan()).  Every width of a last panel, extreme magnitudes, poisoned unread parts, any ld and non-finite right-hand sides are in
+test_gpu_dense_chol_edges.py.  The reference's own statements with cholesky(A) as Pl carry the reference's own bounds."""
 import ctypes as C
 
 import numpy as np
