@@ -790,6 +790,15 @@ int mik_dense_lu_ipiv(const mik_dense_lu *F, int64_t *ipiv);
 /* ldiv!(y, F, x) on DEVICE n-vectors, asynchronous on the ctx stream.  y may equal x (ldiv!(F, x)); a partial overlap, or a vector that
  * overlaps the factors, is MIK_ERR_INVALID. */
 int mik_dense_lu_solve(mik_dense_lu *F, void *y, const void *x);
+/* ldiv!(Y, F, X) on DEVICE column-major blocks: Y[:, 0:nrhs) = F \ X[:, 0:nrhs), n rows each, leading dimensions ldy and ldx; asynchronous
+ * on the ctx stream.  Column j of Y has exactly the bits mik_dense_lu_solve gives for column j of X (non-finite data included): the same
+ * operations on the same operands in the same order; a lane of the substitution kernels carries NB columns (2 of a real type, 1 of a
+ * complex one), and the groups of NB columns run side by side in every launch.  The block runs in passes of at most 32 columns, each pass the launches of one vector solve, through a workspace of
+ * n x 32 elements that the handle allocates at the first block solve, keeps, and frees in destroy (mik_dense_lu_info's bytes does not count
+ * it); nothing is allocated afterwards.  Y may be X with ldy == ldx (the pass is gathered into the workspace first).  MIK_ERR_MISMATCH for
+ * nrhs < 1, ldy < n or ldx < n; MIK_ERR_INVALID for any other overlap of the two blocks, or of a block with the factors.  A refused call
+ * launches nothing.  The rows [n, ld) of Y and its columns from nrhs on are never written.  Added without a version bump, additive. */
+int mik_dense_lu_solve_block(mik_dense_lu *F, void *Y, int64_t ldy, const void *X, int64_t ldx, int64_t nrhs);
 /* The same as a mik_ldiv_fn (user = the handle): a host fills mik_precond{NULL, mik_dense_lu_ldiv_fn, handle} and the fused iterables
  * apply Pl / Pr with no host frame of the caller's. */
 int mik_dense_lu_ldiv_fn(void *user, void *y, const void *x);
@@ -828,6 +837,12 @@ int mik_dense_chol_destroy(mik_dense_chol *F);
 /* ldiv!(y, F, x) on DEVICE n-vectors, asynchronous on the ctx stream; nothing is allocated.  y may equal x (ldiv!(F, x)); a partial overlap,
  * a vector that overlaps the factors, or a handle whose info is not 0 is MIK_ERR_INVALID. */
 int mik_dense_chol_solve(mik_dense_chol *F, void *y, const void *x);
+/* ldiv!(Y, F, X) on DEVICE column-major blocks, as mik_dense_lu_solve_block: column j of Y has exactly the bits mik_dense_chol_solve gives
+ * for column j of X; passes of at most 32 columns, each the launches of one vector solve, through a workspace of n x 32 elements allocated
+ * at the first block solve and kept (mik_dense_chol_info's bytes does not count it).  Y may be X with ldy == ldx.  MIK_ERR_MISMATCH for
+ * nrhs < 1, ldy < n or ldx < n; MIK_ERR_INVALID for any other overlap of the two blocks, an overlap with the factors, or a handle whose info
+ * is not 0.  A refused call launches nothing.  The rows [n, ld) of Y and its columns from nrhs on are never written. */
+int mik_dense_chol_solve_block(mik_dense_chol *F, void *Y, int64_t ldy, const void *X, int64_t ldx, int64_t nrhs);
 /* The same as a mik_ldiv_fn (user = the handle): a host fills mik_precond{NULL, mik_dense_chol_ldiv_fn, handle} and the fused iterables
  * apply Pl / Pr with no host frame of the caller's. */
 int mik_dense_chol_ldiv_fn(void *user, void *y, const void *x);

@@ -75,6 +75,12 @@ int mik_dev_dense_block_plan(const mik_dense *D, int b, const void *X, int64_t l
 /* The narrowest last group this handle gives to the block kernel: 1 .. group width; 0 = the library's threshold.  For measurements and for
  * tests that want the block kernel at every width; results never depend on it. */
 int mik_dev_dense_block_min_width(mik_dense *D, int width);
+/* The plan mik_dense_lu_solve_block / mik_dense_chol_solve_block take for nrhs columns on this handle (the helper the entries run):
+ * *nb = columns a lane of the substitution kernels carries (by element type), *g = columns per pass, *passes = ceil(nrhs / g) (0 for
+ * nrhs < 1), *launches = passes x the launches of one vector solve, *workspace_bytes = the block workspace (n x g elements), whether or
+ * not a block solve has allocated it yet.  Nothing is launched or read on the device.  Any out pointer may be NULL. */
+int mik_dev_dense_lu_block_plan(const mik_dense_lu *F, int64_t nrhs, int64_t *nb, int64_t *g, int64_t *passes, int64_t *launches, int64_t *workspace_bytes);
+int mik_dev_dense_chol_block_plan(const mik_dense_chol *F, int64_t nrhs, int64_t *nb, int64_t *g, int64_t *passes, int64_t *launches, int64_t *workspace_bytes);
 /* Shape of the resident-w Modified Gram-Schmidt kernel (csrc/mik_mgs_res.h): threads per workgroup (threads / 256 segments per round), rounds of a
  * workgroup's segments kept in registers and in LDS; the rest of w is streamed in every pass.  For byte accounting (bench.py). */
 int mik_dev_mgs_resident_shape(int *threads, int *register_rounds, int *lds_rounds);

@@ -87,6 +87,8 @@ SIGNATURES = {
     "mik_dev_dense_plan": (C.c_int, [_vp, C.c_int, _vp, _vp, _ip, _ip, _i64p, _i64p, _i64p, _i64p]),
     "mik_dev_dense_block_plan": (C.c_int, [_vp, C.c_int, _vp, _i64, _vp, _i64, _ip, _ip, _i64p, _i64p, _i64p, _ip, _ip, _ip, _i64p]),
     "mik_dev_dense_block_min_width": (C.c_int, [_vp, C.c_int]),
+    "mik_dev_dense_lu_block_plan": (C.c_int, [_vp, _i64, _i64p, _i64p, _i64p, _i64p, _i64p]),
+    "mik_dev_dense_chol_block_plan": (C.c_int, [_vp, _i64, _i64p, _i64p, _i64p, _i64p, _i64p]),
     "mik_dev_mgs_resident_shape": (C.c_int, [_ip, _ip, _ip]),
     "mik_dev_spmv_plan": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, _i64p, _ip, _ip, _ip]),
     "mik_dev_spmv_run": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -232,11 +234,13 @@ SIGNATURES = {
     "mik_dense_lu_destroy": (C.c_int, [_vp]),
     "mik_dense_lu_ipiv": (C.c_int, [_vp, _i64p]),
     "mik_dense_lu_solve": (C.c_int, [_vp, _vp, _vp]),
+    "mik_dense_lu_solve_block": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64]),
     "mik_dense_lu_ldiv_fn": (C.c_int, [_vp, _vp, _vp]),
     "mik_dense_lu_info": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p]),
     "mik_dense_chol_create": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.c_int, _i64p, C.POINTER(_vp)]),
     "mik_dense_chol_destroy": (C.c_int, [_vp]),
     "mik_dense_chol_solve": (C.c_int, [_vp, _vp, _vp]),
+    "mik_dense_chol_solve_block": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64]),
     "mik_dense_chol_ldiv_fn": (C.c_int, [_vp, _vp, _vp]),
     "mik_dense_chol_info": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p]),
     "mik_dense_mul_shape": (C.c_int, [_ip, _ip]),

@@ -26,6 +26,8 @@
 //   k_dense_fwd<E, false>   one panel of the forward substitution, with the division by the diagonal
 //   k_chol_bwd    one panel of the backward substitution: row r needs conj(L[c,r]), element c of COLUMN r, so the block is loaded along
 //                 its columns (coalesced), turned in LDS (padded pitch) and walked from there, c descending
+//   k_dense_fwd_nb<E, false, NB>, k_chol_bwd_nb<E, NB>   the two for a block of right-hand sides, NB per lane (ldiv!(Y, F, X)): per column the
+//                 same operations on the same operands in the same order, so column j has the bits of the vector solve of column j
 // The element (de_cx and the de_* operations), the serial step of a diagonal block (de_step) and the two k_dense_* kernels are those of
 // csrc/mik_dense_elem.h, written once for the dense stationary methods, the LU and this file.
 // Nothing indexes memory through a data value, so an indefinite or non-finite matrix cannot fault: after the first failing column the
@@ -221,4 +223,61 @@ __global__ void __launch_bounds__(MIK_DS_R) k_chol_bwd(int n, int k0, int k1, co
         return;
     }
     if (live) { t[r] = mine; y[r] = mine; }
+}
+
+// k_chol_bwd for a block of right-hand sides.  A lane carries the NB right-hand sides of group blockIdx.y (csrc/mik_dense_elem.h): every
+// element of the turned chunk is read from LDS once for them.  t is the group's workspace, y column-major with the leading dimension ldy;
+// only the live columns are stored there.
+template <typename E, int NB>
+__global__ void __launch_bounds__(MIK_DS_R) k_chol_bwd_nb(int n, int k0, int k1, const E *__restrict__ A, int64_t ld, E *t, E *y, int64_t ldy, int cols)
+{
+    using R = typename de_real<E>::type;
+    constexpr int BC = MIK_CH_BC;
+    static_assert(64 % BC == 0 && 64 / BC * BC == 64 && BC == 32, "a wave loads 64 / BC columns of BC elements per pass, BC passes per chunk");
+    __shared__ E Ts[64 * (BC + 1)];
+    const int lane = (int)threadIdx.x;
+    const int r0 = (int)blockIdx.x * MIK_DS_R;
+    const int r = r0 + lane;
+    const bool live = r < k1;
+    const bool diag = r0 == k0;                                // workgroup-uniform: this workgroup owns the diagonal block
+    const int hi = min(k1 + MIK_CH_W, n);
+    // the chunks of the columns [lo, hi) in descending order, lo = k0 for the workgroup of the diagonal block and k1 for the others;
+    // k1 - k0 = W whenever there are columns above k1, so every chunk lies on one side of k1
+    const int lo = diag ? k0 : k1;
+    const int g0 = de_group_first<NB>();
+    t += (int64_t)g0 * n;
+    E acc[NB], mine[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) mine[b] = acc[b] = live ? t[(int64_t)r * NB + b] : de_zero<E>();
+    const R d = (diag && live) ? de_re(A[(int64_t)r * ld + r]) : R(1);
+    E reg[BC];
+    int c_lo = lo + (hi - lo - 1) / BC * BC;
+    if (hi > lo) ch_turn_load<E>(reg, A, ld, r0, k1, c_lo, hi, lane);
+    for (; c_lo >= lo && hi > lo; c_lo -= BC) {                // uniform
+        ch_turn_store<E>(Ts, reg, lane);
+        if (c_lo - BC >= lo) ch_turn_load<E>(reg, A, ld, r0, k1, c_lo - BC, hi, lane);
+        const int cnt = min(BC, hi - c_lo);
+        if (c_lo >= k1) {                                      // the panel above: its solution is in t
+            for (int c = cnt - 1; c >= 0; --c) {
+                const E l = Ts[lane * (BC + 1) + c];
+#pragma unroll
+                for (int b = 0; b < NB; ++b) de_msub_lc(acc[b], l, t[(int64_t)(c_lo + c) * NB + b]);
+            }
+        } else {                                               // the diagonal block: steps j descending
+            for (int c = cnt - 1; c >= 0; --c) de_step<false, false>(acc, mine, d, de_conj(Ts[lane * (BC + 1) + c]), c_lo + c - k0, lane);      // wave-uniform j
+        }
+    }
+    if (!diag) {
+        if (live) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) t[(int64_t)r * NB + b] = acc[b];
+        }
+        return;
+    }
+    if (!live) return;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        t[(int64_t)r * NB + b] = mine[b];
+        if (de_col_live<NB>(g0, b, cols)) y[(int64_t)(g0 + b) * ldy + r] = mine[b];
+    }
 }

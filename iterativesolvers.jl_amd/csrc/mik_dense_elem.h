@@ -2,9 +2,11 @@
 // sor, ssor), csrc/mik_dense_lu.h (lu!) and csrc/mik_dense_chol.h (cholesky!).  Each piece is written here once:
 //   the element   a real, or an interleaved (re, im) pair (de_cx), and its operations de_*: every rounding sequence of the three bit
 //                 contracts is one of these.  The complex products are cx_msub of csrc/mik_complex.h.
-//   de_walk       a row's chain acc -= A[r,c] x[c] over a column range, the next batch's loads issued first
+//   de_walk       a row's chain acc -= A[r,c] x[c] over a column range, the next batch's loads issued first; de_walk_nb: the chains of the
+//                 NB right-hand sides a lane of a block solve carries, every A[r,c] loaded once for them
 //   de_step       one serial step of a diagonal block in a wave: quotient, broadcast, the rows on one side subtract
-//   k_dense_fwd   one panel of a forward substitution, unit diagonal (lu) or a division by the real diagonal (cholesky)
+//   k_dense_fwd   one panel of a forward substitution, unit diagonal (lu) or a division by the real diagonal (cholesky); k_dense_fwd_nb:
+//                 the same panel for a block of right-hand sides
 //   k_dense_trail one 64 x 64 tile of a trailing update, general (A22 -= L21 U12) or Hermitian (A22 -= L21 L21^H, lower tiles)
 // No fma, no matrix cores, no reciprocal (the library is built -ffp-contract=off): a product and the difference that takes it are rounded
 // on their own, and an element meets its k in one fixed order.
@@ -17,6 +19,7 @@ constexpr int MIK_DS_R = 64;            // rows per workgroup of a substitution 
 constexpr int MIK_DS_U = 16;            // column loads per batch; two batches in flight
 constexpr int MIK_DS_T = 64;            // tile edge of a trailing update (rows and columns)
 constexpr int MIK_DS_THREADS = 256;     // workgroup of a trailing update: 16 x 16 lanes, 4 x 4 elements each
+constexpr int MIK_DS_G = 32;            // columns per pass of a block solve: the workspace of a handle is n x G
 static_assert(MIK_DS_W == 64 && MIK_DS_R == MIK_DS_W && MIK_DS_T == 64 && MIK_DS_THREADS == 256, "the tile loaders and the one-wave panels are written for these sizes");
 
 // ---- the element ---------------------------------------------------------------------------------------------------------------------
@@ -45,6 +48,13 @@ template <typename E> __device__ __forceinline__ void de_msub_lc(E &a, E l, E y)
 __device__ __forceinline__ float de_div(float a, float d) { return a / d; }
 __device__ __forceinline__ double de_div(double a, double d) { return a / d; }
 template <typename R> __device__ __forceinline__ de_cx<R> de_div(de_cx<R> a, R d) { return de_cx<R>{a.re / d, a.im / d}; }
+
+// right-hand sides a lane of a block solve carries: 2 of a real type, 1 of a complex one.  The groups of a pass run side by side on
+// different compute units (a solve occupies n / 64 of them), while the NB chains of a lane share one wave's instruction issue in the serial
+// steps of a diagonal block: measured with 8 / 4, 4 / 2 and 2 / 1, every width from 1 to 32 columns was fastest with
+// the smallest, and a complex block gains nothing from a second column per lane.
+template <typename E> struct de_block { static constexpr int NB = sizeof(E) == sizeof(typename de_real<E>::type) ? 2 : 1; };
+static_assert(MIK_DS_G % de_block<double>::NB == 0 && MIK_DS_G % de_block<de_cx<double>>::NB == 0, "a pass is whole groups");
 
 // c ? a : b per component: v_cndmask, where a guarded assignment of a pair becomes an exec-masked block and `?:` on a pair goes through memory
 __device__ __forceinline__ float de_select(bool c, float a, float b) { return c ? a : b; }
@@ -121,6 +131,45 @@ __device__ __forceinline__ E de_walk(E acc, const E *__restrict__ Ar, int64_t ld
     return acc;
 }
 
+// The walk for the NB right-hand sides b a lane of a block solve carries: acc[b] = acc[b] - (Ar[c * ld] * x[c * NB + b]) over all columns c
+// of [lo, hi).  x holds the right-hand sides interleaved (the NB values of a column side by side): a column's values are one uniform
+// load, and every Ar[c * ld] is loaded once and used NB times.  Per b it is de_walk's chain: the same operands in the same order.  The
+// columns are counted down in every element type: recomputed from c, as de_walk does for a complex element, the compiler fetches the
+// 16 NB x values of a batch at once and spills scalar registers (208 in ComplexF64 at NB = 4).
+template <typename E, int NB, bool ASC>
+__device__ __forceinline__ void de_walk_nb(E (&acc)[NB], const E *__restrict__ Ar, int64_t ld, const E *__restrict__ x, int lo, int hi)
+{
+    constexpr int U = MIK_DS_U;
+    int left = hi - lo;
+    int c = ASC ? lo : hi - 1;                      // first column of the current batch, in walking order
+    const auto sub = [&](E a, int cc) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) de_msub(acc[b], a, x[(int64_t)cc * NB + b]);
+    };
+    E cur[U], nxt[U];
+    if (left >= U) {
+#pragma unroll
+        for (int q = 0; q < U; ++q) cur[q] = Ar[(int64_t)(ASC ? c + q : c - q) * ld];
+    }
+    while (left >= U) {
+        const int cn = ASC ? c + U : c - U;
+        const bool more = left >= 2 * U;
+        if (more) {
+#pragma unroll
+            for (int q = 0; q < U; ++q) nxt[q] = Ar[(int64_t)(ASC ? cn + q : cn - q) * ld];
+        }
+#pragma unroll
+        for (int q = 0; q < U; ++q) sub(cur[q], ASC ? c + q : c - q);
+        if (more) {
+#pragma unroll
+            for (int q = 0; q < U; ++q) cur[q] = nxt[q];
+        }
+        c = cn;
+        left -= U;
+    }
+    for (; left > 0; --left, c += ASC ? 1 : -1) sub(Ar[(int64_t)c * ld], c);
+}
+
 // ---- one serial step of a diagonal block: lane = row of the block, j the wave-uniform step.  The quotient of lane j is the block's
 // solution j: every lane receives it, lane j keeps its own in `mine`, and the rows on one side of j (BELOW: lane > j, a forward
 // substitution; else lane < j, a backward one) subtract coeff times it.  UNIT: a unit diagonal, no division: the quotient is acc itself,
@@ -135,6 +184,27 @@ __device__ __forceinline__ void de_step(E &acc, E &mine, R d, E coeff, int j, in
     E s = acc;
     de_msub(s, coeff, bj);
     acc = de_select(BELOW ? lane > j : lane < j, s, acc);
+}
+
+// The step for the NB right-hand sides a lane of a block solve carries.  Every instruction of the serial chain waits for the one before
+// it; the NB quotient, broadcast and subtract sequences wait on nothing of each other's, so written stage by stage they fill those waits.
+// Per right-hand side it is the sequence above: the same operations on the same operands.
+template <bool UNIT, bool BELOW, int NB, typename E, typename R>
+__device__ __forceinline__ void de_step(E (&acc)[NB], E (&mine)[NB], R d, E coeff, int j, int lane)
+{
+    E bj[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {                  // NB independent quotients and broadcasts, side by side in the step
+        const E quo = UNIT ? acc[b] : de_div(acc[b], d);
+        bj[b] = ds_bcast(quo, j);
+        if (!UNIT) mine[b] = de_select(lane == j, quo, mine[b]);
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        E s = acc[b];
+        de_msub(s, coeff, bj[b]);
+        acc[b] = de_select(BELOW ? lane > j : lane < j, s, acc[b]);
+    }
 }
 
 // ---- panel k0 / W of a forward substitution with a lower factor, launched over the rows [k0, n) in workgroups of W rows.  src is the
@@ -171,6 +241,60 @@ __global__ void __launch_bounds__(MIK_DS_R) k_dense_fwd(int n, int k0, const E *
         if (!UNIT) acc = mine;
     }
     if (live) t[r] = acc;
+}
+
+// ---- the NB right-hand sides a lane of a substitution carries.  A solve runs in passes of at most G columns; group blockIdx.y of a pass is
+// its columns [c0, c0 + NB), c0 = blockIdx.y * NB, of which those below `cols` (the pass's column count) are live.  The group's workspace
+// is n rows of NB values side by side, NB * n elements after the previous group's: with NB = 1 and one group, the plain work vector of a
+// vector solve.  A dead column (only the last group has any, and none with NB = 1) carries a copy of the group's first column, which is
+// always live, through the workspace, and nothing of it is stored into Y.
+template <int NB> __device__ __forceinline__ int de_group_first() { return (int)blockIdx.y * NB; }
+template <int NB> __device__ __forceinline__ bool de_col_live(int c0, int b, int cols) { return NB == 1 || c0 + b < cols; }
+
+// ---- k_dense_fwd for a block of right-hand sides: the same panel, launched over the rows (grid x) and the column groups of the pass
+// (grid y).  src, column-major with the leading dimension lds, is the right-hand side in the first launch; src = nullptr afterwards (lu:
+// always, the gather has filled t): the accumulators are in t.
+template <typename E, bool UNIT, int NB>
+__global__ void __launch_bounds__(MIK_DS_R) k_dense_fwd_nb(int n, int k0, const E *__restrict__ A, int64_t ld, const E *src, int64_t lds, int cols, E *t)
+{
+    using R = typename de_real<E>::type;
+    const int lane = (int)threadIdx.x;
+    const int r = k0 + (int)blockIdx.x * MIK_DS_R + lane;
+    const bool live = r < n;
+    const E *Ar = A + (live ? r : k0);
+    const int c0 = de_group_first<NB>();
+    t += (int64_t)c0 * n;
+    E acc[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int col = de_col_live<NB>(c0, b, cols) ? c0 + b : c0;
+        const E *from = src ? src + (int64_t)col * lds + r : t + (int64_t)r * NB + b;      // `?:` on the addresses: on a pair it goes through memory
+        acc[b] = live ? *from : de_zero<E>();
+    }
+    if (k0 > 0) de_walk_nb<E, NB, true>(acc, Ar, ld, t, k0 - MIK_DS_W, k0);
+    if (blockIdx.x == 0) {
+        const int m = min(MIK_DS_W, n - k0);
+        const R d = (!UNIT && live) ? de_re(Ar[(int64_t)r * ld]) : R(1);
+        E mine[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) mine[b] = acc[b];
+        for (int j0 = 0; j0 < m; j0 += MIK_DS_U) {
+            E a[MIK_DS_U];
+#pragma unroll
+            for (int q = 0; q < MIK_DS_U; ++q) a[q] = (j0 + q < m && (UNIT || (lane > j0 + q && live))) ? Ar[(int64_t)(k0 + j0 + q) * ld] : de_zero<E>();
+#pragma unroll
+            for (int q = 0; q < MIK_DS_U; ++q)
+                if (j0 + q < m) de_step<UNIT, true>(acc, mine, d, a[q], j0 + q, lane);      // wave-uniform
+        }
+        if (!UNIT) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) acc[b] = mine[b];
+        }
+    }
+    if (live) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) t[(int64_t)r * NB + b] = acc[b];
+    }
 }
 
 // ---- one tile of a trailing update for the full panel [k0, k0 + W): tile (blockIdx.x, blockIdx.y) of T x T elements from

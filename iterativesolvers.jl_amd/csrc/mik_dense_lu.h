@@ -19,9 +19,11 @@
 //   k_lu_strip   U12 = L11^-1 A12: a lane owns a column, its W values in registers, L11 in LDS, k ascending
 //   k_lu_gather  w[i] = x[perm[i]]: the interchanges of ldiv!
 //   k_lu_bwd     one panel of the backward substitution
+//   k_lu_gather_nb, k_lu_bwd_nb   the two for a block of right-hand sides, NB per lane (ldiv!(Y, F, X)): per column the same operations
+//                on the same operands in the same order, so column j has the bits of the vector solve of column j
 // and, from csrc/mik_dense_elem.h, where the pieces the dense kernels share are written once (the walk de_walk, the serial step de_step):
 //   k_dense_trail<T, false>  A22[i,c] -= L21[i,k] * U12[k,c], k ascending: TR x TC tiles, L21 and U12 tiles in LDS, a 4 x 4 register block per lane
-//   k_dense_fwd<T, true>     one panel of the forward substitution with the unit-lower factor
+//   k_dense_fwd<T, true>     one panel of the forward substitution with the unit-lower factor (k_dense_fwd_nb<T, true, NB>: for a block)
 // Every dependency between workgroups is a kernel boundary; nothing indexes memory through a DATA value (ipiv is clamped to [j, n)
 // where it is produced), so a singular or non-finite matrix cannot fault.  Non-finite data follow the loop too: the pivot search treats a
 // NaN as the loop's comparisons do (lu_key), and everything else is the same operations on the same operands in the same order.
@@ -232,11 +234,26 @@ __global__ void __launch_bounds__(64) k_lu_strip(int n, int k0, T *A, int64_t ld
     }
 }
 
+// w[i, b] = x[perm[i], c0 + b] for the NB columns of group blockIdx.y (de_group_first): perm[i] is loaded once for them.  x is column-major
+// with the leading dimension ldx, w the group's workspace.  x may be the caller's Y: the whole pass is gathered before anything is stored there.
 template <typename T>
 __global__ void __launch_bounds__(256) k_lu_gather(int n, const int *__restrict__ perm, const T *__restrict__ x, T *__restrict__ w)
 {
     const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (i < n) w[i] = x[perm[i]];
+}
+
+// the gather of a block solve
+template <typename T, int NB>
+__global__ void __launch_bounds__(256) k_lu_gather_nb(int n, const int *__restrict__ perm, const T *__restrict__ x, int64_t ldx, int cols, T *__restrict__ w)
+{
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const int c0 = de_group_first<NB>();
+    if (i >= n) return;
+    const int p = perm[i];
+    w += (int64_t)c0 * n;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) w[(int64_t)i * NB + b] = x[(int64_t)(de_col_live<NB>(c0, b, cols) ? c0 + b : c0) * ldx + p];
 }
 
 // Panel [k0, k1) of the backward substitution with the upper factor, launched over the rows [0, k1) in workgroups of W rows.
@@ -270,4 +287,48 @@ __global__ void __launch_bounds__(MIK_DS_R) k_lu_bwd(int n, int k0, int k1, cons
         }
     }
     if (live) { t[r] = mine; y[r] = mine; }
+}
+// k_lu_bwd for a block of right-hand sides.  A lane carries the NB right-hand sides of group blockIdx.y (csrc/mik_dense_elem.h): t is the
+// group's workspace, y column-major with the leading dimension ldy, and only the live columns are stored there.
+template <typename T, int NB>
+__global__ void __launch_bounds__(MIK_DS_R) k_lu_bwd_nb(int n, int k0, int k1, const T *__restrict__ A, int64_t ld, T *t, T *y, int64_t ldy, int cols)
+{
+    const int lane = (int)threadIdx.x;
+    const int r = (int)blockIdx.x * MIK_DS_R + lane;
+    const bool live = r < k1;
+    const T *Ar = A + (live ? r : 0);
+    const int c0 = de_group_first<NB>();
+    t += (int64_t)c0 * n;
+    T acc[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[b] = live ? t[(int64_t)r * NB + b] : T(0);
+    if (k1 < n) de_walk_nb<T, NB, false>(acc, Ar, ld, t, k1, min(k1 + MIK_LU_W, n));
+    if ((int)blockIdx.x * MIK_DS_R != k0) {
+        if (live) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) t[(int64_t)r * NB + b] = acc[b];
+        }
+        return;
+    }
+    const int m = k1 - k0;
+    const T d = live ? Ar[(int64_t)r * ld] : T(1);
+    T mine[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) mine[b] = acc[b];
+    for (int j0 = 0; j0 < m; j0 += MIK_DS_U) {
+        T a[MIK_DS_U];
+#pragma unroll
+        for (int q = 0; q < MIK_DS_U; ++q) a[q] = j0 + q < m ? Ar[(int64_t)(k1 - 1 - j0 - q) * ld] : T(0);
+#pragma unroll
+        for (int q = 0; q < MIK_DS_U; ++q) {
+            const int j = m - 1 - j0 - q;                  // tested as j >= 0: shared with the loads' bound the test becomes a lane mask
+            if (j >= 0) de_step<false, false>(acc, mine, d, a[q], j, lane);                       // wave-uniform
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        t[(int64_t)r * NB + b] = mine[b];
+        if (de_col_live<NB>(c0, b, cols)) y[(int64_t)(c0 + b) * ldy + r] = mine[b];
+    }
 }

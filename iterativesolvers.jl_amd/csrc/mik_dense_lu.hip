@@ -9,11 +9,13 @@
 //   outside   the panel's interchanges on the columns left and right of it, the strip solve U12 = L11^-1 A12, the trailing update
 // Every dependency between workgroups is a kernel boundary on the context's stream.  A zero pivot column records its index and the
 // remaining launches still run; create reads the flag (and the pivots) once at the end -- the factorisation's only host synchronisation.
-// ldiv! is a gather into the handle's work vector and ceil(n / W) launches each way; nothing is allocated per solve.
+// ldiv! is a gather into the handle's work vector and ceil(n / W) launches each way; nothing is allocated per solve.  A block of right-hand
+// sides runs the same launches per pass of MIK_DS_G columns, NB columns per lane, through a workspace the handle allocates at the first one.
 #include "mik_internal.h"
 #include "mik_dense_factor.h"
 #include "mik_dense_lu.h"
 
+#include <type_traits>
 #include <vector>
 
 struct mik_dense_lu : mik_dense_factor {      // aux: the interchanges as one gather, n integers
@@ -108,6 +110,26 @@ int lu_solve_dev(mik_dense_lu *F, T *y, const T *x)
     return MIK_OK;
 }
 
+// one pass of a block solve: the `cols` columns from x to y through the groups of the block workspace t, NB columns per lane
+template <int NB, typename T>
+int lu_solve_block_dev(mik_dense_lu *F, T *t, T *y, int64_t ldy, const T *x, int64_t ldx, int cols)
+{
+    mik_ctx *ctx = F->ctx;
+    hipStream_t st = ctx->stream;
+    const int n = F->n;
+    const T *A = (const T *)F->A;
+    const unsigned groups = dense_grid(cols, NB);
+    hipLaunchKernelGGL((k_lu_gather_nb<T, NB>), dim3(dense_grid(n, 256), groups), dim3(256), 0, st, n, (const int *)F->aux, x, ldx, cols, t);
+    for (int k0 = 0; k0 < n; k0 += MIK_LU_W)
+        hipLaunchKernelGGL((k_dense_fwd_nb<T, true, NB>), dim3(dense_grid(n - k0, MIK_DS_R), groups), dim3(MIK_DS_R), 0, st, n, k0, A, F->ld, (const T *)nullptr, (int64_t)0, cols, t);
+    for (int k0 = (n - 1) / MIK_LU_W * MIK_LU_W; k0 >= 0; k0 -= MIK_LU_W)
+        hipLaunchKernelGGL((k_lu_bwd_nb<T, NB>), dim3((unsigned)(k0 / MIK_DS_R + 1), groups), dim3(MIK_DS_R), 0, st, n, k0, std::min(k0 + MIK_LU_W, n), A, F->ld, t, y, ldy, cols);
+    MIK_LAUNCH_CHECK(ctx);
+    return MIK_OK;
+}
+
+int64_t lu_launches_solve(const mik_dense_lu *F) { return 1 + 2 * (((int64_t)F->n + MIK_LU_W - 1) / MIK_LU_W); }
+
 }  // namespace
 
 extern "C" int mik_dense_lu_create(mik_ctx *ctx, void *A, int64_t n, int64_t ld, int dtype, int64_t *singular_col, mik_dense_lu **out)
@@ -147,6 +169,21 @@ extern "C" int mik_dense_lu_solve(mik_dense_lu *F, void *y, const void *x)
     return dense_dispatch<false>(F->dtype, [&](auto e) { return lu_solve_dev(F, (decltype(e) *)y, (const decltype(e) *)x); });
 }
 
+extern "C" int mik_dense_lu_solve_block(mik_dense_lu *F, void *Y, int64_t ldy, const void *X, int64_t ldx, int64_t nrhs)
+{
+    if (!F || !Y || !X) return MIK_ERR_INVALID;
+    MIK_TRY(dense_check_block(F, "mik_dense_lu_solve_block", Y, ldy, X, ldx, nrhs));
+    return dense_block_passes<false>(F, Y, ldy, X, ldx, nrhs, [&](auto *t, auto *y, auto *x, int cols) {
+        return lu_solve_block_dev<de_block<std::remove_pointer_t<decltype(t)>>::NB>(F, t, y, ldy, x, ldx, cols);
+    });
+}
+
+extern "C" int mik_dev_dense_lu_block_plan(const mik_dense_lu *F, int64_t nrhs, int64_t *nb, int64_t *g, int64_t *passes, int64_t *launches, int64_t *workspace_bytes)
+{
+    if (!F) return MIK_ERR_INVALID;
+    return dense_block_query(F, nrhs, lu_launches_solve(F), nb, g, passes, launches, workspace_bytes);
+}
+
 extern "C" int mik_dense_lu_ldiv_fn(void *user, void *y, const void *x) { return mik_dense_lu_solve((mik_dense_lu *)user, y, x); }
 
 extern "C" int mik_dense_lu_info(const mik_dense_lu *F, int64_t *panel_w, int64_t *search_rows, int64_t *tile_rows, int64_t *tile_cols,
@@ -159,7 +196,7 @@ extern "C" int mik_dense_lu_info(const mik_dense_lu *F, int64_t *panel_w, int64_
     if (tile_cols) *tile_cols = MIK_LU_TC;
     if (one_launch_rows) *one_launch_rows = 0;                 // the one-launch panel is not built
     if (launches_factor) *launches_factor = F->launches_factor;
-    if (launches_solve) *launches_solve = 1 + 2 * (((int64_t)F->n + MIK_LU_W - 1) / MIK_LU_W);
+    if (launches_solve) *launches_solve = lu_launches_solve(F);
     if (bytes) *bytes = F->bytes;
     return MIK_OK;
 }

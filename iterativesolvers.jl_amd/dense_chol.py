@@ -14,6 +14,7 @@ caller vouches for it, as with ``cholesky(Hermitian(A, :L))``.
     cholesky!(Hermitian(A, :L))            cholesky_(A)       factors in place, keeps A alive
     ldiv!(y, F, x) / ldiv!(F, x)           F.ldiv_(y, x) / F.ldiv_(y)
     F \\ b                                  F.solve(b)
+    ldiv!(Y, F, X) / ldiv!(F, X), F \\ B     F.ldiv_(Y, X) / F.ldiv_(Y), F.solve(B)   HipMatrix blocks: one call, each column's bits those of its vector solve
     F.uplo, F.info, issuccess(F)           F.uplo == "L", F.info, F.issuccess()
     cholesky(A; check=false)               cholesky(A, check=False)
     PosDefException(k)                     PosDefException(k)

@@ -11,6 +11,7 @@ bit those of the unblocked loops of ``mik_lu_solve`` (the contract is stated in 
     lu!(A)                               lu_(A)         factors in place, keeps A alive
     ldiv!(y, F, x) / ldiv!(F, x)         F.ldiv_(y, x) / F.ldiv_(y)
     F \\ b                                F.solve(b)
+    ldiv!(Y, F, X) / ldiv!(F, X), F \\ B   F.ldiv_(Y, X) / F.ldiv_(Y), F.solve(B)   HipMatrix blocks: one call, each column's bits those of its vector solve
     F.ipiv                               F.ipiv         1-based, numpy int64
     F.factors                            F.factors      the HipMatrix holding L\\U
 

@@ -1391,6 +1391,16 @@ function LinearAlgebra.ldiv!(y::HipVector{T}, F::HipLU{T}, x::HipVector{T}) wher
 end
 LinearAlgebra.ldiv!(F::HipLU{T}, x::HipVector{T}) where {T} = LinearAlgebra.ldiv!(x, F, x)
 Base.:\(F::HipLU{T}, x::HipVector{T}) where {T} = LinearAlgebra.ldiv!(similar(x), F, x)
+# ldiv!(Y, F, X) / ldiv!(F, X) / F \ X on a block of right-hand sides: one call, every column with the bits of its vector solve
+function LinearAlgebra.ldiv!(Y::HipDenseMatrix{T}, F::HipLU{T}, X::HipDenseMatrix{T}) where {T}
+    (Y.n == F.factors.n && X.n == F.factors.n && Y.cols >= X.cols >= 1) ||
+        throw(DimensionMismatch("ldiv!: blocks of $(Y.n) x $(Y.cols) and $(X.n) x $(X.cols), a factorisation of order $(F.factors.n)"))
+    check(ccall((:mik_dense_lu_solve_block, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int64), F.handle, Y.ptr, Y.ld, X.ptr, X.ld, X.cols),
+          "mik_dense_lu_solve_block", F.ctx.handle)
+    Y
+end
+LinearAlgebra.ldiv!(F::HipLU{T}, X::HipDenseMatrix{T}) where {T} = LinearAlgebra.ldiv!(X, F, X)
+Base.:\(F::HipLU{T}, X::HipDenseMatrix{T}) where {T} = LinearAlgebra.ldiv!(HipDenseMatrix(zeros(T, X.n, X.cols), X.ctx), F, X)
 "panel width, rows per workgroup of the pivot search, tile of the trailing update, row limit of the one-launch panel (0: not built), launches, device bytes"
 function dense_lu_info(F::HipLU)
     w = Ref{Int64}(0); r = Ref{Int64}(0); tr = Ref{Int64}(0); tc = Ref{Int64}(0); one = Ref{Int64}(0); lf = Ref{Int64}(0); ls = Ref{Int64}(0); b = Ref{Int64}(0)
@@ -1445,6 +1455,16 @@ function LinearAlgebra.ldiv!(y::HipVector{T}, F::HipCholesky{T}, x::HipVector{T}
 end
 LinearAlgebra.ldiv!(F::HipCholesky{T}, x::HipVector{T}) where {T} = LinearAlgebra.ldiv!(x, F, x)
 Base.:\(F::HipCholesky{T}, x::HipVector{T}) where {T} = LinearAlgebra.ldiv!(similar(x), F, x)
+# ldiv!(Y, F, X) / ldiv!(F, X) / F \ X on a block of right-hand sides: one call, every column with the bits of its vector solve
+function LinearAlgebra.ldiv!(Y::HipDenseMatrix{T}, F::HipCholesky{T}, X::HipDenseMatrix{T}) where {T}
+    (Y.n == F.factors.n && X.n == F.factors.n && Y.cols >= X.cols >= 1) ||
+        throw(DimensionMismatch("ldiv!: blocks of $(Y.n) x $(Y.cols) and $(X.n) x $(X.cols), a factorisation of order $(F.factors.n)"))
+    MIK.check(ccall((:mik_dense_chol_solve_block, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int64), F.handle, Y.ptr, Y.ld, X.ptr, X.ld, X.cols),
+          "mik_dense_chol_solve_block", F.ctx.handle)
+    Y
+end
+LinearAlgebra.ldiv!(F::HipCholesky{T}, X::HipDenseMatrix{T}) where {T} = LinearAlgebra.ldiv!(X, F, X)
+Base.:\(F::HipCholesky{T}, X::HipDenseMatrix{T}) where {T} = LinearAlgebra.ldiv!(HipDenseMatrix(zeros(T, X.n, X.cols), X.ctx), F, X)
 "panel width, rows per workgroup of the panel kernel, tile of the trailing update, launches, device bytes, info"
 function dense_chol_info(F::HipCholesky)
     w = Ref{Int64}(0); r = Ref{Int64}(0); tr = Ref{Int64}(0); tc = Ref{Int64}(0); lf = Ref{Int64}(0); ls = Ref{Int64}(0); b = Ref{Int64}(0); info = Ref{Int64}(0)

@@ -42,6 +42,7 @@ import numpy as np
 
 from ._lib import MikError, check, dtype_code, lib
 from .api import HipCSR, HipMatrix, Identity, JacobiPrec
+from .dense_factor import DenseFactor
 
 _vp = C.c_void_p
 MAX_BLOCK = 32                                                           # widest block of mik_spmm / mik_dense_mm / mik_block_gram / mik_block_rdiv / mik_block_update
@@ -215,6 +216,9 @@ class DeviceOps:
             return
         if not callable(getattr(P, "ldiv_", None)):
             raise MikError(5, "lobpcg", "the preconditioner needs ldiv_(y, x)")
+        if isinstance(P, DenseFactor) and bs >= P.block_min_cols:        # lu(A) / cholesky(A): one block solve in place, the bits of bs vector solves
+            P.ldiv_(X, cols=bs)
+            return
         for j in range(bs):
             P.ldiv_(temp.col(j), X.col(j))
             X.col(j).copyto_(temp.col(j))
