@@ -853,6 +853,65 @@ int mik_dense_chol_ldiv_fn(void *user, void *y, const void *x);
 int mik_dense_chol_info(const mik_dense_chol *F, int64_t *panel_w, int64_t *rows_per_group, int64_t *tile_rows, int64_t *tile_cols,
                         int64_t *launches_factor, int64_t *launches_solve, int64_t *bytes, int64_t *info);
 
+/* ---- dense QR: qr!(A) (Householder, no pivoting), lmul!(Q, Y), lmul!(Q', Y), F \ b and Matrix(F.Q) on an m x n device matrix, m >= n -----
+ * A \ b for a tall matrix is what the reference's tests hold lsqr and lsmr to (test/lsqr.jl:15-19, test/lsmr.jl:68-72), and Matrix(qr(A).Q) is
+ * how they build an orthonormal basis (test/orthogonalize.jl:17-18).  Added without a version bump, additive; real MIK_F64 / MIK_F32
+ * (MIK_C64 / MIK_C32: MIK_ERR_NOTIMPL with a message that names the element type).
+ * THE BIT CONTRACT (stated in csrc/mik_dense_qr.h, restated as unblocked C99 loops in tests/dense_ref/dense_qr_ref.c).  No fma, no matrix
+ * cores, no reciprocal; `/` and sqrt correctly rounded; a product and the sum or difference that takes it rounded on their own.
+ *   - the reduction T over a range of ABSOLUTE rows i: 256 accumulators starting at +0, accumulator i mod 256 takes acc = acc + p_i in
+ *     ascending i; each group of 64 accumulators is folded by a[l] += a[l + s], s = 32, 16, 8, 4, 2, 1; the four sums are added left to right;
+ *   - column j: alpha = A[j,j], s = T(A[i,j] A[i,j]; j < i < m).  s == 0: tau[j] = 0, nothing stored.  Otherwise nrm = sqrt(alpha alpha + s),
+ *     beta = -copysign(nrm, alpha), tau[j] = (beta - alpha) / beta, A[i,j] = A[i,j] / (alpha - beta) for i > j, A[j,j] = beta;
+ *   - reflector j on a column a: skipped if tau[j] == 0; else w = T(v_i a_i; j <= i < m) with v_j = 1, v_i = A[i,j]; t = tau[j] w;
+ *     a_i = a_i - v_i t.  Ascending j in the factorisation and in Q' y, descending j in Q y;
+ *   - F \ b: t = Q' b on a copy of b, then R x = t[0:n] by the upper chain of mik_dense_lu_solve (per row, descending columns, the division
+ *     by R[i,i] last); Matrix(F.Q) is Q applied to the first n columns of the m x m identity.
+ * RANGE: the sums of squares are not rescaled: a column whose alpha^2 + s overflows, or underflows to a subnormal, follows the loops into
+ * Inf / 0 / reduced accuracy.  Non-finite data follow the loops; nothing indexes memory through a data value.
+ * The device plan is blocked (panels of W columns, one launch per column, one trailing update per panel in which a workgroup owns a column);
+ * an element still meets its reflectors in ascending order, so the bits are the unblocked loop's.  Rows are NOT split across workgroups: a
+ * column is worked on by one compute unit, so a tall matrix of very few columns uses few of them.  Every dependency between workgroups is
+ * a kernel boundary on the ctx stream. */
+typedef struct mik_dense_qr mik_dense_qr;
+/* resident_rows: a launch that applies the reflectors from k0 on keeps the rows [k0, m) of the column a workgroup owns in LDS while
+ * m - k0 <= resident_rows, and streams them through memory otherwise (same bits): lmul, the solve and the thin Q start at 0, the trailing
+ * update of a panel at the panel's first column.  0 = the default, the rows that fit; a larger value is cut to that. */
+typedef struct mik_dense_qr_plan { int64_t resident_rows; } mik_dense_qr_plan;
+/* qr!(A): A (column-major m x n, leading dimension ld, device) is overwritten by R on and above the diagonal and the reflectors' v below
+ * it, and must outlive the handle.  plan may be NULL.  *zero_diag = the 1-based index of the first R[k,k] == 0, or 0: not an error (qr! does
+ * not throw); such a handle multiplies, but refuses to solve.  MIK_ERR_MISMATCH for m < n (DimensionMismatch: a wide matrix is not
+ * offered), n < 1 or ld < m; MIK_ERR_NOTIMPL for m >= 2^31 - 64 (so also n) or a complex dtype.  Synchronises once, at the end. */
+int mik_dense_qr_create(mik_ctx *ctx, void *A, int64_t m, int64_t n, int64_t ld, int dtype, const mik_dense_qr_plan *plan, int64_t *zero_diag,
+                        mik_dense_qr **out);
+int mik_dense_qr_destroy(mik_dense_qr *F);
+/* F.τ: host, n entries of the element type.  No device access. */
+int mik_dense_qr_tau(const mik_dense_qr *F, void *tau);
+/* lmul!(F.Q, Y) (adjoint == 0) or lmul!(F.Q', Y) (adjoint != 0) in place on `ncols` DEVICE columns of m rows, leading dimension ldy;
+ * asynchronous on the ctx stream, one launch.  MIK_ERR_MISMATCH for ldy < m or ncols < 1; MIK_ERR_INVALID when Y overlaps the factors. */
+int mik_dense_qr_lmul(mik_dense_qr *F, int adjoint, void *Y, int64_t ldy, int64_t ncols);
+/* ldiv!(x, F, b) / F \ b: x a DEVICE vector of n, b of m, not modified -- unless x == b, where the first n entries of b become x
+ * (ldiv!(F, b)).  Asynchronous on the ctx stream; nothing is allocated.  MIK_ERR_SINGULAR naming SingularException(k) on a handle whose
+ * zero_diag is k; MIK_ERR_INVALID for any other overlap of x and b or an overlap with the factors. */
+int mik_dense_qr_solve(mik_dense_qr *F, void *x, const void *b);
+/* ldiv!(X, F, B) on DEVICE column-major blocks: X n rows (ldx), B m rows (ldb), nrhs columns.  Column j of X has exactly the bits
+ * mik_dense_qr_solve gives for column j of B.  Passes of at most 32 columns, each the launches of one vector solve, through a workspace of
+ * m x 32 elements allocated at the first block solve and kept (mik_dense_qr_info's bytes does not count it).  X may be B with ldx == ldb.
+ * MIK_ERR_MISMATCH for nrhs < 1, ldx < n or ldb < m; MIK_ERR_INVALID for any other overlap; MIK_ERR_SINGULAR as above. */
+int mik_dense_qr_solve_block(mik_dense_qr *F, void *X, int64_t ldx, const void *B, int64_t ldb, int64_t nrhs);
+/* Matrix(F.Q): Q (DEVICE, m x n, leading dimension ldq) = Q applied to the first n columns of the identity.  Two launches. */
+int mik_dense_qr_thin_q(mik_dense_qr *F, void *Q, int64_t ldq);
+/* F.R: R (DEVICE, n x n, leading dimension ldr) = the upper triangle of the factors, +0 below the diagonal.  One launch. */
+int mik_dense_qr_r(mik_dense_qr *F, void *R, int64_t ldr);
+/* mik_dense_qr_solve as a mik_ldiv_fn (user = the handle), for SQUARE handles only (else MIK_ERR_MISMATCH): Pl / Pr of the fused iterables. */
+int mik_dense_qr_ldiv_fn(void *user, void *y, const void *x);
+/* panel_w: W; accumulators: those of T (256); resident_rows: the row limit in use; resident: 1 if the launches that start at reflector 0 (lmul,
+ * solve, thin Q) keep their column in LDS (m <= resident_rows), 0 if they stream; launches_factor: kernel launches the factorisation made (n, plus one per panel that has
+ * columns to its right); launches_solve: launches of one solve (1 + ceil(n / 64)); bytes: device memory held besides A; zero_diag as in
+ * create.  Any pointer may be NULL. */
+int mik_dense_qr_info(const mik_dense_qr *F, int64_t *panel_w, int64_t *accumulators, int64_t *resident_rows, int64_t *resident,
+                      int64_t *launches_factor, int64_t *launches_solve, int64_t *bytes, int64_t *zero_diag);
+
 /* ---- svdl: Golub-Kahan-Lanczos bidiagonalisation with thick restart (src/svdl.jl) ------------------------------------------
  * The Lanczos loop of extend! (:542-609) runs on mik_spmv (A and its adjoint as two operators), mik_gemv_t / mik_gemv_n and the fused
  * sweeps above; the k x k SVD of a restart stays on the host.  Two things no entry above does in one pass (added without a version bump,

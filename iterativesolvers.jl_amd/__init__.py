@@ -12,6 +12,7 @@ The directory name (``iterativesolvers.jl_amd``) is not a Python identifier; loa
   dense_factor.py  what dense_lu.py and dense_chol.py share: the refusals, the handle, ldiv_ / solve, "factor a copy"
   dense_lu.py  lu / lu_ of a dense HipMatrix (partial pivoting on the device) and its ldiv_: the exact Pl / Pr of the reference's tests
   dense_chol.py  cholesky / cholesky_ of a dense HipMatrix, real or complex (lower form, on the device) and its ldiv_: the Pl of test/cg.jl:44-47
+  dense_qr.py  qr / qr_ of an m x n dense HipMatrix, m >= n (Householder, on the device): lmul with Q and Q', the least-squares solve, the thin Q, and ldiv (A \\ b)
   svdl.py    svdl: Golub-Kahan-Lanczos SVD with thick restart (src/svdl.jl) on a HipCSR uploaded with its adjoint, or on a HipMatrix
   lobpcg.py  lobpcg: block eigensolver (src/lobpcg.jl) on HipCSR operators, with dense=True also on dense HipMatrix ones, every sweep on a block of columns
   extras.py  solvers outside the scope contract (IDR(s), LSQR, LSMR, QMR, power method); kept apart, unjudged
@@ -38,6 +39,7 @@ from .stationary_dense import (DenseGaussSeidelIterable, DenseJacobiIterable, De
                                jacobi_iterable, sor, sor_, sor_iterable, ssor, ssor_, ssor_iterable)   # dispatch: HipCSR -> stationary.py
 from .dense_lu import DenseLU, lu, lu_                   # noqa: F401
 from .dense_chol import DenseCholesky, cholesky, cholesky_   # noqa: F401
+from .dense_qr import DenseQR, ldiv, qr, qr_                # noqa: F401
 from .svdl import (BrokenArrowBidiagonal, PartialFactorization, svdl, svdl_method_, isconverged, build, thickrestart_,   # noqa: F401
                    harmonicrestart_, extend_, ArgumentError, BoundsError, SvdlBreakdown, SVD)
 from .lobpcg import (LOBPCGIterator, LOBPCGResults, LOBPCGState, LobpcgCholeskyError, LobpcgRefusal, lobpcg, lobpcg_)   # noqa: F401

@@ -243,6 +243,16 @@ SIGNATURES = {
     "mik_dense_chol_solve_block": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64]),
     "mik_dense_chol_ldiv_fn": (C.c_int, [_vp, _vp, _vp]),
     "mik_dense_chol_info": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p]),
+    "mik_dense_qr_create": (C.c_int, [_vp, _vp, _i64, _i64, _i64, C.c_int, _i64p, _i64p, C.POINTER(_vp)]),    # plan: NULL or a pointer to its one int64
+    "mik_dense_qr_destroy": (C.c_int, [_vp]),
+    "mik_dense_qr_tau": (C.c_int, [_vp, _vp]),
+    "mik_dense_qr_lmul": (C.c_int, [_vp, C.c_int, _vp, _i64, _i64]),
+    "mik_dense_qr_solve": (C.c_int, [_vp, _vp, _vp]),
+    "mik_dense_qr_solve_block": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64]),
+    "mik_dense_qr_thin_q": (C.c_int, [_vp, _vp, _i64]),
+    "mik_dense_qr_r": (C.c_int, [_vp, _vp, _i64]),
+    "mik_dense_qr_ldiv_fn": (C.c_int, [_vp, _vp, _vp]),
+    "mik_dense_qr_info": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p]),
     "mik_dense_mul_shape": (C.c_int, [_ip, _ip]),
     "mik_dense_mul_shape_for": (C.c_int, [C.c_int, _ip, _ip]),
     "mik_dense_create": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _i64, C.POINTER(_vp)]),

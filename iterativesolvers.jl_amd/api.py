@@ -614,7 +614,9 @@ class _Bound:
         if isinstance(P, JacobiPrec):
             return _lib.MikPrecond(P.diagonal.ptr, _lib.LDIV_FN(), None)
         from .dense_factor import DenseFactor                            # (dense_factor imports this module)
-        if isinstance(P, DenseFactor):                                   # lu / cholesky: the library's own callback, no Python frame per ldiv!
+        if isinstance(P, DenseFactor):                                   # lu / cholesky / a square qr: the library's own callback, no Python frame per ldiv!
+            if getattr(P, "m", P.n) != P.n:
+                raise ValueError(f"DimensionMismatch: the {P._name} of a {P.m} x {P.n} matrix is no preconditioner: only a square one is")
             if P.n != self.n or P.dtype != self.dtype:                   # the callback never sees the vector lengths
                 raise ValueError(f"DimensionMismatch: the {P._name} of a {P.n} x {P.n} {P.dtype} matrix as a preconditioner of {self.n}-vectors of {self.dtype}")
             self.keep.append(P)

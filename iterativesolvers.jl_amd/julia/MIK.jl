@@ -427,6 +427,10 @@ function precond_struct(P, ::Type{T}, n::Int, ctx::Context, keep::Vector{Any}) w
         push!(keep, P)
         return chol_precond_struct(P, T, n)
     end
+    if P isa HipQR                                               # a square one only
+        push!(keep, P)
+        return qr_precond_struct(P, T, n)
+    end
     box = CallbackBox{T}(P, n, ctx); push!(keep, box)
     MikPrecond(C_NULL, @cfunction(ldiv_trampoline, Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid})), pointer_from_objref(box))
 end
@@ -1475,6 +1479,106 @@ end
 function chol_precond_struct(F::HipCholesky, ::Type{T}, n::Int) where {T}
     (eltype(F) == T && F.factors.n == n) || throw(DimensionMismatch("the cholesky of a $(F.factors.n) x $(F.factors.n) $(eltype(F)) matrix as a preconditioner of $n-vectors of $T"))
     MikPrecond(C_NULL, cglobal((:mik_dense_chol_ldiv_fn, libmik)), F.handle)
+end
+
+# ---- dense QR: qr(A) / qr!(A) (Householder, no pivoting) of an m x n dense device matrix, m >= n; lmul!(F.Q, Y), lmul!(F.Q', Y), F \ b and
+# ---- Matrix(F.Q) (csrc/mik_dense_qr.hip).  A \ b for a tall matrix is what the reference's tests hold lsqr and lsmr to (test/lsqr.jl:15-19,
+# test/lsmr.jl:68-72); Matrix(qr(A).Q) is their orthonormal basis (test/orthogonalize.jl:17-18).  Factors, tau, products and solution have
+# the bits of the unblocked loops stated in include/mik.h.  Float64 / Float32.
+mutable struct HipQR{T}
+    handle::Ptr{Cvoid}
+    factors::HipDenseMatrix{T}       # R on and above the diagonal, the reflectors below it; kept alive with the handle
+    τ::Vector{T}
+    zero_diag::Int64                 # 0, or the first k with R[k,k] == 0: F \ b then throws SingularException(k)
+    ctx::Context
+end
+struct HipQRQ{T}                     # F.Q
+    F::HipQR{T}
+end
+struct HipQRQAdjoint{T}              # F.Q'
+    F::HipQR{T}
+end
+function LinearAlgebra.qr!(A::HipDenseMatrix{T}; resident_rows::Integer = 0) where {T}
+    size(A, 1) >= size(A, 2) || throw(DimensionMismatch("the matrix is $(size(A, 1)) x $(size(A, 2)): qr of a wide matrix is not offered"))
+    h = Ref{Ptr{Cvoid}}(C_NULL); col = Ref{Int64}(0); plan = Ref{Int64}(resident_rows)
+    check(ccall((:mik_dense_qr_create, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Cint, Ptr{Int64}, Ref{Int64}, Ref{Ptr{Cvoid}}),
+                A.ctx.handle, A.ptr, A.n, A.cols, A.ld, dtype_code(T), resident_rows == 0 ? Ptr{Int64}(C_NULL) : Base.unsafe_convert(Ptr{Int64}, plan), col, h),
+          "mik_dense_qr_create", A.ctx.handle)
+    τ = Vector{T}(undef, A.cols)
+    check(ccall((:mik_dense_qr_tau, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), h[], τ), "mik_dense_qr_tau", A.ctx.handle)
+    F = HipQR{T}(h[], A, τ, col[], A.ctx)
+    finalizer(o -> alive(o.ctx) && ccall((:mik_dense_qr_destroy, libmik), Cint, (Ptr{Cvoid},), o.handle), F)
+    F
+end
+function LinearAlgebra.qr(A::HipDenseMatrix{T}; resident_rows::Integer = 0) where {T}        # factors a copy
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mik_malloc, libmik), Cint, (Ptr{Cvoid}, Csize_t, Ref{Ptr{Cvoid}}), A.ctx.handle, A.ld * max(A.cols, 1) * sizeof(T), p), "mik_malloc", A.ctx.handle)
+    m = HipDenseMatrix{T}(p[], A.n, A.cols, A.ld, A.ctx)
+    finalizer(x -> alive(x.ctx) && ccall((:mik_free, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), x.ctx.handle, x.ptr), m)
+    check(ccall((:mik_copy, libmik), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}), A.ctx.handle, dtype_code(T), A.ld * A.cols, A.ptr, m.ptr),
+          "mik_copy", A.ctx.handle)
+    LinearAlgebra.qr!(m; resident_rows = resident_rows)
+end
+Base.size(F::HipQR) = size(F.factors)
+Base.size(F::HipQR, d::Integer) = size(F.factors, d)
+Base.eltype(::HipQR{T}) where {T} = T
+Base.getproperty(F::HipQR, s::Symbol) = s === :Q ? HipQRQ(F) : getfield(F, s)
+Base.adjoint(Q::HipQRQ) = HipQRQAdjoint(Q.F)
+Base.adjoint(Q::HipQRQAdjoint) = HipQRQ(Q.F)
+function qr_lmul!(F::HipQR{T}, adjoint::Bool, ptr::Ptr{Cvoid}, rows::Int, ld::Int, cols::Int) where {T}
+    rows == F.factors.n || throw(DimensionMismatch("lmul!: $rows rows, a factorisation of $(F.factors.n) x $(F.factors.cols)"))
+    check(ccall((:mik_dense_qr_lmul, libmik), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Int64), F.handle, adjoint ? 1 : 0, ptr, ld, cols), "mik_dense_qr_lmul", F.ctx.handle)
+end
+LinearAlgebra.lmul!(Q::HipQRQ{T}, y::HipVector{T}) where {T} = (qr_lmul!(Q.F, false, y.ptr, length(y), length(y), 1); y)
+LinearAlgebra.lmul!(Q::HipQRQAdjoint{T}, y::HipVector{T}) where {T} = (qr_lmul!(Q.F, true, y.ptr, length(y), length(y), 1); y)
+LinearAlgebra.lmul!(Q::HipQRQ{T}, Y::HipDenseMatrix{T}) where {T} = (qr_lmul!(Q.F, false, Y.ptr, Y.n, Y.ld, Y.cols); Y)
+LinearAlgebra.lmul!(Q::HipQRQAdjoint{T}, Y::HipDenseMatrix{T}) where {T} = (qr_lmul!(Q.F, true, Y.ptr, Y.n, Y.ld, Y.cols); Y)
+function Base.Matrix(Q::HipQRQ{T}) where {T}                    # the thin Q, m x n, on the device
+    F = Q.F
+    out = HipDenseMatrix(zeros(T, F.factors.n, F.factors.cols), F.ctx)
+    check(ccall((:mik_dense_qr_thin_q, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), F.handle, out.ptr, out.ld), "mik_dense_qr_thin_q", F.ctx.handle)
+    out
+end
+function qr_R(F::HipQR{T}) where {T}                            # F.R as a new n x n device matrix
+    out = HipDenseMatrix(zeros(T, F.factors.cols, F.factors.cols), F.ctx)
+    check(ccall((:mik_dense_qr_r, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), F.handle, out.ptr, out.ld), "mik_dense_qr_r", F.ctx.handle)
+    out
+end
+function LinearAlgebra.ldiv!(x::HipVector{T}, F::HipQR{T}, b::HipVector{T}) where {T}
+    (length(b) == F.factors.n && length(x) == (x === b ? F.factors.n : F.factors.cols)) ||
+        throw(DimensionMismatch("ldiv!: vectors of $(length(x)) and $(length(b)), a factorisation of $(F.factors.n) x $(F.factors.cols)"))
+    F.zero_diag == 0 || throw(LinearAlgebra.SingularException(Int(F.zero_diag)))
+    check(ccall((:mik_dense_qr_solve, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), F.handle, x.ptr, b.ptr), "mik_dense_qr_solve", F.ctx.handle)
+    x
+end
+LinearAlgebra.ldiv!(F::HipQR{T}, b::HipVector{T}) where {T} = LinearAlgebra.ldiv!(b, F, b)
+Base.:\(F::HipQR{T}, b::HipVector{T}) where {T} = LinearAlgebra.ldiv!(HipVector(zeros(T, F.factors.cols), F.ctx), F, b)
+function LinearAlgebra.ldiv!(X::HipDenseMatrix{T}, F::HipQR{T}, B::HipDenseMatrix{T}) where {T}
+    (B.n == F.factors.n && X.n == (X === B ? F.factors.n : F.factors.cols) && X.cols >= B.cols >= 1) ||
+        throw(DimensionMismatch("ldiv!: blocks of $(X.n) x $(X.cols) and $(B.n) x $(B.cols), a factorisation of $(F.factors.n) x $(F.factors.cols)"))
+    F.zero_diag == 0 || throw(LinearAlgebra.SingularException(Int(F.zero_diag)))
+    check(ccall((:mik_dense_qr_solve_block, libmik), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int64), F.handle, X.ptr, X.ld, B.ptr, B.ld, B.cols),
+          "mik_dense_qr_solve_block", F.ctx.handle)
+    X
+end
+LinearAlgebra.ldiv!(F::HipQR{T}, B::HipDenseMatrix{T}) where {T} = LinearAlgebra.ldiv!(B, F, B)
+Base.:\(F::HipQR{T}, B::HipDenseMatrix{T}) where {T} = LinearAlgebra.ldiv!(HipDenseMatrix(zeros(T, F.factors.cols, B.cols), B.ctx), F, B)
+"A \\ b on a dense device matrix: lu for a square one, qr (least squares) for a tall one; a wide one is refused"
+function Base.:\(A::HipDenseMatrix{T}, b::Union{HipVector{T}, HipDenseMatrix{T}}) where {T}
+    size(A, 1) >= size(A, 2) || throw(DimensionMismatch("A \\ b of a wide matrix ($(size(A, 1)) x $(size(A, 2))): the minimum-norm solution is not offered"))
+    size(A, 1) == size(A, 2) ? LinearAlgebra.lu(A) \ b : LinearAlgebra.qr(A) \ b
+end
+"panel width, accumulators of a reduction, the row limit of the LDS-resident form and whether the handle is within it, launches, device bytes, zero_diag"
+function dense_qr_info(F::HipQR)
+    w = Ref{Int64}(0); a = Ref{Int64}(0); rr = Ref{Int64}(0); r = Ref{Int64}(0); lf = Ref{Int64}(0); ls = Ref{Int64}(0); b = Ref{Int64}(0); z = Ref{Int64}(0)
+    check(ccall((:mik_dense_qr_info, libmik), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                F.handle, w, a, rr, r, lf, ls, b, z), "mik_dense_qr_info", F.ctx.handle)
+    (W = w[], accumulators = a[], resident_rows = rr[], resident = r[] != 0, launches_factor = lf[], launches_solve = ls[], bytes = b[], zero_diag = z[])
+end
+function qr_precond_struct(F::HipQR, ::Type{T}, n::Int) where {T}
+    (eltype(F) == T && F.factors.n == n && F.factors.cols == n) ||
+        throw(DimensionMismatch("the qr of a $(F.factors.n) x $(F.factors.cols) $(eltype(F)) matrix as a preconditioner of $n-vectors of $T"))
+    MikPrecond(C_NULL, cglobal((:mik_dense_qr_ldiv_fn, libmik)), F.handle)
 end
 
 end # module
